@@ -19,6 +19,15 @@ search) plus the merge.
 Inputs (query, documents) are resident in HBM before the timed region.
 value = compares processed by all ranks / (max over ranks of the time).
 
+A plain run sets up, warms up, times the K steps and prints the headline line
+(metric, value, unit, ms_per_step, dtype, config). --dump-outputs DIR also
+writes what the last timed step returned (accumulators, threshold bits,
+top-k) as DIR/<name>.npy; the inputs depend on the arguments alone, so two
+builds can be compared output for output. --full adds, after the timed steps,
+everything else the line can carry: HIP-event profiling of the steps and the
+rooflines, parity against the clear restatement, the leveled-only, host-buffer
+and all-gather timings, the top-k check and the CPU oracle baseline.
+
 Launch: python bench.py [--gpus N --steps K --warmup W]. For N > 1 either
 under torch.distributed.run (one process per GPU, RCCL = backend "nccl";
 WORLD_SIZE must equal --gpus), or directly: the process then starts the N
@@ -66,7 +75,13 @@ def parse():
     ap.add_argument("--top-k", type=int, default=10)
     ap.add_argument("--min-similarity", type=float, default=0.5)
     ap.add_argument("--seed", type=int, default=1234)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline: HIP-event profiling of "
+                         "the steps and the rooflines, parity against the clear restatement and the oracle, the "
+                         "leveled / host-buffer / all-gather timings, the top-k check and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-compares", type=int, default=0,
                     help="oracle sample size (0: 64 compares scaled down by the sign plan's cost, 10-30 s)")
     ap.add_argument("--mode", choices=("compare", "corpus", "embed", "lut"), default="compare",
@@ -81,7 +96,34 @@ def parse():
     ap.add_argument("--seq-len", type=int, default=100, help="--mode embed: tokens per sequence (max_length)")
     ap.add_argument("--embed-precision", choices=("f32", "bf16"), default="f32",
                     help="--mode embed: the encoder's arithmetic (f32: the reference's, on the f32 MFMA)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all files of one run together
+DUMP_SAMPLE_SEED = 20240229    # the fixed sample of an output that is larger
+
+
+def dump_outputs(dir_, arrays: dict, rank: int = 0) -> None:
+    """--dump-outputs: every array of `arrays` (what the last timed step
+    returned) as DIR/<name>.npy, float32 for a float32 tensor and float64 for
+    everything else (the integers of this project are below 2^53 except raw
+    ciphertext words, which round). Each array gets an equal share of
+    DUMP_MAX_BYTES; a larger one is cut to a fixed seeded sample of its
+    flattened elements, in index order. Ranks above 0 write <name>_rank<r>.npy."""
+    d = Path(dir_)
+    d.mkdir(parents=True, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(d / (f"{name}.npy" if rank == 0 else f"{name}_rank{rank}.npy"), a)
 
 
 def _free_port() -> int:
@@ -453,7 +495,8 @@ def main():
         step()
     torch.cuda.synchronize()
 
-    eng.profile(True)
+    if args.full:
+        eng.profile(True)
     if dist_on():
         torch.distributed.barrier()
     torch.cuda.synchronize()
@@ -464,9 +507,8 @@ def main():
     if dist_on():
         torch.distributed.barrier()
     elapsed = time.perf_counter() - t0
-    eng.profile(False)
-    br = read_br(eng)
-    ks = eng.profile_read("keyswitch")
+    if args.full:
+        eng.profile(False)
 
     if dist_on():
         on_dev = torch.distributed.get_backend() == "nccl"
@@ -478,21 +520,8 @@ def main():
     value = compares / elapsed
     ms_step = elapsed / args.steps * 1e3
 
-    roof = roofline(p, br, B, isolated_br(eng, br, B) if pipelined(B) else None)
-    # every rank checks its own shard against the clear restatement of the
-    # reference path; the flags meet in one all-reduce (MIN)
-    par = shard_parity(args, model, q_np, docs_np, acc, below, T)
-    if dist_on():
-        flags = torch.tensor([int(par["acc_bit_exact"]), int(par["threshold_bit_exact"]),
-                              int(par["quant_params_equal"]), par["compares_checked"]], dtype=torch.int64)
-        on_dev = torch.distributed.get_backend() == "nccl"
-        mins, tot = flags[:3].to(dev if on_dev else "cpu"), flags[3:].to(dev if on_dev else "cpu")
-        torch.distributed.all_reduce(mins, op=torch.distributed.ReduceOp.MIN)
-        torch.distributed.all_reduce(tot, op=torch.distributed.ReduceOp.SUM)
-        mins, tot = mins.cpu().tolist(), int(tot.item())
-        par = {"compares_checked": tot, "ranks": world, "acc_bit_exact": bool(mins[0]),
-               "threshold_bit_exact": bool(mins[1]), "quant_params_equal": bool(mins[2])}
-        allgather_ms = time_allgather(args.top_k, dev, on_dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"acc": acc, "below": below, "topk_acc": oa, "topk_index": oi}, rank)
 
     out = {
         "metric": METRIC,
@@ -519,9 +548,42 @@ def main():
             "params": p.as_dict(), "parallelism": f"shard{world}",
         },
         "pbs_per_sec": round(value * n_pbs, 1),
-        "roofline": roof,
-        "keyswitch_ms_total": round(ks["total_ms"], 3),
     }
+    if args.full:
+        full_report(args, out, model, world, rank, dev, q_np, docs_np, q_dev, d_dev, T, acc, below, oa, oi)
+    elif dist_on():
+        out["dist"] = dist_info(dev)
+
+    share_note(out, world)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if dist_on():
+        torch.distributed.destroy_process_group()
+
+
+def full_report(args, out, model, world, rank, dev, q_np, docs_np, q_dev, d_dev, T, acc, below, oa, oi) -> None:
+    """--full: everything the compare line carries beside the headline, from
+    the profiled timed steps and from runs of its own after them."""
+    eng = model.engine
+    B = docs_np.shape[0]
+    br = read_br(eng)
+    ks = eng.profile_read("keyswitch")
+    out["roofline"] = roofline(eng.params, br, B, isolated_br(eng, br, B) if pipelined(B) else None)
+    out["keyswitch_ms_total"] = round(ks["total_ms"], 3)
+    # every rank checks its own shard against the clear restatement of the
+    # reference path; the flags meet in one all-reduce (MIN)
+    par = shard_parity(args, model, q_np, docs_np, acc, below, T)
+    if dist_on():
+        flags = torch.tensor([int(par["acc_bit_exact"]), int(par["threshold_bit_exact"]),
+                              int(par["quant_params_equal"]), par["compares_checked"]], dtype=torch.int64)
+        on_dev = torch.distributed.get_backend() == "nccl"
+        mins, tot = flags[:3].to(dev if on_dev else "cpu"), flags[3:].to(dev if on_dev else "cpu")
+        torch.distributed.all_reduce(mins, op=torch.distributed.ReduceOp.MIN)
+        torch.distributed.all_reduce(tot, op=torch.distributed.ReduceOp.SUM)
+        mins, tot = mins.cpu().tolist(), int(tot.item())
+        par = {"compares_checked": tot, "ranks": world, "acc_bit_exact": bool(mins[0]),
+               "threshold_bit_exact": bool(mins[1]), "quant_params_equal": bool(mins[2])}
+        allgather_ms = time_allgather(args.top_k, dev, on_dev)
 
     out["parity"] = par
     out["leveled_score"] = leveled_score(args, model, q_dev, d_dev, acc)
@@ -541,12 +603,6 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_leg(args, model, q_np, docs_np, par)
 
-    share_note(out, world)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist_on():
-        torch.distributed.destroy_process_group()
-
 
 def dist_info(dev) -> dict:
     """What ran the collectives: the backend and, for RCCL, the device it is
@@ -564,7 +620,9 @@ def share_note(out: dict, world: int) -> None:
     if world > ngpu:
         note = f"{world} ranks share {ngpu} GPU(s): kernel launch times overlap other ranks' kernels"
         out["config"]["gpu_sharing"] = note
-        raw = out.pop("roofline", None)
+        if "roofline" not in out:
+            return
+        raw = out.pop("roofline")
         out["roofline"] = {"per_gpu": False, "note": note + "; the fraction below is not a per-GPU roofline",
                            "shared_raw": raw}
 
@@ -798,11 +856,10 @@ def lut_main(args, world, rank, local, dev):
     table bootstrap of all of them into P-bit outputs (a random signed
     table). The default gadget is the set's most precise multi-bit one, the
     sign extraction's kernel family (P = 16: (15,2), k_blind_rotate_mb<2, 0,
-    15, BrTvLut>). Every output is decrypted against lut[m]; four phases
-    against the oracle's ref_pbs_table_gadget on the same keys; the sign
-    path's kernel on the same gadget and inputs is timed beside it."""
-    from dataclasses import replace
-    from fheicp.engine import Engine, u64
+    15, BrTvLut>). With --full every output is decrypted against lut[m]; four
+    phases against the oracle's ref_pbs_table_gadget on the same keys; the
+    sign path's kernel on the same gadget and inputs is timed beside it."""
+    from fheicp.engine import Engine
     from fheicp.params import gadget_of, params_for_bits
     P, lb, B = args.lut_msg_bits, args.lut_bits, args.docs
     p = params_for_bits(P)
@@ -817,7 +874,6 @@ def lut_main(args, world, rank, local, dev):
     ct = eng.encrypt(m, seed=args.seed + 4)
     eng.set_msg_bits(P)
     lut_d = eng.to_dev(lut)
-    small = eng.keyswitch(ct, 0, 0)
 
     def step():
         sm = eng.keyswitch(ct, 0, 0)
@@ -826,13 +882,43 @@ def lut_main(args, world, rank, local, dev):
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    eng.profile(True)
+    if args.full:
+        eng.profile(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = step()
     torch.cuda.synchronize()
     secs = time.perf_counter() - t0
-    eng.profile(False)
+    if args.full:
+        eng.profile(False)
+    bl, lv, grp = gadget_of(p, gad)
+    value = B * args.steps / secs
+    line = {
+        "metric": "programmable bootstraps/sec (table PBS, key switch + blind rotation), 1 GPU",
+        "value": round(value, 1), "unit": "PBS/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(secs / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+        "config": {"workload": f"table bootstrap of {B} ciphertexts: {lb}-bit inputs -> {P}-bit outputs "
+                               f"(random signed table), params_for_bits({P}), gadget {gad} ({bl},{lv}) "
+                               f"{'multi-bit' if grp == 2 else 'classic'}",
+                   "ciphertexts": B, "lut_bits": lb, "msg_bits_P": P, "gadget": [bl, lv, grp]},
+    }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"decrypted": eng.decrypt(out), "ciphertexts": out})
+    if args.full:
+        lut_full_report(args, line, eng, p, gad, ct, lut, lut_d, m, out)
+    print(json.dumps(line), flush=True)
+
+
+def lut_full_report(args, line, eng, p, gad, ct, lut, lut_d, m, out) -> None:
+    """--full of --mode lut: the roofline of the profiled steps, every output
+    decrypted against the table, the sign path's kernel on the same inputs
+    and the oracle's table bootstrap (phases and CPU baseline)."""
+    from dataclasses import replace
+    from fheicp.engine import u64
+    from fheicp.params import gadget_of
+    lb, B = args.lut_bits, args.docs
+    small = eng.keyswitch(ct, 0, 0)
     bucket = {0: "blind_rotate_main", 1: "blind_rotate_fast", 2: "blind_rotate_fast2", 3: "blind_rotate_mid",
               4: "blind_rotate_mid2", 5: "blind_rotate_mid0"}[gad]
     br = eng.profile_read(bucket)
@@ -875,17 +961,8 @@ def lut_main(args, world, rank, local, dev):
         oracle["cpu_baseline"] = {"value": round(cnt / cpu_s, 3), "unit": "PBS/s", "cores": nthr, "kind": "port",
                                   "sample": f"{cnt} table bootstraps (ref_pbs_table_gadget, exact integer "
                                             f"restatement, OpenMP over the host cores)"}
-    value = B * args.steps / secs
     tf = k["achieved_tflops_f64"]
-    line = {
-        "metric": "programmable bootstraps/sec (table PBS, key switch + blind rotation), 1 GPU",
-        "value": round(value, 1), "unit": "PBS/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(secs / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-        "config": {"workload": f"table bootstrap of {B} ciphertexts: {lb}-bit inputs -> {P}-bit outputs "
-                               f"(random signed table), params_for_bits({P}), gadget {gad} ({bl},{lv}) "
-                               f"{'multi-bit' if grp == 2 else 'classic'}",
-                   "ciphertexts": B, "lut_bits": lb, "msg_bits_P": P, "gadget": [bl, lv, grp]},
+    line.update({
         "parity": {"outputs_checked": B, "decrypt_equal_lut": exact, "oracle": oracle},
         "roofline": {"kernel": k["kernel"], "bound": "f64-valu", "achieved": round(tf, 3),
                      "peak": F64_VALU_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(tf / F64_VALU_PEAK_TFLOPS, 4),
@@ -899,10 +976,9 @@ def lut_main(args, world, rank, local, dev):
         "keyswitch_ms_per_launch": round(ks["total_ms"] / max(ks["launches"], 1), 4),
         "sign_path_kernel": {"kernel": sign_kernel, "avg_launch_ms": round(sign_ms, 4),
                              "table_over_sign": round(k["avg_launch_ms"] / sign_ms, 4) if sign_ms else None},
-    }
+    })
     if oracle.get("cpu_baseline"):
         line["cpu_baseline"] = oracle.pop("cpu_baseline")
-    print(json.dumps(line), flush=True)
 
 
 def corpus_main(args, world, rank, local, dev):
@@ -940,7 +1016,8 @@ def corpus_main(args, world, rank, local, dev):
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    eng.profile(True)
+    if args.full:
+        eng.profile(True)
     if dist_on():
         torch.distributed.barrier()
     torch.cuda.synchronize()
@@ -951,15 +1028,16 @@ def corpus_main(args, world, rank, local, dev):
     if dist_on():
         torch.distributed.barrier()
     elapsed = time.perf_counter() - t0
-    eng.profile(False)
-    br = read_br(eng)
-    ks = eng.profile_read("keyswitch")
+    if args.full:
+        eng.profile(False)
     if dist_on():
         on_dev = torch.distributed.get_backend() == "nccl"
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if on_dev else "cpu")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     value = world * B * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"acc": acc, "below": below, "topk_acc": oa, "topk_index": oi}, rank)
     out = {
         "metric": METRIC + " [encrypted-corpus mode]",
         "value": round(value, 2), "unit": "compares/s", "n_gpus": world, "steps": args.steps,
@@ -974,10 +1052,12 @@ def corpus_main(args, world, rank, local, dev):
             "corpus_bytes_per_doc": 8 * (args.dim + 1), "params": p.as_dict(), "parallelism": f"shard{world}",
         },
         "pbs_per_sec": round(value * n_pbs, 1),
-        "roofline": roofline(p, br, B),
-        "keyswitch_ms_total": round(ks["total_ms"], 3),
     }
-    if rank == 0:
+    if args.full:
+        br = read_br(eng)
+        out["roofline"] = roofline(p, br, B)
+        out["keyswitch_ms_total"] = round(eng.profile_read("keyswitch")["total_ms"], 3)
+    if rank == 0 and args.full:
         from oracle import quant_ref as Q
         X, y = __import__("fheicp.datagen", fromlist=["x"]).training_pairs(args.dim, 1000, seed=args.seed + 1)
         oq = Q.fit_quantized_linear(X, y, args.n_bits)
@@ -995,6 +1075,7 @@ def corpus_main(args, world, rank, local, dev):
         }
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = corpus_cpu_leg(args, c, bodies, ids, oq, cq, q_np, docs_np, P, out["parity"])
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist_on():
         torch.distributed.destroy_process_group()
@@ -1039,7 +1120,7 @@ def embed_main(args, world, rank, local, dev):
     bert-base (the weights are an offline download; synthetic token ids,
     every sequence --seq-len tokens). One step = one forward pass + mean
     pooling of --embed-batch sequences, in --embed-precision (f32, the
-    reference's arithmetic, by default). Roofline: the MFMA GEMMs
+    reference's arithmetic, by default). With --full, the roofline: the MFMA GEMMs
     (algorithmic 2*M*N*K per launch over their HIP-event time) against the
     dense peak of that arithmetic (f32-input or bf16 MFMA); the CPU baseline
     is the reference's own torch fp32 forward on the host cores, on a
@@ -1050,7 +1131,6 @@ def embed_main(args, world, rank, local, dev):
     m = BertModel(BertConfig(), add_pooling_layer=False).eval()
     prec = args.embed_precision
     g = GpuBert(model=m, device=local, precision=prec)
-    peak = F32_MFMA_PEAK_TFLOPS if prec == "f32" else BF16_MFMA_PEAK_TFLOPS
     B, S = args.embed_batch, args.seq_len
     gen = torch.Generator().manual_seed(args.seed + rank)
     ids = torch.randint(1000, 30000, (B, S), generator=gen)
@@ -1061,7 +1141,8 @@ def embed_main(args, world, rank, local, dev):
     for _ in range(args.warmup):
         g.forward(ids_d, mask_d)
     torch.cuda.synchronize()
-    g.profile(True)
+    if args.full:
+        g.profile(True)
     if dist_on():
         torch.distributed.barrier()
     torch.cuda.synchronize()
@@ -1072,13 +1153,41 @@ def embed_main(args, world, rank, local, dev):
     if dist_on():
         torch.distributed.barrier()
     elapsed = time.perf_counter() - t0
-    g.profile(False)
-    prof = {k: g.profile_read(k) for k in ("gemm", "attention", "other")}
+    if args.full:
+        g.profile(False)
     if dist_on():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     seqs = world * B * args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"embeddings": out}, rank)
+    out_line = {
+        "metric": "BERT embeddings/sec (encoder forward + mean pooling) [embedding stage, SURVEY.md §8f-4]",
+        "value": round(seqs / elapsed, 2), "unit": "sequences/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "fp32" if prec == "f32" else "bf16",
+        "data": "synthetic (random-init bert-base, random ids)",
+        "config": {"workload": f"bert-base forward, {B} sequences x {S} tokens per GPU, mean pooling",
+                   "batch": B, "seq_len": S, "tokens_per_step": B * S * world, "parallelism": f"replicas{world}"},
+        "tokens_per_sec": round(seqs * S / elapsed, 1),
+    }
+    if args.full:
+        embed_full_report(args, out_line, g, m, ids, mask, out, world, rank, dev)
+    if rank == 0:
+        print(json.dumps(out_line), flush=True)
+    if dist_on():
+        torch.distributed.destroy_process_group()
+
+
+def embed_full_report(args, out_line, g, m, ids, mask, out, world, rank, dev) -> None:
+    """--full of --mode embed: the MFMA roofline of the profiled steps, the
+    agreement with torch's fp32 forward, the same model through torch on this
+    GPU and the CPU baseline."""
+    prec = args.embed_precision
+    peak = F32_MFMA_PEAK_TFLOPS if prec == "f32" else BF16_MFMA_PEAK_TFLOPS
+    B, S = args.embed_batch, args.seq_len
+    prof = {k: g.profile_read(k) for k in ("gemm", "attention", "other")}
     gm = prof["gemm"]
     tf = gm["flops"] / (gm["total_ms"] * 1e-3) / 1e12 if gm["total_ms"] else 0.0
     # agreement with the fp32 torch forward on the first sequences (tolerance: tests/test_gpu_bert.py)
@@ -1089,16 +1198,8 @@ def embed_main(args, world, rank, local, dev):
     cos = float(torch.nn.functional.cosine_similarity(got, ref, dim=1).min())
     mxd = float((got - ref).abs().max())
     tol = EMBED_TOL[prec]
-    out_line = {
-        "metric": "BERT embeddings/sec (encoder forward + mean pooling) [embedding stage, SURVEY.md §8f-4]",
-        "value": round(seqs / elapsed, 2), "unit": "sequences/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "fp32" if prec == "f32" else "bf16",
-        "data": "synthetic (random-init bert-base, random ids)",
-        "config": {"workload": f"bert-base forward, {B} sequences x {S} tokens per GPU, mean pooling",
-                   "batch": B, "seq_len": S, "tokens_per_step": B * S * world, "parallelism": f"replicas{world}"},
-        "tokens_per_sec": round(seqs * S / elapsed, 1),
-        "roofline": {"bound": "mfma", "kernel": "fbert::k_gemm2_f32<EPI>" if prec == "f32" else "fbert::k_gemm3<EPI>",
+    out_line.update({
+        "roofline": {"bound": "mfma","kernel": "fbert::k_gemm2_f32<EPI>" if prec == "f32" else "fbert::k_gemm3<EPI>",
                      "achieved": round(tf, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(tf / peak, 4),
                      "traffic": None, "gemm_ms_per_step": round(gm["total_ms"] / args.steps, 3),
                      "gemm_launches_per_step": gm["launches"] // max(args.steps, 1),
@@ -1109,7 +1210,7 @@ def embed_main(args, world, rank, local, dev):
                    "max_abs_diff_vs_fp32_torch": mxd,
                    "tolerance": f"cosine >= {tol['cos']}, max |diff| <= {tol['max']} (tests/test_gpu_bert.py)",
                    "within_tolerance": cos >= tol["cos"] and mxd <= tol["max"]},
-    }
+    })
     # the reference's own forward on this GPU (torch fp32 -> hipBLASLt / MIOpen,
     # bert_embeddings.py:136 with device="cuda"), same batch, after the timed
     # region: the yardstick of the HIP encoder in the same arithmetic
@@ -1144,10 +1245,6 @@ def embed_main(args, world, rank, local, dev):
                                     "sample": f"{reps} x {nb} sequences of {S} tokens through the same model in torch "
                                               f"fp32 on the host (the reference's BertEmbedder forward, "
                                               f"bert_embeddings.py:136), {cores} threads"}
-    if rank == 0:
-        print(json.dumps(out_line), flush=True)
-    if dist_on():
-        torch.distributed.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -18,6 +18,42 @@ def test_world_size_mismatch_exits_nonzero():
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_full_is_off_by_default_and_steps_must_be_positive(monkeypatch):
+    sys.path.insert(0, str(REPO))
+    import bench
+    import pytest
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs_dtypes_sample_and_size(tmp_path, monkeypatch):
+    """--dump-outputs: float32 stays, everything else becomes float64; an
+    array above its share of the size limit is cut to the same seeded sample
+    on every call, in index order; all files together stay within the limit."""
+    sys.path.insert(0, str(REPO))
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 3 * 800)
+    big = np.arange(1000, dtype=np.int64) * 3
+    arrays = {"i": torch.arange(-5, 5, dtype=torch.int64), "f": torch.linspace(0, 1, 7, dtype=torch.float32), "big": big}
+    bench.dump_outputs(tmp_path / "a", arrays)
+    bench.dump_outputs(tmp_path / "b", arrays, rank=1)
+    i, f, b = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("i", "f", "big"))
+    assert i.dtype == np.float64 and np.array_equal(i, np.arange(-5, 5))
+    assert f.dtype == np.float32 and np.array_equal(f, arrays["f"].numpy())
+    assert b.dtype == np.float64 and b.shape == (100,) and np.all(np.diff(b) > 0) and np.all(b % 3 == 0)
+    assert np.array_equal(b, np.load(tmp_path / "b" / "big_rank1.npy"))
+    assert i.nbytes + f.nbytes + b.nbytes <= 3 * 800
+
+
 def test_rank_launch_cmd():
     sys.path.insert(0, str(REPO))
     import bench

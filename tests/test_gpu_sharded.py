@@ -121,7 +121,7 @@ def test_bench_c4_two_ranks_gloo(need_gpu, tmp_path):
     env = dict(os.environ, FHEICP_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(REPO / "bench.py"),
-           "--gpus", "2", "--workload", "c4", "--total-docs", "4096", "--steps", "1", "--warmup", "1"]
+           "--gpus", "2", "--workload", "c4", "--total-docs", "4096", "--steps", "1", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, cwd=str(REPO), env=env, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -143,7 +143,7 @@ def test_bench_gpus2_without_launcher(need_gpu):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(FHEICP_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--workload", "c4", "--total-docs", "4096",
-           "--steps", "1", "--warmup", "1"]
+           "--steps", "1", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, cwd=str(REPO), env=env, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -167,7 +167,7 @@ def test_bench_one_rank_rccl(need_gpu):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(REPO / "bench.py"),
            "--gpus", "1", "--workload", "c4", "--total-docs", "4096", "--steps", "1", "--warmup", "1",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=str(REPO), env=env, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

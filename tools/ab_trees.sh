@@ -9,7 +9,9 @@ for rep in ${REPS:-1 2}; do
   for t in old new; do
     d=$R; [ "$t" = old ] && d=$R/${OLD:-ab_r05}
     o=$R/gpurun_out/ab_trees/${TAG:-c2}_${t}_$rep.json
-    (cd "$d" && timeout -k 10 300 python bench.py --no-cpu-baseline --steps ${STEPS:-20} --warmup 3 ${ARGS:-} > $o 2> $o.err) || { echo "FAIL $t"; tail -5 $o.err; exit 1; }
+    # a tree from before bench.py had --full printed everything by default
+    full=$(grep -q -e '"--full"' "$d/bench.py" && echo --full)
+    (cd "$d" && timeout -k 10 300 python bench.py $full --no-cpu-baseline --steps ${STEPS:-20} --warmup 3 ${ARGS:-} > $o 2> $o.err) || { echo "FAIL $t"; tail -5 $o.err; exit 1; }
     python3 -c "
 import json; d=json.loads(open('$o').read().strip().splitlines()[-1])
 p=d.get('parity',{})

@@ -4,7 +4,7 @@ sha256 of the libfheicp.so they were measured on (bench.py reads them only
 for that exact build).
 
 Inputs: rocprofv3 counter_collection.csv files of separate --pmc passes over
-`bench.py --steps 1 --warmup 0 --no-cpu-baseline` (tools/pmc_bench.sh):
+`bench.py --full --steps 1 --warmup 0 --no-cpu-baseline` (tools/pmc_bench.sh):
   f64   SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU
   fetch FETCH_SIZE
   write WRITE_SIZE
@@ -83,7 +83,7 @@ def main():
     ap.add_argument("--write", required=True)
     ap.add_argument("--trace", default="")
     ap.add_argument("--grbm", default="", help="counter csv of a GRBM_GUI_ACTIVE GRBM_COUNT pass")
-    ap.add_argument("--command", default="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline")
+    ap.add_argument("--command", default="python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline")
     ap.add_argument("--out", required=True)
     ap.add_argument("--merge", default="", help="an earlier br_pmc.json of the same library to extend")
     a = ap.parse_args()

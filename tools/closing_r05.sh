@@ -16,14 +16,14 @@ step tests; timeout -k 10 1000 python -u -m pytest tests/ -m gpu -v -p no:cachep
 step smoke; timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/${T}_smoke.log" 2>&1 || exit 1
 step pmc; bash tools/pmc_r03.sh > "$OUT/${T}_pmc.log" 2>&1 || exit 1
 cp "$OUT/pmc_r03/br_pmc.json" profiles/br_pmc.json
-step bench; timeout -k 10 600 python bench.py > "$OUT/${T}_bench.json" 2> "$OUT/${T}_bench.err" || exit 1
-step c3; timeout -k 10 400 python bench.py --docs 10000 --dim 32 --n-bits 8 --steps 2 > "$OUT/${T}_c3_bench.json" 2> "$OUT/${T}_c3.err" || exit 1
-step c4; timeout -k 10 300 python bench.py --docs 12500 --dim 16 --n-bits 6 --steps 2 > "$OUT/${T}_c4_bench.json" 2> "$OUT/${T}_c4.err" || exit 1
-step c5; timeout -k 10 400 python bench.py --docs 1000 --dim 768 --n-bits 8 --steps 2 > "$OUT/${T}_c5_bench.json" 2> "$OUT/${T}_c5.err" || exit 1
-step embed; timeout -k 10 300 python bench.py --mode embed --steps 5 > "$OUT/${T}_embed_bench.json" 2> "$OUT/${T}_embed.err" || exit 1
-step embed_bf16; timeout -k 10 300 python bench.py --mode embed --embed-precision bf16 --steps 5 > "$OUT/${T}_embed_bf16_bench.json" 2> "$OUT/${T}_embed_bf16.err" || exit 1
+step bench; timeout -k 10 600 python bench.py --full > "$OUT/${T}_bench.json" 2> "$OUT/${T}_bench.err" || exit 1
+step c3; timeout -k 10 400 python bench.py --full --docs 10000 --dim 32 --n-bits 8 --steps 2 > "$OUT/${T}_c3_bench.json" 2> "$OUT/${T}_c3.err" || exit 1
+step c4; timeout -k 10 300 python bench.py --full --docs 12500 --dim 16 --n-bits 6 --steps 2 > "$OUT/${T}_c4_bench.json" 2> "$OUT/${T}_c4.err" || exit 1
+step c5; timeout -k 10 400 python bench.py --full --docs 1000 --dim 768 --n-bits 8 --steps 2 > "$OUT/${T}_c5_bench.json" 2> "$OUT/${T}_c5.err" || exit 1
+step embed; timeout -k 10 300 python bench.py --full --mode embed --steps 5 > "$OUT/${T}_embed_bench.json" 2> "$OUT/${T}_embed.err" || exit 1
+step embed_bf16; timeout -k 10 300 python bench.py --full --mode embed --embed-precision bf16 --steps 5 > "$OUT/${T}_embed_bf16_bench.json" 2> "$OUT/${T}_embed_bf16.err" || exit 1
 step sq; bash tools/pmc_sq.sh > /dev/null || exit 1
-step n2; FHEICP_DIST_BACKEND=gloo timeout -k 10 500 python bench.py --gpus 2 --steps 2 --warmup 1 > "$OUT/${T}_n2.json" 2> "$OUT/${T}_n2.err" || exit 1
+step n2; FHEICP_DIST_BACKEND=gloo timeout -k 10 500 python bench.py --full --gpus 2 --steps 2 --warmup 1 > "$OUT/${T}_n2.json" 2> "$OUT/${T}_n2.err" || exit 1
 cd /tmp && export TMPDIR=/tmp && cd "$R"
-step prof_embed; timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/${T}_prof_embed" -o run --output-format csv -- python3 bench.py --mode embed --steps 3 --no-cpu-baseline > "$OUT/${T}_prof_embed.log" 2>&1 || exit 1
+step prof_embed; timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/${T}_prof_embed" -o run --output-format csv -- python3 bench.py --full --mode embed --steps 3 --no-cpu-baseline > "$OUT/${T}_prof_embed.log" 2>&1 || exit 1
 step done

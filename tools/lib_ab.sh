@@ -8,7 +8,7 @@ for rep in ${REPS:-1 2}; do
   for name in ${LIBS}; do
     lib=fhe-icp_amd/fheicp/libfheicp.so; [ "$name" = default ] || lib=fhe-icp_amd/fheicp/libfheicp_$name.so
     o=gpurun_out/lib_ab/${TAG:-c2}_${name}_$rep.json
-    FHEICP_LIB=$R/$lib timeout -k 10 300 python bench.py --no-cpu-baseline --steps ${STEPS:-5} --warmup 1 ${ARGS:-} > $o 2> $o.err || { echo "FAIL $name"; tail -5 $o.err; exit 1; }
+    FHEICP_LIB=$R/$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps ${STEPS:-5} --warmup 1 ${ARGS:-} > $o 2> $o.err || { echo "FAIL $name"; tail -5 $o.err; exit 1; }
     python3 -c "
 import json; d=json.load(open('$o'))
 p=d.get('parity',{})

@@ -4,7 +4,7 @@
 # gpurun_out/pmc_sq/summary.txt. $LIB (optional) = an A/B build to load.
 set -u -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out/pmc_sq${TAG:-}; mkdir -p "$OUT"; cd "$R"; export TMPDIR=/tmp
-CMD="$R/bench.py --steps 1 --warmup 0 --no-cpu-baseline ${BENCH_ARGS:-}"
+CMD="$R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline ${BENCH_ARGS:-}"
 i=0
 for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS" \
            "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE GRBM_COUNT"; do
