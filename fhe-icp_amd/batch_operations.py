@@ -108,6 +108,13 @@ class BatchConfig:
     embedding_bits: Optional[int] = None     # n_e (default: n_bits)
     embedding_scale: Optional[float] = None  # s_e (default: calibrated on training embeddings)
     corpus_path: Optional[str] = None        # fheicp.persist corpus file: load, or save after creation
+    # private-query mode (fheicp.query): the store keeps plaintext
+    # vectors as the reference's does and the QUERY is encrypted; the server
+    # scores it against the device-resident quantized corpus without seeing
+    # it. Same bilinear quantisation (and scores) as store_ciphertexts; needs
+    # fhe="execute" and embedding bits <= 8. Keys, mask key and quantizer
+    # persist through corpus_path exactly as for store_ciphertexts.
+    encrypt_query: bool = False
     # the secret keys of model_path / corpus_path files are Fernet-wrapped
     # under this password (default: $FHE_MASTER_PASSWORD, fheicp.persist);
     # without one, saving a corpus needs allow_plaintext_secrets=True
@@ -127,6 +134,11 @@ class BatchConfig:
             raise ValueError("input_dim must be >= 1 and n_bits in [2, 16]")
         if self.gpu_embedder_precision not in ("f32", "bf16"):
             raise ValueError("gpu_embedder_precision must be 'f32' or 'bf16'")
+        if self.encrypt_query and self.store_ciphertexts:
+            raise ValueError("encrypt_query and store_ciphertexts are exclusive: the private-query mode "
+                             "scores an encrypted query against a plaintext store")
+        if self.encrypt_query and self.fhe != "execute":
+            raise ValueError("encrypt_query needs fhe='execute'")
 
 
 def _world():
@@ -156,11 +168,12 @@ class BatchProcessor:
             EncryptedDocument.allowed_dims = tuple(sorted(set(DEFAULT_DIMS) | {self.config.input_dim}))
         self._resident = None  # (host array identity, device tensor)
         self._resident_ct = None  # (host bodies, rank range, (device bodies, device ids))
-        self.corpus_engine = None  # fheicp.corpus.EncryptedCorpus (store_ciphertexts)
+        self.corpus_engine = None  # fheicp.corpus.EncryptedCorpus (store_ciphertexts, encrypt_query)
+        self._resident_q = None  # encrypt_query: (host array identity, rank range, [(docs8, B) per chunk])
         self.fhe_model = fhe_model
         if self.fhe_model is None:
             self._init_model()
-        elif self.config.store_ciphertexts and self.config.fhe == "execute":
+        elif (self.config.store_ciphertexts or self.config.encrypt_query) and self.config.fhe == "execute":
             self._init_corpus(self.fhe_model)
         if self.fhe_model is not None and EncryptedDocument.allowed_dims is not None and \
                 self.fhe_model.input_dim not in EncryptedDocument.allowed_dims:
@@ -202,7 +215,7 @@ class BatchProcessor:
             if needs_keys:
                 m.compile(X[:10], key_seed=cfg.key_seed)
         self.fhe_model = m
-        if cfg.store_ciphertexts and needs_keys:
+        if (cfg.store_ciphertexts or cfg.encrypt_query) and needs_keys:
             self._init_corpus(m)
 
     def _model_from_key_manager(self, needs_keys: bool):
@@ -229,7 +242,8 @@ class BatchProcessor:
         """A corpus that will be saved needs a password for its secret keys
         (or the explicit plaintext opt-in): fail before the keygen, not after."""
         cfg = self.config
-        if not (cfg.store_ciphertexts and cfg.fhe == "execute" and cfg.corpus_path) or os.path.exists(cfg.corpus_path):
+        if not ((cfg.store_ciphertexts or cfg.encrypt_query) and cfg.fhe == "execute" and cfg.corpus_path) or \
+                os.path.exists(cfg.corpus_path):
             return
         from fheicp.persist import _password
         if _password(cfg.password) is None and not cfg.allow_plaintext_secrets:
@@ -243,6 +257,7 @@ class BatchProcessor:
         cfg = self.config
         if cfg.corpus_path and os.path.exists(cfg.corpus_path):
             self.corpus_engine = persist.load_corpus(cfg.corpus_path, device=cfg.device, password=cfg.password)
+            self._check_query_bits(self.corpus_engine.cq)
             return
         self._check_corpus_secret()
         qp = m.model.quant_params
@@ -252,10 +267,16 @@ class BatchProcessor:
             from fheicp.datagen import training_embeddings
             e1, e2 = training_embeddings(len(qp.coef), 1000, seed=0 if cfg.seed is None else cfg.seed)
             cq = CorpusQuant.calibrate(qp, np.concatenate([e1, e2]), cfg.embedding_bits)
+        self._check_query_bits(cq)
         self.corpus_engine = EncryptedCorpus(cq).compile(key_seed=cfg.key_seed, device=cfg.device)
         if cfg.corpus_path:
             persist.save_corpus(cfg.corpus_path, self.corpus_engine, password=cfg.password,
                                 allow_plaintext_secrets=cfg.allow_plaintext_secrets)
+
+    def _check_query_bits(self, cq):
+        """encrypt_query: the documents are the matrix cores' i8 operand."""
+        if self.config.encrypt_query and cq.n_e > 8:
+            raise ValueError(f"encrypt_query needs embedding bits <= 8 (BatchConfig.embedding_bits), got {cq.n_e}")
 
     def _require_model(self) -> FHESimilarityModel:
         if self.fhe_model is None:
@@ -354,7 +375,7 @@ class BatchProcessor:
         """Plaintext vectors as in the reference (:175-178), or, with
         store_ciphertexts, seeded-LWE payloads of the quantized vectors."""
         vecs = np.asarray(vecs).astype(np.float32)
-        if self.corpus_engine is not None:
+        if self.corpus_engine is not None and not self.config.encrypt_query:
             from fheicp.corpus import PAYLOAD_VERSION
             bodies, ids = self.corpus_engine.encrypt_docs(vecs)
             payloads = self.corpus_engine.payloads(bodies, ids)
@@ -475,6 +496,8 @@ class BatchProcessor:
         k = len(ids) if top_k < 0 else min(int(top_k), len(ids))
         if k == 0:
             return []
+        if self.config.encrypt_query:
+            return [(ids[i], s) for i, s in self._search_private_query(query, E, k, min_similarity)][:top_k]
         if self.config.fhe != "execute":
             if _world()[0] > 1:
                 hits = self._search_clear_sharded(m, query, E, k, min_similarity)
@@ -533,6 +556,44 @@ class BatchProcessor:
         s = np.float64(c.cq.out_scale)
         hits = [(ids[int(i)], float(s * np.float64(a))) for a, i in zip(oa, oi) if i >= 0]
         return hits[:top_k]
+
+    def _search_private_query(self, query, E, k: int, t: float):
+        """The private-query search (fheicp.query): the client side encrypts
+        the query; the server side scores the payload against the packed,
+        device-resident quantized corpus in batch_size chunks, never
+        decrypting the query; top-k as in _search_gpu (one contiguous document
+        range per rank under torch.distributed)."""
+        import torch
+        from fheicp.query import EncryptedQuerySearch
+        from fheicp.search import sharded_topk
+        c = self.corpus_engine
+        if c is None:
+            raise RuntimeError("encrypt_query needs BatchConfig(encrypt_query=True, fhe='execute')")
+        qs = EncryptedQuerySearch(c)
+        eng = c.engine
+        world, rank = _world()
+        n = E.shape[0]
+        lo, hi = rank * n // world, (rank + 1) * n // world
+        r = self._resident_q
+        if r is None or r[0] is not E or r[1] != (lo, hi):
+            step = self.config.batch_size
+            chunks = [(qs.pack_docs(E[s:min(hi, s + step)]), min(hi, s + step) - s) for s in range(lo, hi, step)]
+            r = self._resident_q = (E, (lo, hi), chunks)
+        payload = qs.encrypt_query(query)
+        accs, belows = [], []
+        for docs8, nb in r[2]:
+            acc, below = qs.compare(payload, docs8, nb, t)
+            accs.append(acc)
+            belows.append(below)
+        if accs:
+            acc, below = torch.cat(accs), torch.cat(belows)
+        else:  # more ranks than documents
+            acc = torch.zeros(0, dtype=torch.int64, device=eng.device)
+            below = torch.zeros(0, dtype=torch.int64, device=eng.device)
+        oa, oi = sharded_topk(acc, below, k, lo, lambda a, b, kk, base: eng.topk(a, b, kk, base), world)
+        oa, oi = oa.cpu().numpy(), oi.cpu().numpy()
+        s = np.float64(c.cq.out_scale)
+        return [(int(i), float(s * np.float64(a))) for a, i in zip(oa, oi) if i >= 0]
 
     @staticmethod
     def _search_clear_sharded(m, query, E, k, t):

@@ -6,6 +6,8 @@
 //   k_client.h        keygen, encrypt / decrypt, seeded (stored) corpus kernels
 //   k_server.h        leveled linear layer, key switch (VALU and i8 MFMA),
 //                     quantisation, top-k
+//   k_query.h         private-query search: document packing, query byte planes,
+//                     the i8 MFMA GEMM of one encrypted query x clear documents
 //   k_blind_rotate.h  blind rotation (external products over an f64 wave FFT):
 //                     v4 (br_v4.h, the default hot kernel), v2/v3, v1
 //   this file         context, launch selection, profiling, the C ABI
@@ -26,6 +28,7 @@
 #include "common.h"
 #include "k_client.h"
 #include "k_server.h"
+#include "k_query.h"
 #include "k_blind_rotate.h"
 
 // ============================================================ host =========
@@ -65,6 +68,9 @@ struct fhe_ctx {
   bool prof = false;
   ProfAcc prof_br, prof_brf[5], prof_ks;  // blind rotation on the main / fast / fast2 / mid / mid2 / mid0 gadget
   ProfAcc prof_enc;                       // the fused client encryption + leveled dot (k_encrypt_linear)
+  ProfAcc prof_lq;                        // private-query leveled step: k_query_planes + k_linear_query_mfma
+  void* lq_ws = nullptr;                  // its query byte planes (grown on demand)
+  size_t lq_ws_bytes = 0;
   int br_variant = 4;  // N=1024 blind rotation: 4 = a wave per GLWE component (k = 2, default), 2
                        // (two waves per ciphertext; forced by FHEICP_BR_VARIANT=2)
   // A/B builds only (FHEICP_AB, tools/build_variant.sh): other v4 shapes
@@ -529,7 +535,7 @@ void fhe_ctx_destroy(fhe_ctx* ctx) {
                       (void*)ctx->bskf[2], (void*)ctx->bskf[3], (void*)ctx->bskf_fft[2], (void*)ctx->bskf_fft[3],
                       (void*)ctx->bskf[4], (void*)ctx->bskf_fft[4],
                       (void*)ctx->ksk8, (void*)ctx->ks_ws, (void*)ctx->ks_ws1, (void*)ctx->tw4, (void*)ctx->bsk_fft_v2,
-                      (void*)ctx->psi, (void*)ctx->mb_msg})
+                      (void*)ctx->psi, (void*)ctx->mb_msg, ctx->lq_ws})
       (void)hipFree(ptr);
     for (hipStream_t s : ctx->lane_st)
       if (s) (void)hipStreamDestroy(s);
@@ -539,6 +545,7 @@ void fhe_ctx_destroy(fhe_ctx* ctx) {
     for (auto& a : ctx->prof_brf) free_ev(a);
     free_ev(ctx->prof_ks);
     free_ev(ctx->prof_enc);
+    free_ev(ctx->prof_lq);
   }
   delete ctx;
 }
@@ -1847,6 +1854,111 @@ int fhe_compare_seeded_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_
   return FHE_OK;
 }
 
+// ---- private-query search: an encrypted query against clear documents -----
+static int query_kb(int32_t D) { return (D + 63) / 64; }
+static int query_args(fhe_ctx* ctx, int64_t B, int32_t D) {
+  if (B < 0 || D <= 0) return fail(ctx, FHE_E_ARG, "bad query arguments (B < 0 or D <= 0)");
+  if (D > 65536) return fail(ctx, FHE_E_ARG, "query dimension D > 65536 overflows the i32 accumulators");
+  return FHE_OK;
+}
+
+size_t fhe_query_docs_bytes(const fhe_params* p, int64_t B, int32_t D) {
+  (void)p;  // the packing depends on the MFMA tile only, not on the scheme
+  if (B < 0 || D <= 0) return 0;
+  return (size_t)((B + 15) / 16) * 16 * (size_t)query_kb(D) * 64;
+}
+
+int fhe_query_docs_pack(fhe_ctx* ctx, const int64_t* d_dq, int64_t B, int32_t D, void* d_docs8, void* stream) {
+  int rc = query_args(ctx, B, D);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  if ((rc = need_device(ctx))) return rc;
+  if (B > 0 && (!d_dq || !d_docs8)) return fail(ctx, FHE_E_ARG, "null query document buffers");
+  if (B == 0) return FHE_OK;
+  const int KB = query_kb(D);
+  const int64_t ncb = (B + 15) / 16, lanes = ncb * KB * 64;
+  if ((lanes + 255) / 256 > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "query document batch too large: split the call");
+  hipLaunchKernelGGL(k_query_docs_pack, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_dq,
+                     B, (int)D, KB, ncb, (v4i*)d_docs8);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+int fhe_linear_query_batch(fhe_ctx* ctx, const uint64_t* d_ct_q, const void* d_docs8, int64_t B, int32_t D,
+                           const int64_t* d_w, int64_t cst, uint64_t* d_out, void* stream) {
+  int rc = query_args(ctx, B, D);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  if ((rc = need_device(ctx))) return rc;
+  if (B > 0 && (!d_ct_q || !d_docs8 || !d_w || !d_out)) return fail(ctx, FHE_E_ARG, "null linear query buffers");
+  if (B == 0) return FHE_OK;
+  const fhe_params& p = ctx->p;
+  hipStream_t st = (hipStream_t)stream;
+  const int W = p.k * p.N + 1, NB = (W + 15) / 16, KB = query_kb(D);
+  const int64_t rblocks = ((B + 15) / 16 + 4 * LQ_RB - 1) / (4 * LQ_RB);
+  if (rblocks > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "query document batch too large: split the call");
+  // the query's byte planes: KB * 64 rows x NB * 16 columns x 8 planes
+  const size_t need = (size_t)KB * 64 * NB * 16 * 8;
+  if (need > ctx->lq_ws_bytes) {
+    if (ctx->lq_ws) {
+      HIPCHK(ctx, hipDeviceSynchronize());
+      HIPCHK(ctx, hipFree(ctx->lq_ws));
+      ctx->lq_ws = nullptr;
+      ctx->lq_ws_bytes = 0;
+    }
+    HIPCHK(ctx, hipMalloc(&ctx->lq_ws, need));
+    ctx->lq_ws_bytes = need;
+  }
+  hipEvent_t e1;
+  prof_begin(ctx, ctx->prof_lq, st, &e1);
+  ctx->prof_lq.kernel = "k_linear_query_mfma";
+  hipLaunchKernelGGL(k_query_planes, dim3((unsigned)(KB * NB)), dim3(64), 0, st, d_ct_q, (int)D, W, NB, KB, d_w,
+                     (v4i*)ctx->lq_ws);
+  hipLaunchKernelGGL(k_linear_query_mfma, dim3((unsigned)rblocks, (unsigned)((NB + LQ_CB - 1) / LQ_CB)), dim3(256), 0,
+                     st, (const v4i*)d_docs8, (const v4i*)ctx->lq_ws, B, W, NB, KB, (u64)cst << (64 - p.msg_bits),
+                     d_out);
+  prof_end(ctx, ctx->prof_lq, st, e1, B);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+int fhe_compare_query_batch(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0, const uint32_t h_mask_key[8],
+                            const void* d_docs8, int64_t B, int32_t D, const int64_t* d_w, int64_t cst, int64_t T,
+                            int64_t* d_acc, int64_t* d_below, void* stream) {
+  int rc = query_args(ctx, B, D);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  if ((rc = need_keys(ctx))) return rc;
+  if (!h_mask_key || (B > 0 && (!d_qbody || !d_docs8 || !d_w || !d_acc || !d_below)))
+    return fail(ctx, FHE_E_ARG, "null compare query arguments");
+  if (B == 0) return FHE_OK;
+  const fhe_params& p = ctx->p;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t Wb = fhe_big_lwe_words(&p), Ws = fhe_small_lwe_words(&p);
+  // workspace: ct_v (B big) | sign (B big) | small (B) | v (B) | the query's
+  // D expanded ciphertexts | its stream id
+  rc = ensure_ws(ctx, 8 * (2 * (size_t)B * Wb + (size_t)B * Ws + (size_t)B + (size_t)D * Wb + 1));
+  if (rc) return rc;
+  u64* ctv = (u64*)ctx->ws;
+  u64* sgn = ctv + (size_t)B * Wb;
+  u64* small = sgn + (size_t)B * Wb;
+  int64_t* v = (int64_t*)(small + (size_t)B * Ws);
+  u64* ctq = (u64*)(v + B);
+  u64* idw = ctq + (size_t)D * Wb;
+  hipLaunchKernelGGL(k_store_word, dim3(1), dim3(64), 0, st, idw, (u64)id0);
+  HIPCHK(ctx, hipGetLastError());
+  rc = fhe_expand_seeded_batch(ctx, d_qbody, idw, 1, D, h_mask_key, ctq, stream);
+  if (rc) return rc;
+  rc = fhe_linear_query_batch(ctx, ctq, d_docs8, B, D, d_w, cst - T, ctv, stream);
+  if (rc) return rc;
+  rc = fhe_decrypt_batch(ctx, ctv, B, v, stream);
+  if (rc) return rc;
+  rc = sign_extract_batch(ctx, ctv, B, sgn, small, st);
+  if (rc) return rc;
+  rc = fhe_decrypt_bits_batch(ctx, sgn, B, d_below, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_add_scalar, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, v, B, T, d_acc);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
 int fhe_threshold_batch(fhe_ctx* ctx, const uint64_t* d_ct_acc, int64_t count, int64_t T, uint64_t* d_bit,
                         void* stream) {
   int rc = need_keys(ctx);
@@ -2035,6 +2147,7 @@ static ProfAcc* prof_bucket(fhe_ctx* ctx, const char* kernel) {
   if (!strcmp(kernel, "blind_rotate_mid0")) return &ctx->prof_brf[4];
   if (!strcmp(kernel, "keyswitch")) return &ctx->prof_ks;
   if (!strcmp(kernel, "encrypt_linear")) return &ctx->prof_enc;
+  if (!strcmp(kernel, "linear_query")) return &ctx->prof_lq;
   return nullptr;
 }
 

@@ -92,6 +92,10 @@ SIGNATURES = [
     ("fhe_expand_seeded_batch", C.c_int, [_CTXP, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     ("fhe_linear_seeded_batch", C.c_int, [_CTXP, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp]),
     ("fhe_compare_seeded_batch", C.c_int, [_CTXP, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    ("fhe_query_docs_bytes", C.c_size_t, [_P, _i64, _i32]),
+    ("fhe_query_docs_pack", C.c_int, [_CTXP, _vp, _i64, _i32, _vp, _vp]),
+    ("fhe_linear_query_batch", C.c_int, [_CTXP, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp]),
+    ("fhe_compare_query_batch", C.c_int, [_CTXP, _vp, _u64, _vp, _vp, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _vp]),
     ("fhe_key_from_seed", None, [_u64, _vp]),
     ("fhe_quantize_pairs", C.c_int, [_CTXP, _vp, _i32, _vp, _i32, _i64, _i32, C.c_double, _i64, _i64, _i64, _vp, _vp]),
     ("fhe_dequantize", C.c_int, [_CTXP, _vp, _i64, C.c_double, _vp, _vp]),

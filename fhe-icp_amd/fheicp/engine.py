@@ -381,6 +381,38 @@ class Engine:
                                                    _stream(self.device)))
         return acc, below
 
+    # ------------------------- private query (encrypted query, clear docs) --
+    def pack_docs(self, dq: torch.Tensor) -> torch.Tensor:
+        """Quantized documents (int64 [B, D], values in [-128, 127]) -> the
+        i8 MFMA document operand of linear_query / compare_query
+        (fhe_query_docs_pack): a uint8 tensor of fhe_query_docs_bytes bytes."""
+        B, D = dq.shape
+        n = self._L.fhe_query_docs_bytes(C.byref(self._P), B, D)
+        docs8 = torch.empty(n, dtype=torch.uint8, device=self.device)
+        self._chk(self._L.fhe_query_docs_pack(self._ctx, _ptr(dq), B, D, _ptr(docs8), _stream(self.device)))
+        return docs8
+
+    def linear_query(self, ct_q: torch.Tensor, docs8: torch.Tensor, B: int, D: int, w, cst: int) -> torch.Tensor:
+        """out[b] = sum_j dq[b, j] * (w[j] * ct_q[j]) + cst (fhe_linear_query_batch):
+        ct_q D x (kN+1), docs8 from pack_docs; B x (kN+1)."""
+        wd = self.to_dev(w)
+        out = self.empty_big(B)
+        self._chk(self._L.fhe_linear_query_batch(self._ctx, _ptr(ct_q), _ptr(docs8), B, D, _ptr(wd), int(cst),
+                                                 _ptr(out), _stream(self.device)))
+        return out
+
+    def compare_query(self, qbody: torch.Tensor, id0: int, mask_key, docs8: torch.Tensor, B: int, D: int,
+                      w: torch.Tensor, cst: int, T: int):
+        """fhe_compare_query_batch: a seeded query (D body words, stream id,
+        public mask key) against packed clear documents;
+        (acc int64[B], below int64[B])."""
+        acc = torch.empty(B, dtype=torch.int64, device=self.device)
+        below = torch.empty(B, dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_compare_query_batch(self._ctx, _ptr(qbody), C.c_uint64(int(id0)), self._key(mask_key),
+                                                  _ptr(docs8), B, D, _ptr(w), int(cst), int(T), _ptr(acc),
+                                                  _ptr(below), _stream(self.device)))
+        return acc, below
+
     def topk(self, acc: torch.Tensor, below: torch.Tensor | None, k: int, base_idx: int = 0):
         oa = torch.empty(k, dtype=torch.int64, device=self.device)
         oi = torch.empty(k, dtype=torch.int64, device=self.device)

@@ -1,0 +1,141 @@
+"""Private-query search: an encrypted query against a clear document store.
+
+The third deployment shape. The reference's store holds
+plaintext embeddings (``EncryptedDocument.encrypted_embedding`` is the PCA
+vector, batch_operations.py:175-178); here the documents stay as they are and
+the QUERY is what arrives encrypted:
+
+  * the client quantizes its query with the corpus quantizer,
+    ``qq = E.quant(q)`` (fheicp.corpus.CorpusQuant), and encrypts the D values
+    as seeded LWEs at the worst-case width P0 (fhe_encrypt_seeded_batch, one
+    row): D body words, a 64-bit stream id and the public mask key;
+  * the server quantizes its documents the same way, ``dq = E.quant(d)``,
+    packs them once for the i8 matrix cores (fhe_query_docs_pack) and computes
+    ``acc_b = sum_j q_w[j] * qq_j * dq[b, j] + q_b'`` homomorphically
+    (fhe_compare_query_batch: the query's byte planes, one integer GEMM, sign
+    extraction of ``acc - T``).
+
+It is the bilinear quantisation of fheicp.corpus with the roles swapped, so
+the expected values are the same restatement (oracle/quant_ref.py,
+``corpus_*``). The server never sees the query, so every compare runs at P0
+(no per-query width, no rescale shift) and the threshold is placed on the
+worst-case range [-bound, bound].
+
+Query payload (uint64 vector):
+    [MAGIC, 1, D, P0, id0, mask key (4 words), k*N, body_0 .. body_{D-1}]
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+from .corpus import HEADER_WORDS, EncryptedCorpus
+
+QUERY_VERSION = "fheicp-seeded-query-v1"
+MAGIC = int.from_bytes(b"FHEICPQY", "little")
+
+
+def pack_query(body, id0: int, P0: int, mask_key, big: int) -> np.ndarray:
+    body = np.asarray(body, dtype=np.uint64).reshape(-1)
+    mk = np.ascontiguousarray(mask_key, dtype=np.uint32).view(np.uint64)
+    head = np.array([MAGIC, 1, body.size, P0, np.uint64(id0)], dtype=np.uint64)
+    return np.concatenate([head, mk, np.array([big], np.uint64), body])
+
+
+def unpack_query(arr) -> dict:
+    a = np.asarray(arr)
+    if a.dtype != np.uint64 or a.ndim != 1 or a.size < HEADER_WORDS or int(a[0]) != MAGIC:
+        raise ValueError("not an fheicp seeded-query payload")
+    if int(a[1]) != 1:
+        raise ValueError(f"unsupported query payload version {int(a[1])}")
+    D = int(a[2])
+    if a.size != HEADER_WORDS + D:
+        raise ValueError(f"query payload holds {a.size - HEADER_WORDS} bodies, header says {D}")
+    return {"D": D, "P0": int(a[3]), "id0": int(a[4]), "mask_key": a[5:9].copy().view(np.uint32),
+            "big": int(a[9]), "body": a[HEADER_WORDS:].copy()}
+
+
+class EncryptedQuerySearch:
+    """Both sides of the private-query mode over one EncryptedCorpus: its
+    context, keys, mask key, noise key, CorpusQuant and P0 (so
+    persist.save_corpus / load_corpus carry everything this mode needs)."""
+
+    MAX_BITS = 8  # the documents are the GEMM's i8 operand
+
+    def __init__(self, corpus: EncryptedCorpus):
+        self.corpus = corpus
+        self.cq = corpus.cq
+        self.P0 = corpus.P0
+
+    # ----------------------------------------------------------- planning --
+    def bound(self) -> int:
+        """max |acc| over every query and document: the value behind worst_msg_bits."""
+        qw = np.abs(np.asarray(self.cq.model.q_w, dtype=np.int64))
+        return int(qw.sum()) * 4 ** (self.cq.n_e - 1) + abs(self.cq.q_b)
+
+    def plan(self, min_similarity: float | None):
+        """Clear per-search constants (w int64 [D], cst, T). The server cannot
+        see the query: T sits on the worst-case range, w = q_w."""
+        b = self.bound()
+        T = self.cq.threshold_int(-b, b, min_similarity) if min_similarity is not None else -b
+        return np.asarray(self.cq.model.q_w, dtype=np.int64).copy(), self.cq.q_b, T
+
+    def check(self, pl: dict) -> None:
+        c = self.corpus
+        if pl["P0"] != self.P0 or pl["big"] != c.scheme.k * c.scheme.N:
+            raise ValueError("query was encrypted under different parameters")
+        if c.mask_key is not None and not np.array_equal(pl["mask_key"], c.mask_key):
+            raise ValueError("query was encrypted under a different mask key")
+        if pl["D"] != len(self.cq.model.q_w):
+            raise ValueError(f"query holds {pl['D']} features, the model {len(self.cq.model.q_w)}")
+
+    # ------------------------------------------------------------- client --
+    def encrypt_query(self, q, id0: int | None = None) -> np.ndarray:
+        """A reduced query vector -> the uint64 payload sent to the server."""
+        c = self.corpus
+        c._need()
+        eng = c.engine
+        qq = self.cq.quant(np.asarray(q).reshape(1, -1))
+        if id0 is None:
+            id0 = int.from_bytes(os.urandom(8), "little")
+        eng.set_msg_bits(self.P0)
+        ids = eng.to_dev(np.array([id0], dtype=np.uint64))
+        body = eng.encrypt_seeded(eng.to_dev(qq), c.mask_key, c._noise_key, ids)
+        return pack_query(body.cpu().numpy().view(np.uint64)[0], id0, self.P0, c.mask_key, c.scheme.k * c.scheme.N)
+
+    def decrypt_query(self, payload) -> np.ndarray:
+        """The quantized query (the key holder's view; tests)."""
+        c = self.corpus
+        c._need()
+        pl = unpack_query(payload)
+        self.check(pl)
+        return c.decrypt_docs(pl["body"][None, :], [pl["id0"]])[0]
+
+    # ------------------------------------------------------------- server --
+    def pack_docs(self, docs):
+        """docs f32/f64 [B, D] (host array or device tensor) -> the packed,
+        device-resident i8 corpus (a uint8 tensor; keep B beside it)."""
+        import torch
+        if self.cq.n_e > self.MAX_BITS:
+            raise ValueError(f"private-query search needs embedding bits n_e <= {self.MAX_BITS}, got {self.cq.n_e} "
+                             "(the documents are the i8 operand of the matrix cores)")
+        self.corpus._need()
+        eng = self.corpus.engine
+        dd = docs if isinstance(docs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(docs))
+        dq = eng.quantize(dd.to(eng.device).contiguous(), self.cq.s_e, 0, self.cq.qmin, self.cq.qmax)
+        return eng.pack_docs(dq)
+
+    def compare(self, payload, docs8, B: int, min_similarity: float | None):
+        """-> (acc int64 [B], below int64 [B]) device tensors."""
+        self.corpus._need()
+        eng = self.corpus.engine
+        pl = unpack_query(payload)
+        self.check(pl)
+        w, cst, T = self.plan(min_similarity)
+        eng.set_msg_bits(self.P0)
+        return eng.compare_query(eng.to_dev(pl["body"]), pl["id0"], pl["mask_key"], docs8, int(B), pl["D"],
+                                 eng.to_dev(w), cst, T)
+
+    def scores(self, acc) -> np.ndarray:
+        return self.corpus.scores(acc)

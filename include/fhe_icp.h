@@ -350,6 +350,41 @@ int fhe_linear_seeded_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t
 int fhe_compare_seeded_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t B, int32_t D,
                              const uint32_t h_mask_key[8], const int64_t* d_w, int64_t cst, int64_t T,
                              int64_t* d_acc, int64_t* d_below, void* stream);
+/* ---- private-query search: an encrypted query against clear documents -----
+ * The third deployment shape: the store keeps plaintext
+ * embeddings, as the reference's does (batch_operations.py:175-178), and the
+ * QUERY arrives encrypted. Query and documents are quantized by one symmetric
+ * n_e <= 8 bit quantizer; the server holds the quantized documents dq (B x D)
+ * in the clear and computes
+ *   out[b] = sum_j dq[b, j] * (d_w[j] * ct_q[j]) + trivial(cst * Delta),
+ * an integer GEMM [B x D] . [D x (kN+1)] over Z_2^64 on the i8 matrix cores,
+ * bit-identical to the plain u64 sum.
+ * fhe_query_docs_pack turns dq (int64, values in [-128, 127]) into the GEMM's
+ * document operand, once per resident corpus: fhe_query_docs_bytes bytes
+ * (B padded to a multiple of 16, D to a multiple of 64; one byte each).
+ * Document group i (rows 16 i .. 16 i + 15) occupies bytes [i, i + 1) * 16 *
+ * padded D, so a batch that starts at a multiple of 16 documents is a pointer
+ * into d_docs8.
+ * 0 < D <= 65536 (the i32 accumulators); d_w may hold any 64-bit weights. */
+size_t fhe_query_docs_bytes(const fhe_params* params, int64_t B, int32_t D);
+int fhe_query_docs_pack(fhe_ctx* ctx, const int64_t* d_dq, int64_t B, int32_t D, void* d_docs8, void* stream);
+/* The leveled step alone: d_ct_q holds the query's D full ciphertexts
+ * (D x (kN+1)), d_out B x (kN+1). Needs no keys. The query's byte planes live
+ * in context-owned workspace (8 * 64 ceil(D/64) * 16 ceil((kN+1)/16) bytes,
+ * grown on demand). */
+int fhe_linear_query_batch(fhe_ctx* ctx, const uint64_t* d_ct_q, const void* d_docs8, int64_t B, int32_t D,
+                           const int64_t* d_w, int64_t cst, uint64_t* d_out, void* stream);
+/* fhe_compare_seeded_batch with the roles swapped. The query travels as a
+ * seeded LWE vector (fhe_encrypt_seeded_batch with B = 1): D body words
+ * (d_qbody, device), its stream id id0 (feature j under id0 + j) and the
+ * public mask key. Expand the query -> planes -> GEMM with d_w and cst - T ->
+ * decrypt the leveled accumulator -> sign extraction -> decrypt the threshold
+ * bit. The query was encrypted at the context's msg_bits. Same single-party
+ * contract and outputs as fhe_compare_seeded_batch: d_acc[b] the accumulator,
+ * d_below[b] = 1 iff acc < T. */
+int fhe_compare_query_batch(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0, const uint32_t h_mask_key[8],
+                            const void* d_docs8, int64_t B, int32_t D, const int64_t* d_w, int64_t cst, int64_t T,
+                            int64_t* d_acc, int64_t* d_below, void* stream);
 /* The 64-bit-seed -> 256-bit ChaCha key expansion used by the seed forms
  * (fhe_keygen, fhe_encrypt_batch, ...; splitmix64): tests and
  * benches only. Host only. */
@@ -398,9 +433,10 @@ int fhe_stream_sync(fhe_ctx* ctx, void* stream);
  * synchronises and returns total milliseconds, launch count and ciphertexts
  * processed for kernel "blind_rotate" (all gadgets), "blind_rotate_main",
  * "blind_rotate_fast" (fhe_params.pbs_fast_*), "blind_rotate_fast2",
- * "blind_rotate_mid", "blind_rotate_mid2", "blind_rotate_mid0", "keyswitch" or "encrypt_linear"
- * (the fused client encryption + leveled dot), then resets what it
- * read. */
+ * "blind_rotate_mid", "blind_rotate_mid2", "blind_rotate_mid0", "keyswitch", "encrypt_linear"
+ * (the fused client encryption + leveled dot) or "linear_query" (the
+ * private-query leveled step: query planes + GEMM, one bracket around both),
+ * then resets what it read. */
 int fhe_profile_enable(fhe_ctx* ctx, int enable);
 int fhe_profile_read(fhe_ctx* ctx, const char* kernel, double* total_ms, int64_t* launches, int64_t* items);
 /* The kernel last launched for that bucket, as rocprofv3 names it (e.g.

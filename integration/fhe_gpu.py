@@ -50,6 +50,13 @@ _PROTOS = {
     "fhe_score_batch": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _i64, _u64, _u64, _vp, _vp]),
     "fhe_compare_batch_key": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _i64, _vp, _u64, _vp, _vp, _vp]),
     "fhe_score_batch_key": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _i64, _vp, _u64, _vp, _vp]),
+    # private query over a plaintext store
+    "fhe_set_msg_bits": (C.c_int, [_vp, _i32]),
+    "fhe_encrypt_seeded_batch": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "fhe_query_docs_bytes": (C.c_size_t, [C.POINTER(fhe_params), _i64, _i32]),
+    "fhe_query_docs_pack": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "fhe_linear_query_batch": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp]),
+    "fhe_compare_query_batch": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _vp]),
 }
 
 
@@ -146,6 +153,57 @@ class GpuCompare:
                                             id0, bufs[2], None)
             self._ok(rc)
             return self._to_host(bufs[2], B)
+        finally:
+            for d in bufs:
+                self.L.fhe_dev_free(self.ctx, d)
+
+    # ---- private query: an encrypted query against clear documents ----------
+    def pack_docs(self, dq: np.ndarray):
+        """Quantized documents (int64 [B, D], values in [-128, 127]) -> the
+        device-resident packed corpus (handle, B, D); free it with free_docs."""
+        dq = np.asarray(dq, np.int64)
+        B, D = dq.shape
+        src = self._to_dev(dq)
+        try:
+            docs8 = self._alloc(self.L.fhe_query_docs_bytes(C.byref(self.P), B, D))
+            self._ok(self.L.fhe_query_docs_pack(self.ctx, src, B, D, docs8, None))
+            # fhe_memcpy_d2h synchronises the stream: the pack is done before src is freed
+            self._to_host(src, 1)
+        finally:
+            self.L.fhe_dev_free(self.ctx, src)
+        return docs8, B, D
+
+    def free_docs(self, docs) -> None:
+        self.L.fhe_dev_free(self.ctx, docs[0])
+
+    def encrypt_query(self, qq: np.ndarray, mask_key, noise_key, id0: int | None = None):
+        """Client side: the quantized query (int64 [D]) as one seeded row at
+        the context's msg_bits; (body uint64 [D], id0). mask_key is public,
+        noise_key secret (8 u32 words each)."""
+        qq = np.asarray(qq, np.int64).reshape(1, -1)
+        D = qq.shape[1]
+        id0 = int.from_bytes(os.urandom(8), "little") if id0 is None else int(id0)
+        bufs = [self._to_dev(qq), self._to_dev(np.array([id0], np.uint64)), self._alloc(8 * D)]
+        try:
+            mk = (C.c_uint32 * 8)(*[int(x) for x in mask_key])
+            nk = (C.c_uint32 * 8)(*[int(x) for x in noise_key])
+            self._ok(self.L.fhe_encrypt_seeded_batch(self.ctx, bufs[0], 1, D, mk, nk, bufs[1], bufs[2], None))
+            return self._to_host(bufs[2], D).view(np.uint64), id0
+        finally:
+            for d in bufs:
+                self.L.fhe_dev_free(self.ctx, d)
+
+    def compare_query(self, body: np.ndarray, id0: int, mask_key, docs, q_w: np.ndarray, cst: int, T: int):
+        """Server side: the seeded query against a packed corpus (pack_docs):
+        (acc int64[B], below int64[B]); w = q_w, T on the worst-case range."""
+        docs8, B, D = docs
+        bufs = [self._to_dev(np.asarray(body, np.uint64)), self._to_dev(np.asarray(q_w, np.int64)),
+                self._alloc(8 * B), self._alloc(8 * B)]
+        try:
+            mk = (C.c_uint32 * 8)(*[int(x) for x in mask_key])
+            self._ok(self.L.fhe_compare_query_batch(self.ctx, bufs[0], int(id0), mk, docs8, B, D, bufs[1], int(cst),
+                                                    int(T), bufs[2], bufs[3], None))
+            return self._to_host(bufs[2], B), self._to_host(bufs[3], B)
         finally:
             for d in bufs:
                 self.L.fhe_dev_free(self.ctx, d)

@@ -1,0 +1,161 @@
+#!/usr/bin/env python3
+"""Private-query search: the leveled step against the seeded-corpus one, and
+the end-to-end compare rate (docs/AB_LOG_r07.md).
+
+For B = 1024 documents at D = 16 and D = 768 (C2's and C5's dimensions) and
+n_bits 6 and 8, in one process:
+
+  * the "linear_query" profile bucket (fhe_linear_query_batch: query byte
+    planes + the i8 MFMA GEMM, one HIP-event bracket around both) and
+    fhe_linear_seeded_batch at the same B and D (HIP events around the call),
+    interleaved launch by launch, the median of --launches launches each
+    after --warmup;
+  * fhe_compare_query_batch end to end (host clock around the call and a
+    device synchronise) as compares/s, its accumulators checked against the
+    oracle restatement. A shape whose worst-case width P0 has no parameter
+    set (P0 > 27) reports null there.
+
+The floor of the leveled step is its output, B * (kN + 1) * 8 bytes, over the
+6.29 TB/s a float4 copy reaches on the MI355X; `floor_fraction` is that floor
+over the measured time. Prints one JSON line and writes it to --out.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parents[1]
+for p in (str(REPO / "fhe-icp_amd"), str(REPO)):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+COPY_BW = 6.29e12  # bytes/s, measured float4 copy on the MI355X
+MAX_BITS = 27      # widest accumulator params_for_bits plans
+
+
+def corpus_quant(D: int, n_bits: int):
+    import numpy as np
+    from oracle import quant_ref as Q
+    from fheicp.corpus import CorpusQuant
+    from fheicp.datagen import training_embeddings
+    from fheicp.model import FheLinearModel
+    X, y = Q.prepare_training_data(D, 1000, seed=1236)
+    m = FheLinearModel.fit(X, y, n_bits)
+    e1, e2 = training_embeddings(D, 1000, seed=0)
+    return CorpusQuant.calibrate(m.qparams, np.concatenate([e1, e2])), Q.fit_quantized_linear(X, y, n_bits)
+
+
+def leveled(eng, B: int, D: int, n_bits: int, launches: int, warmup: int) -> dict:
+    """Interleaved medians (ms) of the linear_query bucket and fhe_linear_seeded_batch."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(D * 100 + n_bits)
+    u64 = lambda shape: eng.to_dev(rng.integers(0, 2 ** 64, shape, dtype=np.uint64))  # noqa: E731
+    ct_q, body, ids = u64((D, eng.W)), u64((B, D)), u64(B)
+    dq = eng.to_dev(rng.integers(-(2 ** (n_bits - 1)), 2 ** (n_bits - 1), (B, D)))
+    docs8 = eng.pack_docs(dq)
+    w = eng.to_dev(rng.integers(-(2 ** (n_bits - 1)), 2 ** (n_bits - 1), D))
+    mk = eng.key_from_seed(11)
+    eng.profile(True)
+    t_q, t_s = [], []
+    for i in range(warmup + launches):
+        eng.linear_query(ct_q, docs8, B, D, w, 3)
+        r = eng.profile_read("linear_query")
+        assert r["launches"] == 1
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        eng.linear_seeded(body, ids, mk, w, 3)
+        e1.record()
+        e1.synchronize()
+        if i >= warmup:
+            t_q.append(r["total_ms"])
+            t_s.append(e0.elapsed_time(e1))
+    eng.profile(False)
+    q_ms, s_ms = statistics.median(t_q), statistics.median(t_s)
+    out_bytes = B * eng.W * 8
+    floor_ms = out_bytes / COPY_BW * 1e3
+    return {"linear_query_ms": q_ms, "linear_query_min_ms": min(t_q), "linear_seeded_ms": s_ms,
+            "linear_seeded_min_ms": min(t_s), "ratio_query_over_seeded": q_ms / s_ms, "launches": launches,
+            "kernel": eng.kernel_name("linear_query"), "out_bytes": out_bytes, "floor_ms": floor_ms,
+            "floor_fraction": floor_ms / q_ms}
+
+
+def end_to_end(cq, oq, B: int, D: int, n_bits: int, reps: int) -> dict:
+    import numpy as np
+    import torch
+    from oracle import quant_ref as Q
+    from fheicp.corpus import EncryptedCorpus
+    from fheicp.query import EncryptedQuerySearch
+    c = EncryptedCorpus(cq).compile(key_seed=5, device=0, noise_seed=6)
+    qs = EncryptedQuerySearch(c)
+    q, docs = Q.make_corpus(D, B, seed=21)
+    docs8 = qs.pack_docs(docs)
+    payload = qs.encrypt_query(q)
+    times = []
+    for i in range(reps + 1):   # the first call warms up (workspace, code objects)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        acc, below = qs.compare(payload, docs8, B, 0.5)
+        torch.cuda.synchronize()
+        if i:
+            times.append(time.perf_counter() - t0)
+    ref = Q.corpus_accumulate(oq, cq.s_e, n_bits, q, docs)
+    scores = np.float64(Q.corpus_out_scale(oq, cq.s_e)) * ref.astype(np.float64)
+    exact = bool(np.array_equal(acc.cpu().numpy(), ref) and
+                 np.array_equal(below.cpu().numpy(), (scores < 0.5).astype(np.int64)))
+    sec = statistics.median(times)
+    from fheicp.params import sign_pbs_count
+    c.engine.close()
+    return {"compare_query_ms": sec * 1e3, "compares_per_s": B / sec, "reps": reps, "bit_exact": exact,
+            "pbs_per_compare": sign_pbs_count(c.scheme)}
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--dims", type=int, nargs="+", default=[16, 768])
+    ap.add_argument("--n-bits", type=int, nargs="+", default=[6, 8])
+    ap.add_argument("--launches", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--no-end-to-end", action="store_true",
+                    help="the leveled step only (kernel traces: no keygen, no sign extraction)")
+    ap.add_argument("--out", default=str(REPO / "profiles" / "query_bench.json"))
+    a = ap.parse_args()
+    if a.launches < 20:
+        ap.error("--launches must be >= 20 (the medians compared are of at least 20 launches)")
+    import torch
+    if not torch.cuda.is_available():
+        print("query_bench needs a GPU: nothing measured", file=sys.stderr)
+        return 2
+    from fheicp.engine import Engine
+    from fheicp.params import params_for_bits
+    shapes = []
+    for D in a.dims:
+        for nb in a.n_bits:
+            cq, oq = corpus_quant(D, nb)
+            P0 = cq.worst_msg_bits()
+            # the leveled step's shape is B x D x (kN + 1): the same for every planned width
+            eng = Engine(params_for_bits(min(P0, MAX_BITS)), 0)
+            row = {"B": a.batch, "D": D, "n_bits": nb, "P0": P0}
+            row.update(leveled(eng, a.batch, D, nb, a.launches, a.warmup))
+            eng.close()
+            row["end_to_end"] = (end_to_end(cq, oq, a.batch, D, nb, a.reps)
+                                 if P0 <= MAX_BITS and not a.no_end_to_end else None)
+            row["meets_bar"] = row["linear_query_ms"] <= row["linear_seeded_ms"]
+            shapes.append(row)
+    res = {"bench": "query_bench", "device": torch.cuda.get_device_name(0), "copy_bw_bytes_per_s": COPY_BW,
+           "shapes": shapes, "meets_bar": all(r["meets_bar"] for r in shapes)}
+    line = json.dumps(res)
+    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(a.out).write_text(line + "\n")
+    print(line)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
