@@ -8,6 +8,8 @@
 //                     quantisation, top-k
 //   k_query.h         private-query search: document packing, query byte planes,
 //                     the i8 MFMA GEMM of one encrypted query x clear documents
+//   k_pack.h          LWE -> GLWE packing key switch (two-party replies): wide
+//                     digits, key generation, rotation, packed decryption
 //   k_blind_rotate.h  blind rotation (external products over an f64 wave FFT):
 //                     v4 (br_v4.h, the default hot kernel), v2/v3, v1
 //   this file         context, launch selection, profiling, the C ABI
@@ -29,6 +31,7 @@
 #include "k_client.h"
 #include "k_server.h"
 #include "k_query.h"
+#include "k_pack.h"
 #include "k_blind_rotate.h"
 
 // ============================================================ host =========
@@ -47,7 +50,8 @@ struct fhe_ctx {
   fhe_params p{};
   int device = -1;
   std::string err;
-  bool keys = false;
+  bool keys = false;    // evaluation keys (bsk, ksk, the gadgets' keys) are in place
+  bool secret = false;  // ... and the secret keys: false after fhe_import_eval_keys
   u64 *s_small = nullptr, *s_big = nullptr, *bsk = nullptr, *ksk = nullptr, *ksk_colsum = nullptr;
   c64 *bsk_fft = nullptr, *tw = nullptr, *twist = nullptr, *tw4 = nullptr;
   c64* bsk_fft_v2 = nullptr;  // v2-layout copy of the main BSK for the table bootstrap (made on first use)
@@ -89,6 +93,14 @@ struct fhe_ctx {
   hipStream_t lane_st[2] = {nullptr, nullptr};
   hipEvent_t lane_ev[3] = {nullptr, nullptr, nullptr};
   int ks_variant = 2;  // 2 = MFMA (i8 planes, any ks_level with kN % 64 == 0), 1 = VALU split-K
+  // LWE -> GLWE packing key (k_pack.h): gadget (pk_beta, pk_level), the key
+  // [i][l][(k+1)N] as exported and its 8 byte planes in B-fragment order
+  u64* pk = nullptr;
+  int8_t* pk8 = nullptr;
+  int pk_beta = 0, pk_level = 0;
+  void* pack_ws = nullptr;  // digits | zero bodies | the GEMM's count x (k+1)N result
+  size_t pack_ws_bytes = 0;
+  ProfAcc prof_pack;        // fhe_pack_batch: k_pack_digits + the GEMM + k_pack_rotate
 };
 
 static std::mutex g_err_mu;
@@ -535,7 +547,8 @@ void fhe_ctx_destroy(fhe_ctx* ctx) {
                       (void*)ctx->bskf[2], (void*)ctx->bskf[3], (void*)ctx->bskf_fft[2], (void*)ctx->bskf_fft[3],
                       (void*)ctx->bskf[4], (void*)ctx->bskf_fft[4],
                       (void*)ctx->ksk8, (void*)ctx->ks_ws, (void*)ctx->ks_ws1, (void*)ctx->tw4, (void*)ctx->bsk_fft_v2,
-                      (void*)ctx->psi, (void*)ctx->mb_msg, ctx->lq_ws})
+                      (void*)ctx->psi, (void*)ctx->mb_msg, ctx->lq_ws, (void*)ctx->pk, (void*)ctx->pk8,
+                      ctx->pack_ws})
       (void)hipFree(ptr);
     for (hipStream_t s : ctx->lane_st)
       if (s) (void)hipStreamDestroy(s);
@@ -546,6 +559,7 @@ void fhe_ctx_destroy(fhe_ctx* ctx) {
     free_ev(ctx->prof_ks);
     free_ev(ctx->prof_enc);
     free_ev(ctx->prof_lq);
+    free_ev(ctx->prof_pack);
   }
   delete ctx;
 }
@@ -566,10 +580,19 @@ static int need_device(fhe_ctx* ctx) {
   if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, FHE_E_DEVICE, "hipSetDevice failed");
   return FHE_OK;
 }
-static int need_keys(fhe_ctx* ctx) {
+// evaluation keys: everything the server side computes with
+static int need_eval_keys(fhe_ctx* ctx) {
   int rc = need_device(ctx);
   if (rc) return rc;
-  if (!ctx->keys) return fail(ctx, FHE_E_STATE, "no keys: call fhe_keygen or fhe_import_keys");
+  if (!ctx->keys) return fail(ctx, FHE_E_STATE, "no keys: call fhe_keygen, fhe_import_keys or fhe_import_eval_keys");
+  return FHE_OK;
+}
+// the secret keys too: encryption, decryption, key generation from them
+static int need_secret(fhe_ctx* ctx) {
+  int rc = need_eval_keys(ctx);
+  if (rc) return rc;
+  if (!ctx->secret)
+    return fail(ctx, FHE_E_STATE, "no secret key: this context holds evaluation keys only (fhe_import_eval_keys)");
   return FHE_OK;
 }
 
@@ -637,18 +660,25 @@ static void keygen_fast_bsks(fhe_ctx* ctx, const ChaKey& K, hipStream_t st) {
                        mb ? kTagMbMask[g] : kTagMask[g], mb ? kTagMbNoise[g] : kTagNoise[g]);
   }
 }
-static int alloc_keys(fhe_ctx* ctx) {
+// Device buffers of the keys: the evaluation keys always, the secrets (and
+// mb_msg, derived from s_small) only with_secret: an evaluation-only context
+// never allocates them.
+static int alloc_keys(fhe_ctx* ctx, bool with_secret = true) {
   const fhe_params& p = ctx->p;
   for (int g = 1; g < NGAD; ++g) {
-    if (!fast_level(p, g) || ctx->bskf[g - 1]) continue;
-    const fhe_params q = fast_params(p, g);
-    HIPCHK(ctx, hipMalloc(&ctx->bskf[g - 1], 8 * fast_bsk_words(p, g)));
-    HIPCHK(ctx, hipMalloc(&ctx->bskf_fft[g - 1], sizeof(c64) * fast_bsk_words(p, g) / 2));
-    if (mb_for(p, g) && !ctx->mb_msg) HIPCHK(ctx, hipMalloc(&ctx->mb_msg, 8 * 3 * (size_t)((q.n + 1) / 2)));
+    if (!fast_level(p, g)) continue;
+    if (!ctx->bskf[g - 1]) {
+      HIPCHK(ctx, hipMalloc(&ctx->bskf[g - 1], 8 * fast_bsk_words(p, g)));
+      HIPCHK(ctx, hipMalloc(&ctx->bskf_fft[g - 1], sizeof(c64) * fast_bsk_words(p, g) / 2));
+    }
+    if (with_secret && mb_for(p, g) && !ctx->mb_msg)
+      HIPCHK(ctx, hipMalloc(&ctx->mb_msg, 8 * 3 * (size_t)((p.n + 1) / 2)));
   }
-  if (ctx->s_small) return FHE_OK;
-  HIPCHK(ctx, hipMalloc(&ctx->s_small, 8 * (size_t)p.n));
-  HIPCHK(ctx, hipMalloc(&ctx->s_big, 8 * (size_t)p.k * p.N));
+  if (with_secret && !ctx->s_small) {
+    HIPCHK(ctx, hipMalloc(&ctx->s_small, 8 * (size_t)p.n));
+    HIPCHK(ctx, hipMalloc(&ctx->s_big, 8 * (size_t)p.k * p.N));
+  }
+  if (ctx->bsk) return FHE_OK;
   HIPCHK(ctx, hipMalloc(&ctx->bsk, 8 * fhe_bsk_words(&p)));
   HIPCHK(ctx, hipMalloc(&ctx->ksk, 8 * fhe_ksk_words(&p)));
   HIPCHK(ctx, hipMalloc(&ctx->ksk_colsum, 8 * (size_t)(p.n + 1)));
@@ -724,6 +754,7 @@ int fhe_keygen_key(fhe_ctx* ctx, const uint32_t h_key[8], void* stream) {
   if (rc) return rc;
   HIPCHK(ctx, hipStreamSynchronize(st));
   ctx->keys = true;
+  ctx->secret = true;
   return FHE_OK;
 }
 
@@ -733,7 +764,7 @@ int fhe_keygen(fhe_ctx* ctx, uint64_t seed, void* stream) {
 }
 
 int fhe_export_keys(fhe_ctx* ctx, uint64_t* h_s_small, uint64_t* h_s_big, uint64_t* h_bsk, uint64_t* h_ksk) {
-  int rc = need_keys(ctx);
+  int rc = (h_s_small || h_s_big) ? need_secret(ctx) : need_eval_keys(ctx);
   if (rc) return rc;
   const fhe_params& p = ctx->p;
   HIPCHK(ctx, hipDeviceSynchronize());
@@ -745,7 +776,7 @@ int fhe_export_keys(fhe_ctx* ctx, uint64_t* h_s_small, uint64_t* h_s_big, uint64
 }
 
 int fhe_export_fast_bsk(fhe_ctx* ctx, int32_t which, uint64_t* h_bsk) {
-  int rc = need_keys(ctx);
+  int rc = need_eval_keys(ctx);
   if (rc) return rc;
   if (which < 1 || which >= NGAD)
     return fail(ctx, FHE_E_ARG, "which must be 1 (fast), 2 (fast2), 3 (mid), 4 (mid2) or 5 (mid0)");
@@ -782,6 +813,46 @@ int fhe_import_keys(fhe_ctx* ctx, const uint64_t* h_s_small, const uint64_t* h_s
   if (rc) return rc;
   HIPCHK(ctx, hipDeviceSynchronize());
   ctx->keys = true;
+  ctx->secret = true;
+  return FHE_OK;
+}
+
+// Evaluation keys only (the server of the two-party mode):
+// the keys are used as given and nothing is re-encrypted; the context holds
+// no s_small, s_big or mb_msg afterwards (zeroed and freed if it had them).
+int fhe_import_eval_keys(fhe_ctx* ctx, const uint64_t* h_bsk, const uint64_t* h_ksk,
+                         const uint64_t* const h_gadget_bsk[5]) {
+  int rc = need_device(ctx);
+  if (rc) return rc;
+  if (!h_bsk || !h_ksk) return fail(ctx, FHE_E_ARG, "the bootstrapping and key-switch key buffers are required");
+  const fhe_params& p = ctx->p;
+  for (int g = 1; g < NGAD; ++g)
+    if (fast_level(p, g) && (!h_gadget_bsk || !h_gadget_bsk[g - 1]))
+      return fail(ctx, FHE_E_ARG, "missing bootstrapping key of gadget " + std::to_string(g) +
+                                      " (these parameters have it)");
+  ctx->secret = false;
+  if (ctx->s_small || ctx->s_big || ctx->mb_msg) {
+    HIPCHK(ctx, hipDeviceSynchronize());
+    if (ctx->s_small) HIPCHK(ctx, hipMemset(ctx->s_small, 0, 8 * (size_t)p.n));
+    if (ctx->s_big) HIPCHK(ctx, hipMemset(ctx->s_big, 0, 8 * (size_t)p.k * p.N));
+    if (ctx->mb_msg) HIPCHK(ctx, hipMemset(ctx->mb_msg, 0, 8 * 3 * (size_t)((p.n + 1) / 2)));
+    HIPCHK(ctx, hipDeviceSynchronize());
+    for (u64** q : {&ctx->s_small, &ctx->s_big, &ctx->mb_msg}) {
+      if (*q) HIPCHK(ctx, hipFree(*q));
+      *q = nullptr;
+    }
+  }
+  rc = alloc_keys(ctx, false);
+  if (rc) return rc;
+  HIPCHK(ctx, hipMemcpy(ctx->bsk, h_bsk, 8 * fhe_bsk_words(&p), hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(ctx->ksk, h_ksk, 8 * fhe_ksk_words(&p), hipMemcpyHostToDevice));
+  for (int g = 1; g < NGAD; ++g)
+    if (fast_level(p, g))
+      HIPCHK(ctx, hipMemcpy(ctx->bskf[g - 1], h_gadget_bsk[g - 1], 8 * fast_bsk_words(p, g), hipMemcpyHostToDevice));
+  rc = convert_bsk(ctx, nullptr);
+  if (rc) return rc;
+  HIPCHK(ctx, hipDeviceSynchronize());
+  ctx->keys = true;
   return FHE_OK;
 }
 
@@ -796,7 +867,7 @@ static bool key_arg(const uint32_t* h_key, ChaKey& K) {
 
 static int encrypt_impl(fhe_ctx* ctx, const int64_t* d_msg, int64_t count, const ChaKey& K, uint64_t id0,
                         uint64_t* d_ct, void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_secret(ctx);
   if (rc) return rc;
   if (count < 0 || (count > 0 && (!d_msg || !d_ct))) return fail(ctx, FHE_E_ARG, "bad encrypt arguments");
   if (count == 0) return FHE_OK;
@@ -822,7 +893,7 @@ static int packed_chunks(const fhe_params& p, int32_t D) { return (D + p.N - 1) 
 
 static int encrypt_packed_impl(fhe_ctx* ctx, const int64_t* d_qx, int64_t B, int32_t D, const ChaKey& K,
                                uint64_t id0, uint64_t* d_glwe, void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_secret(ctx);
   if (rc) return rc;
   if (B < 0 || D <= 0 || (B > 0 && (!d_qx || !d_glwe))) return fail(ctx, FHE_E_ARG, "bad packed-encrypt arguments");
   if (B == 0) return FHE_OK;
@@ -862,7 +933,7 @@ int fhe_linear_packed_batch(fhe_ctx* ctx, const uint64_t* d_glwe, int64_t B, int
 
 static int encrypt_linear_impl(fhe_ctx* ctx, const int64_t* d_qx, int64_t B, int32_t D, const ChaKey& K,
                                uint64_t id0, const int64_t* d_w, int64_t cst, uint64_t* d_out, void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_secret(ctx);
   if (rc) return rc;
   if (B < 0 || D <= 0 || (B > 0 && (!d_qx || !d_w || !d_out))) return fail(ctx, FHE_E_ARG, "bad encrypt-linear arguments");
   if (B == 0) return FHE_OK;
@@ -900,7 +971,7 @@ static int seeded_args(fhe_ctx* ctx, int64_t B, int32_t D, const void* a, const 
 
 int fhe_encrypt_seeded_batch(fhe_ctx* ctx, const int64_t* d_msg, int64_t B, int32_t D, const uint32_t h_mask_key[8],
                              const uint32_t h_noise_key[8], const uint64_t* d_id0, uint64_t* d_body, void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_secret(ctx);
   if (rc) return rc;
   if ((rc = seeded_args(ctx, B, D, d_msg, d_id0, d_body))) return rc;
   if (!h_mask_key || !h_noise_key) return fail(ctx, FHE_E_ARG, "seeded encryption needs both keys");
@@ -948,7 +1019,7 @@ int fhe_linear_seeded_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t
 }
 
 static int decrypt_mode(fhe_ctx* ctx, const uint64_t* d_ct, int64_t count, int64_t* d_out, int mode, void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_secret(ctx);
   if (rc) return rc;
   if (count < 0 || (count > 0 && (!d_ct || !d_out))) return fail(ctx, FHE_E_ARG, "bad decrypt arguments");
   if (count == 0) return FHE_OK;
@@ -1090,7 +1161,7 @@ static int keyswitch_lane(fhe_ctx* ctx, const uint64_t* d_big, int64_t count, in
 static int ks_max_shift(const fhe_params& p) { return 63 - p.ks_level * p.ks_base_log - p.ks_level; }
 int fhe_keyswitch_batch(fhe_ctx* ctx, const uint64_t* d_big, int64_t count, int32_t shift, uint64_t add_body,
                         uint64_t* d_small, void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_eval_keys(ctx);
   if (rc) return rc;
   if (count < 0 || shift < 0 || shift > ks_max_shift(ctx->p) || (count > 0 && (!d_big || !d_small)))
     return fail(ctx, FHE_E_ARG, "bad keyswitch arguments (shift must be in [0, 63 - ks_level * (ks_base_log + 1)])");
@@ -1305,7 +1376,7 @@ static int launch_br(fhe_ctx* ctx, const uint64_t* d_small, int64_t count, BrTv 
 }
 
 int fhe_pbs_batch(fhe_ctx* ctx, const uint64_t* d_small, int64_t count, uint64_t tv, uint64_t* d_out, void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_eval_keys(ctx);
   if (rc) return rc;
   if (count < 0 || (count > 0 && (!d_small || !d_out))) return fail(ctx, FHE_E_ARG, "bad pbs arguments");
   if (count == 0) return FHE_OK;
@@ -1314,7 +1385,7 @@ int fhe_pbs_batch(fhe_ctx* ctx, const uint64_t* d_small, int64_t count, uint64_t
 
 int fhe_pbs_gadget_batch(fhe_ctx* ctx, const uint64_t* d_small, int64_t count, int32_t gadget, uint64_t tv,
                          uint64_t* d_out, void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_eval_keys(ctx);
   if (rc) return rc;
   if (count < 0 || gadget < 0 || gadget >= NGAD || (count > 0 && (!d_small || !d_out)))
     return fail(ctx, FHE_E_ARG, "bad pbs-gadget arguments");
@@ -1332,7 +1403,7 @@ static int log2i(int x) {
 
 int fhe_pbs_lut_batch(fhe_ctx* ctx, const uint64_t* d_small, int64_t count, uint64_t base, uint64_t step,
                       int32_t log_slots, uint64_t* d_out, void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_eval_keys(ctx);
   if (rc) return rc;
   const int logN = log2i(ctx->p.N);
   if (count < 0 || (count > 0 && (!d_small || !d_out)) || log_slots < 0 || log_slots > logN)
@@ -1466,7 +1537,7 @@ static int launch_br_table(fhe_ctx* ctx, const uint64_t* d_small, int64_t count,
 
 int fhe_pbs_table_gadget_batch(fhe_ctx* ctx, const uint64_t* d_small, int64_t count, int32_t gadget,
                                const int64_t* d_lut, int32_t lut_bits, uint64_t* d_out, void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_eval_keys(ctx);
   if (rc) return rc;
   const int logN = log2i(ctx->p.N);
   if (count < 0 || lut_bits < 0 || lut_bits > logN - 1 || !d_lut || (count > 0 && (!d_small || !d_out)))
@@ -1690,7 +1761,7 @@ static int sign_extract_batch(fhe_ctx* ctx, uint64_t* d_ct_v, int64_t count, uin
 }
 
 int fhe_sign_batch(fhe_ctx* ctx, uint64_t* d_ct_v, int64_t count, uint64_t* d_sign, void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_eval_keys(ctx);
   if (rc) return rc;
   if (count < 0 || (count > 0 && (!d_ct_v || !d_sign))) return fail(ctx, FHE_E_ARG, "bad sign arguments");
   if (count == 0) return FHE_OK;
@@ -1701,7 +1772,7 @@ int fhe_sign_batch(fhe_ctx* ctx, uint64_t* d_ct_v, int64_t count, uint64_t* d_si
 
 int fhe_sign_trace_batch(fhe_ctx* ctx, uint64_t* d_ct_v, int64_t count, const int32_t* h_sched, int32_t rounds,
                          uint64_t* d_sign, uint32_t* d_phase, void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_secret(ctx);
   if (rc) return rc;
   const fhe_params& p = ctx->p;
   int d, tmp[64];
@@ -1731,7 +1802,7 @@ int fhe_sign_trace_batch(fhe_ctx* ctx, uint64_t* d_ct_v, int64_t count, const in
 
 int fhe_bit_extract_batch(fhe_ctx* ctx, uint64_t* d_ct_v, int64_t count, uint64_t* d_refreshed, uint64_t* d_sign,
                           void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_eval_keys(ctx);
   if (rc) return rc;
   if (count < 0 || (count > 0 && (!d_ct_v || !d_refreshed || !d_sign)))
     return fail(ctx, FHE_E_ARG, "bad bit-extract arguments");
@@ -1743,7 +1814,7 @@ int fhe_bit_extract_batch(fhe_ctx* ctx, uint64_t* d_ct_v, int64_t count, uint64_
 
 static int compare_impl(fhe_ctx* ctx, const int64_t* d_qx, int64_t B, int32_t D, const int64_t* d_w, int64_t cst,
                         int64_t T, const ChaKey& K, uint64_t id0, int64_t* d_acc, int64_t* d_below, void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_secret(ctx);
   if (rc) return rc;
   if (B < 0 || D <= 0 || (B > 0 && (!d_qx || !d_w || !d_acc || !d_below)))
     return fail(ctx, FHE_E_ARG, "bad compare arguments");
@@ -1792,7 +1863,7 @@ int fhe_compare_batch_key(fhe_ctx* ctx, const int64_t* d_qx, int64_t B, int32_t 
 // accumulator in the msg_bits-bit encoding (acc - T must fit it).
 static int score_impl(fhe_ctx* ctx, const int64_t* d_qx, int64_t B, int32_t D, const int64_t* d_w, int64_t cst,
                       int64_t T, const ChaKey& K, uint64_t id0, int64_t* d_acc, void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_secret(ctx);
   if (rc) return rc;
   if (B < 0 || D <= 0 || (B > 0 && (!d_qx || !d_w || !d_acc))) return fail(ctx, FHE_E_ARG, "bad score arguments");
   if (B == 0) return FHE_OK;
@@ -1826,7 +1897,7 @@ int fhe_score_batch_key(fhe_ctx* ctx, const int64_t* d_qx, int64_t B, int32_t D,
 int fhe_compare_seeded_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t B, int32_t D,
                              const uint32_t h_mask_key[8], const int64_t* d_w, int64_t cst, int64_t T,
                              int64_t* d_acc, int64_t* d_below, void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_secret(ctx);
   if (rc) return rc;
   if ((rc = seeded_args(ctx, B, D, d_body, d_id0, d_w))) return rc;
   if (!h_mask_key || (B > 0 && (!d_acc || !d_below))) return fail(ctx, FHE_E_ARG, "bad seeded compare arguments");
@@ -1920,48 +1991,317 @@ int fhe_linear_query_batch(fhe_ctx* ctx, const uint64_t* d_ct_q, const void* d_d
   return FHE_OK;
 }
 
+// ---- LWE -> GLWE packing key switch (k_pack.h) ------------
+// gadget (beta, L) of a packing key: int8 digits, at most 8 levels, and every
+// tie coin (input bit 62 - beta L - s, s < L) an input bit
+static bool pack_gadget_ok(int32_t beta, int32_t L) {
+  return beta >= 1 && beta <= 7 && L >= 1 && L <= 8 && beta * L + L <= 62;
+}
+static int pack_gadget_args(fhe_ctx* ctx, int32_t beta, int32_t L) {
+  if (!pack_gadget_ok(beta, L))
+    return fail(ctx, FHE_E_ARG, "packing gadget out of range (1 <= base_log <= 7, 1 <= level <= 8, "
+                                "level * (base_log + 1) <= 62)");
+  return FHE_OK;
+}
+size_t fhe_pack_key_words(const fhe_params* p, int32_t base_log, int32_t level) {
+  if (!p || !pack_gadget_ok(base_log, level)) return 0;
+  return (size_t)p->k * p->N * level * (p->k + 1) * p->N;
+}
+
+// Variance the packing adds to each packed phase, in units of the integer
+// words (torus variance times 2^128): the key rows' noise through the digits
+// of min(count, N) inputs, plus the rounding of the input's kN mask words to
+// beta L bits (half of them meet a set key bit). fheicp/params.py pack_var is
+// the same expression.
+static double pack_var(const fhe_params& p, int64_t count, int beta, int L) {
+  const double B = std::ldexp(1.0, beta);
+  const double big = (double)p.k * p.N;
+  const double m = (double)std::min<int64_t>(count, p.N);
+  return m * big * L * ((B * B + 2) / 12.0) * tuniform_var(p.glwe_noise_bits) +
+         (1.0 + big / 2.0) * std::ldexp(1.0, 2 * (64 - beta * L)) / 12.0;
+}
+static double pack_sigmas(const fhe_params& p, int64_t count, double in_var, int beta, int L, int margin_log) {
+  return std::ldexp(1.0, margin_log) / std::sqrt(in_var * std::ldexp(1.0, 128) + pack_var(p, count, beta, L));
+}
+int fhe_pack_plan(const fhe_params* params, int64_t count, double in_var, int32_t* base_log, int32_t* level,
+                  int32_t* bit_levels) {
+  std::string why;
+  if (validate(params, why)) return fail(nullptr, FHE_E_ARG, why);
+  if (count < 1 || !(in_var >= 0)) return fail(nullptr, FHE_E_ARG, "bad pack-plan arguments (count >= 1, in_var >= 0)");
+  const fhe_params& p = *params;
+  const int mlog = 63 - p.msg_bits;
+  int bb = 0, bl = 0;
+  for (int L = 1; L <= 8 && !bb; ++L)
+    for (int beta = 7; beta >= 1; --beta)
+      if (pack_gadget_ok(beta, L) && pack_sigmas(p, count, in_var, beta, L, mlog) >= 9.2) {
+        bb = beta;
+        bl = L;
+        break;
+      }
+  if (!bb) {  // no gadget reaches the bar: the most precise one
+    double best = -1;
+    for (int L = 1; L <= 8; ++L)
+      for (int beta = 7; beta >= 1; --beta) {
+        if (!pack_gadget_ok(beta, L)) continue;
+        const double sg = pack_sigmas(p, count, in_var, beta, L, mlog);
+        if (sg > best) { best = sg; bb = beta; bl = L; }
+      }
+  }
+  int lb = bl;
+  for (int L = 1; L <= bl; ++L)
+    if (pack_sigmas(p, count, in_var, bb, L, 62) >= 9.2) { lb = L; break; }
+  if (base_log) *base_log = bb;
+  if (level) *level = bl;
+  if (bit_levels) *bit_levels = lb;
+  return FHE_OK;
+}
+
+// (re)allocate the packing key's buffers for gadget (beta, L)
+static int pack_key_alloc(fhe_ctx* ctx, int32_t beta, int32_t L) {
+  const size_t words = fhe_pack_key_words(&ctx->p, beta, L);
+  if (ctx->pk && fhe_pack_key_words(&ctx->p, ctx->pk_beta, ctx->pk_level) != words) {
+    HIPCHK(ctx, hipDeviceSynchronize());
+    HIPCHK(ctx, hipFree(ctx->pk));
+    ctx->pk = nullptr;
+    HIPCHK(ctx, hipFree(ctx->pk8));
+    ctx->pk8 = nullptr;
+  }
+  ctx->pk_beta = ctx->pk_level = 0;
+  if (!ctx->pk) {
+    HIPCHK(ctx, hipMalloc(&ctx->pk, 8 * words));
+    HIPCHK(ctx, hipMalloc(&ctx->pk8, 8 * words));
+  }
+  return FHE_OK;
+}
+// the key's 8 byte planes in B-fragment order: k_ksk_to_i8 on the layout
+// [i][l][(k+1)N] with no rounding
+static int pack_key_planes(fhe_ctx* ctx, int32_t beta, int32_t L, hipStream_t st) {
+  const fhe_params& p = ctx->p;
+  const int big = p.k * p.N, K = big * L, n1 = (p.k + 1) * p.N;
+  const int64_t tot = (int64_t)K * n1;
+  hipLaunchKernelGGL(k_ksk_to_i8, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, ctx->pk, K, big, (int)L, n1,
+                     n1 / 16, 0, 8, ctx->pk8);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  ctx->pk_beta = beta;
+  ctx->pk_level = L;
+  return FHE_OK;
+}
+
+int fhe_keygen_pack_key_key(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint32_t h_key[8], void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  int rc = pack_gadget_args(ctx, base_log, level);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  if ((rc = need_secret(ctx))) return rc;
+  ChaKey K;
+  if (!key_arg(h_key, K)) return fail(ctx, FHE_E_ARG, "null key");
+  if ((rc = pack_key_alloc(ctx, base_log, level))) return rc;
+  const fhe_params& p = ctx->p;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_keygen_pack, dim3((unsigned)(p.k * p.N * level)), dim3(256), 8 * (size_t)p.N + p.N, st, K, p.N,
+                     p.k, (int)level, (int)base_log, p.glwe_noise_bits, ctx->s_big, ctx->pk);
+  HIPCHK(ctx, hipGetLastError());
+  return pack_key_planes(ctx, base_log, level, st);
+}
+int fhe_keygen_pack_key(fhe_ctx* ctx, int32_t base_log, int32_t level, uint64_t seed, void* stream) {
+  const ChaKey K = key_from_seed(seed);
+  return fhe_keygen_pack_key_key(ctx, base_log, level, K.w, stream);
+}
+
+static int need_pack_key(fhe_ctx* ctx) {
+  int rc = need_device(ctx);
+  if (rc) return rc;
+  if (!ctx->pk_level) return fail(ctx, FHE_E_STATE, "no packing key: call fhe_keygen_pack_key or fhe_import_pack_key");
+  return FHE_OK;
+}
+
+int fhe_export_pack_key(fhe_ctx* ctx, uint64_t* h_out) {
+  int rc = need_pack_key(ctx);
+  if (rc) return rc;
+  if (!h_out) return fail(ctx, FHE_E_ARG, "null buffer");
+  HIPCHK(ctx, hipDeviceSynchronize());
+  HIPCHK(ctx, hipMemcpy(h_out, ctx->pk, 8 * fhe_pack_key_words(&ctx->p, ctx->pk_beta, ctx->pk_level),
+                        hipMemcpyDeviceToHost));
+  return FHE_OK;
+}
+
+int fhe_import_pack_key(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint64_t* h_in) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  int rc = pack_gadget_args(ctx, base_log, level);  // argument errors first
+  if (rc) return rc;
+  if ((rc = need_device(ctx))) return rc;
+  if (!h_in) return fail(ctx, FHE_E_ARG, "null buffer");
+  if ((rc = pack_key_alloc(ctx, base_log, level))) return rc;
+  HIPCHK(ctx, hipMemcpy(ctx->pk, h_in, 8 * fhe_pack_key_words(&ctx->p, base_log, level), hipMemcpyHostToDevice));
+  return pack_key_planes(ctx, base_log, level, nullptr);
+}
+
+// digits -> GEMM on the i8 matrix cores -> rotation, on the first `levels`
+// levels of the key. The GEMM is the key switch's kernel on 8 planes with
+// (k+1)N columns (a multiple of 16: no padded column block), K = kN * levels
+// level-major, so a level prefix is a prefix of the key's k-blocks.
+static int pack_impl(fhe_ctx* ctx, const uint64_t* d_ct, int64_t count, int32_t levels, uint64_t* d_glwe,
+                     hipStream_t st) {
+  const fhe_params& p = ctx->p;
+  const int big = p.k * p.N, K = big * levels, KB = K / 64, n1 = (p.k + 1) * p.N, NB = n1 / 16;
+  const int64_t ncb = (count + 15) / 16, G = (count + p.N - 1) / p.N;
+  if (ncb > 65535 || G * (p.N / PK_JC) > 65535) return fail(ctx, FHE_E_ARG, "pack batch too large: split the call");
+  const size_t dbytes = (size_t)ncb * 16 * K, bbytes = 8 * (size_t)ncb * 16;
+  const size_t need = dbytes + bbytes + 8 * (size_t)count * n1;
+  if (need > ctx->pack_ws_bytes) {
+    if (ctx->pack_ws) {
+      HIPCHK(ctx, hipDeviceSynchronize());
+      HIPCHK(ctx, hipFree(ctx->pack_ws));
+      ctx->pack_ws = nullptr;
+      ctx->pack_ws_bytes = 0;
+    }
+    HIPCHK(ctx, hipMalloc(&ctx->pack_ws, need));
+    ctx->pack_ws_bytes = need;
+  }
+  uint32_t* Dg = (uint32_t*)ctx->pack_ws;
+  u64* body = (u64*)((char*)ctx->pack_ws + dbytes);
+  u64* M = (u64*)((char*)ctx->pack_ws + dbytes + bbytes);
+  // K split as the key switch's: ~2 workgroups per CU when the (ciphertext
+  // block, column block) grid alone would leave CUs idle
+  const int64_t ctb = (count + KSM_CTS - 1) / KSM_CTS, ktiles = ctb * NB;
+  int S = (int)std::max<int64_t>(1, std::min<int64_t>(KB / KSM_RING, 512 / ktiles));
+  const int kslice = (KB / KSM_RING + S - 1) / S * KSM_RING;
+  S = (KB + kslice - 1) / kslice;
+  hipEvent_t e1;
+  prof_begin(ctx, ctx->prof_pack, st, &e1);
+  ctx->prof_pack.kernel = "k_keyswitch_mfma<8, 1>";
+  HIPCHK(ctx, hipMemsetAsync(d_glwe, 0, 8 * (size_t)G * n1, st));
+  // the digits kernel also zeroes the rows the split's atomics add into
+  hipLaunchKernelGGL(k_pack_digits, dim3((unsigned)(big / 64), (unsigned)ncb), dim3(256), 0, st, d_ct, count, big,
+                     ctx->pk_beta, (int)levels, KB, Dg, body, S > 1 ? n1 : 0, M);
+  hipLaunchKernelGGL((k_keyswitch_mfma<8, 1>), dim3((unsigned)(ktiles * S)), dim3(256), 0, st, (const v4i*)Dg,
+                     (const v4i*)ctx->pk8, body, count, n1, NB, KB, 0, S, kslice, M);
+  hipLaunchKernelGGL(k_pack_rotate, dim3((unsigned)(p.N / 256), (unsigned)(p.k + 1), (unsigned)(G * (p.N / PK_JC))),
+                     dim3(256), 0, st, M, d_ct, count, p.N, p.k, d_glwe);
+  prof_end(ctx, ctx->prof_pack, st, e1, count);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+int fhe_pack_batch(fhe_ctx* ctx, const uint64_t* d_ct, int64_t count, int32_t levels, uint64_t* d_glwe, void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  // argument errors first: a host-only context reports them too
+  if (count < 0 || levels < 0 || levels > 8) return fail(ctx, FHE_E_ARG, "bad pack arguments (count < 0 or levels outside [0, 8])");
+  int rc = need_pack_key(ctx);
+  if (rc) return rc;
+  if (levels > ctx->pk_level) return fail(ctx, FHE_E_ARG, "pack levels exceed the packing key's");
+  if (count > 0 && (!d_ct || !d_glwe)) return fail(ctx, FHE_E_ARG, "null pack buffers");
+  if (count == 0) return FHE_OK;
+  return pack_impl(ctx, d_ct, count, levels ? levels : ctx->pk_level, d_glwe, (hipStream_t)stream);
+}
+
+int fhe_decrypt_packed_batch(fhe_ctx* ctx, const uint64_t* d_glwe, int64_t count, int32_t mode, int64_t* d_out,
+                             void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  if (count < 0 || mode < 0 || mode > 2) return fail(ctx, FHE_E_ARG, "bad packed-decrypt arguments (count < 0 or mode outside 0..2)");
+  int rc = need_secret(ctx);
+  if (rc) return rc;
+  if (count > 0 && (!d_glwe || !d_out)) return fail(ctx, FHE_E_ARG, "null packed-decrypt buffers");
+  if (count == 0) return FHE_OK;
+  const fhe_params& p = ctx->p;
+  const int64_t G = (count + p.N - 1) / p.N;
+  if (G > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "packed-decrypt batch too large: split the call");
+  hipLaunchKernelGGL(k_decrypt_packed, dim3((unsigned)G), dim3(256), 8 * (size_t)p.N + p.N, (hipStream_t)stream, p.N,
+                     p.k, p.msg_bits, (int)mode, ctx->s_big, d_glwe, count, d_out);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+// The leveled part of a private-query search, shared by the single-party
+// compare and the two-party server entry: the workspace
+//   ct_v (B big) | sign (B big) | small (B) | v (B) | the query's D expanded
+//   ciphertexts | its stream id | (keep_copy: a second B big)
+// then the query's expansion and the GEMM with cst on the body, into ct_v.
+struct QueryWs {
+  u64 *ctv, *sgn, *small;
+  int64_t* v;
+  u64* cpy;
+};
+static int query_leveled(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0, const uint32_t h_mask_key[8],
+                         const void* d_docs8, int64_t B, int32_t D, const int64_t* d_w, int64_t cst, bool keep_copy,
+                         QueryWs* w, void* stream) {
+  const fhe_params& p = ctx->p;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t Wb = fhe_big_lwe_words(&p), Ws = fhe_small_lwe_words(&p);
+  int rc = ensure_ws(ctx, 8 * (2 * (size_t)B * Wb + (size_t)B * Ws + (size_t)B + (size_t)D * Wb + 1 +
+                               (keep_copy ? (size_t)B * Wb : 0)));
+  if (rc) return rc;
+  w->ctv = (u64*)ctx->ws;
+  w->sgn = w->ctv + (size_t)B * Wb;
+  w->small = w->sgn + (size_t)B * Wb;
+  w->v = (int64_t*)(w->small + (size_t)B * Ws);
+  u64* ctq = (u64*)(w->v + B);
+  u64* idw = ctq + (size_t)D * Wb;
+  w->cpy = keep_copy ? idw + 1 : nullptr;
+  hipLaunchKernelGGL(k_store_word, dim3(1), dim3(64), 0, st, idw, (u64)id0);
+  HIPCHK(ctx, hipGetLastError());
+  rc = fhe_expand_seeded_batch(ctx, d_qbody, idw, 1, D, h_mask_key, ctq, stream);
+  if (rc) return rc;
+  return fhe_linear_query_batch(ctx, ctq, d_docs8, B, D, d_w, cst, w->ctv, stream);
+}
+
 int fhe_compare_query_batch(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0, const uint32_t h_mask_key[8],
                             const void* d_docs8, int64_t B, int32_t D, const int64_t* d_w, int64_t cst, int64_t T,
                             int64_t* d_acc, int64_t* d_below, void* stream) {
   int rc = query_args(ctx, B, D);  // argument errors first: a host-only context reports them too
   if (rc) return rc;
-  if ((rc = need_keys(ctx))) return rc;
+  if ((rc = need_secret(ctx))) return rc;
   if (!h_mask_key || (B > 0 && (!d_qbody || !d_docs8 || !d_w || !d_acc || !d_below)))
     return fail(ctx, FHE_E_ARG, "null compare query arguments");
   if (B == 0) return FHE_OK;
-  const fhe_params& p = ctx->p;
   hipStream_t st = (hipStream_t)stream;
-  const size_t Wb = fhe_big_lwe_words(&p), Ws = fhe_small_lwe_words(&p);
-  // workspace: ct_v (B big) | sign (B big) | small (B) | v (B) | the query's
-  // D expanded ciphertexts | its stream id
-  rc = ensure_ws(ctx, 8 * (2 * (size_t)B * Wb + (size_t)B * Ws + (size_t)B + (size_t)D * Wb + 1));
+  QueryWs w;
+  rc = query_leveled(ctx, d_qbody, id0, h_mask_key, d_docs8, B, D, d_w, cst - T, false, &w, stream);
   if (rc) return rc;
-  u64* ctv = (u64*)ctx->ws;
-  u64* sgn = ctv + (size_t)B * Wb;
-  u64* small = sgn + (size_t)B * Wb;
-  int64_t* v = (int64_t*)(small + (size_t)B * Ws);
-  u64* ctq = (u64*)(v + B);
-  u64* idw = ctq + (size_t)D * Wb;
-  hipLaunchKernelGGL(k_store_word, dim3(1), dim3(64), 0, st, idw, (u64)id0);
-  HIPCHK(ctx, hipGetLastError());
-  rc = fhe_expand_seeded_batch(ctx, d_qbody, idw, 1, D, h_mask_key, ctq, stream);
+  rc = fhe_decrypt_batch(ctx, w.ctv, B, w.v, stream);
   if (rc) return rc;
-  rc = fhe_linear_query_batch(ctx, ctq, d_docs8, B, D, d_w, cst - T, ctv, stream);
+  rc = sign_extract_batch(ctx, w.ctv, B, w.sgn, w.small, st);
   if (rc) return rc;
-  rc = fhe_decrypt_batch(ctx, ctv, B, v, stream);
+  rc = fhe_decrypt_bits_batch(ctx, w.sgn, B, d_below, stream);
   if (rc) return rc;
-  rc = sign_extract_batch(ctx, ctv, B, sgn, small, st);
-  if (rc) return rc;
-  rc = fhe_decrypt_bits_batch(ctx, sgn, B, d_below, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_add_scalar, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, v, B, T, d_acc);
+  hipLaunchKernelGGL(k_add_scalar, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, w.v, B, T, d_acc);
   HIPCHK(ctx, hipGetLastError());
   return FHE_OK;
 }
 
+// The server of the two-party private query: the pipeline of
+// fhe_compare_query_batch without either decryption. The leveled ciphertexts
+// of acc - T are copied (the sign extraction consumes them) and packed with
+// every level; the sign ciphertexts with the first levels_bit levels (0: all).
+// Needs the evaluation keys and the packing key only.
+int fhe_search_query_batch(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0, const uint32_t h_mask_key[8],
+                           const void* d_docs8, int64_t B, int32_t D, const int64_t* d_w, int64_t cst, int64_t T,
+                           int32_t levels_bit, uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream) {
+  int rc = query_args(ctx, B, D);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  if (levels_bit < 0 || levels_bit > 8) return fail(ctx, FHE_E_ARG, "bad search query arguments (levels_bit outside [0, 8])");
+  if ((rc = need_eval_keys(ctx))) return rc;
+  if ((rc = need_pack_key(ctx))) return rc;
+  if (levels_bit > ctx->pk_level) return fail(ctx, FHE_E_ARG, "search query levels_bit exceeds the packing key's levels");
+  if (!h_mask_key || (B > 0 && (!d_qbody || !d_docs8 || !d_w || !d_glwe_acc || !d_glwe_bit)))
+    return fail(ctx, FHE_E_ARG, "null search query arguments");
+  if (B == 0) return FHE_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t Wb = fhe_big_lwe_words(&ctx->p);
+  QueryWs w;
+  rc = query_leveled(ctx, d_qbody, id0, h_mask_key, d_docs8, B, D, d_w, cst - T, true, &w, stream);
+  if (rc) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(w.cpy, w.ctv, 8 * (size_t)B * Wb, hipMemcpyDeviceToDevice, st));
+  rc = sign_extract_batch(ctx, w.ctv, B, w.sgn, w.small, st);
+  if (rc) return rc;
+  rc = pack_impl(ctx, w.cpy, B, ctx->pk_level, d_glwe_acc, st);
+  if (rc) return rc;
+  return pack_impl(ctx, w.sgn, B, levels_bit ? levels_bit : ctx->pk_level, d_glwe_bit, st);
+}
+
 int fhe_threshold_batch(fhe_ctx* ctx, const uint64_t* d_ct_acc, int64_t count, int64_t T, uint64_t* d_bit,
                         void* stream) {
-  int rc = need_keys(ctx);
+  int rc = need_eval_keys(ctx);
   if (rc) return rc;
   if (count < 0 || (count > 0 && (!d_ct_acc || !d_bit))) return fail(ctx, FHE_E_ARG, "bad threshold arguments");
   if (count == 0) return FHE_OK;
@@ -2148,6 +2488,7 @@ static ProfAcc* prof_bucket(fhe_ctx* ctx, const char* kernel) {
   if (!strcmp(kernel, "keyswitch")) return &ctx->prof_ks;
   if (!strcmp(kernel, "encrypt_linear")) return &ctx->prof_enc;
   if (!strcmp(kernel, "linear_query")) return &ctx->prof_lq;
+  if (!strcmp(kernel, "pack")) return &ctx->prof_pack;
   return nullptr;
 }
 

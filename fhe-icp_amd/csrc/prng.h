@@ -41,6 +41,8 @@ enum StreamTag : uint32_t {
   TAG_BSK6_NOISE = 26,
   TAG_MB6_MASK = 27,   // the mid0 gadget's multi-bit key
   TAG_MB6_NOISE = 28,
+  TAG_PACK_MASK = 29,  // the LWE -> GLWE packing key (fhe_keygen_pack_key)
+  TAG_PACK_NOISE = 30,
 };
 
 struct ChaKey {

@@ -96,6 +96,18 @@ SIGNATURES = [
     ("fhe_query_docs_pack", C.c_int, [_CTXP, _vp, _i64, _i32, _vp, _vp]),
     ("fhe_linear_query_batch", C.c_int, [_CTXP, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp]),
     ("fhe_compare_query_batch", C.c_int, [_CTXP, _vp, _u64, _vp, _vp, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _vp]),
+    ("fhe_import_eval_keys", C.c_int, [_CTXP, _vp, _vp, C.POINTER(C.c_void_p)]),
+    ("fhe_pack_key_words", C.c_size_t, [_P, _i32, _i32]),
+    ("fhe_keygen_pack_key_key", C.c_int, [_CTXP, _i32, _i32, _vp, _vp]),
+    ("fhe_keygen_pack_key", C.c_int, [_CTXP, _i32, _i32, _u64, _vp]),
+    ("fhe_export_pack_key", C.c_int, [_CTXP, _vp]),
+    ("fhe_import_pack_key", C.c_int, [_CTXP, _i32, _i32, _vp]),
+    ("fhe_pack_batch", C.c_int, [_CTXP, _vp, _i64, _i32, _vp, _vp]),
+    ("fhe_decrypt_packed_batch", C.c_int, [_CTXP, _vp, _i64, _i32, _vp, _vp]),
+    ("fhe_pack_plan", C.c_int, [_P, _i64, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                C.POINTER(C.c_int32)]),
+    ("fhe_search_query_batch", C.c_int, [_CTXP, _vp, _u64, _vp, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _vp,
+                                         _vp]),
     ("fhe_key_from_seed", None, [_u64, _vp]),
     ("fhe_quantize_pairs", C.c_int, [_CTXP, _vp, _i32, _vp, _i32, _i64, _i32, C.c_double, _i64, _i64, _i64, _vp, _vp]),
     ("fhe_dequantize", C.c_int, [_CTXP, _vp, _i64, C.c_double, _vp, _vp]),

@@ -45,6 +45,7 @@ class Engine:
         self.W = self.big + 1
         self.Ws = params.n + 1
         self.has_keys = False
+        self.pack_gadget = None   # (base_log, level) of the packing key, once one is generated or imported
 
     def close(self) -> None:
         if getattr(self, "_ctx", None):
@@ -412,6 +413,104 @@ class Engine:
                                                   _ptr(docs8), B, D, _ptr(w), int(cst), int(T), _ptr(acc),
                                                   _ptr(below), _stream(self.device)))
         return acc, below
+
+    # ------------------ two-party private query: evaluation keys, packing --
+    def keygen_pack(self, base_log: int, level: int, key=None, seed: int | None = None) -> None:
+        """Generate the LWE -> GLWE packing key for gadget (base_log, level)
+        (fhe_keygen_pack_key[_key]); `key` is a 256-bit ChaCha20 key (os.urandom
+        when neither is given), `seed` the 64-bit test form."""
+        if seed is not None:
+            rc = self._L.fhe_keygen_pack_key(self._ctx, int(base_log), int(level), C.c_uint64(seed),
+                                             _stream(self.device))
+        else:
+            import os
+            rc = self._L.fhe_keygen_pack_key_key(self._ctx, int(base_log), int(level),
+                                                 self._key(key if key is not None else os.urandom(32)),
+                                                 _stream(self.device))
+        self._chk(rc)
+        self.pack_gadget = (int(base_log), int(level))
+
+    def export_pack_key(self) -> np.ndarray:
+        b, L = self.pack_gadget
+        out = np.zeros(self._L.fhe_pack_key_words(C.byref(self._P), b, L), np.uint64)
+        self._chk(self._L.fhe_export_pack_key(self._ctx, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def import_pack_key(self, base_log: int, level: int, key) -> None:
+        a = np.ascontiguousarray(key, dtype=np.uint64)
+        if a.size != self._L.fhe_pack_key_words(C.byref(self._P), int(base_log), int(level)):
+            raise ValueError("packing key size does not match its gadget and these parameters")
+        self._chk(self._L.fhe_import_pack_key(self._ctx, int(base_log), int(level), C.c_void_p(a.ctypes.data)))
+        self.pack_gadget = (int(base_log), int(level))
+
+    def export_eval_keys(self) -> dict:
+        """Everything a server needs and nothing more, as numpy arrays: bsk,
+        ksk, every present gadget's key (gadget_bsk1..5) and, when one was
+        generated, the packing key with its gadget (pack_key, pack_gadget)."""
+        from .params import gadget_level
+        p = self.params
+        out = {"bsk": np.zeros(self._L.fhe_bsk_words(C.byref(self._P)), np.uint64),
+               "ksk": np.zeros(self._L.fhe_ksk_words(C.byref(self._P)), np.uint64)}
+        self._chk(self._L.fhe_export_keys(self._ctx, None, None, C.c_void_p(out["bsk"].ctypes.data),
+                                          C.c_void_p(out["ksk"].ctypes.data)))
+        for g in (1, 2, 3, 4, 5):
+            if gadget_level(p, g):
+                out[f"gadget_bsk{g}"] = self.export_fast_bsk(g)
+        if self.pack_gadget:
+            out["pack_key"] = self.export_pack_key()
+            out["pack_gadget"] = np.array(self.pack_gadget, dtype=np.int64)
+        return out
+
+    def import_eval_keys(self, d: dict) -> None:
+        """Install evaluation keys only (fhe_import_eval_keys; the packing key
+        too when the dict has one). The context holds no secret key afterwards."""
+        bsk = np.ascontiguousarray(d["bsk"], dtype=np.uint64)
+        ksk = np.ascontiguousarray(d["ksk"], dtype=np.uint64)
+        if bsk.size != self._L.fhe_bsk_words(C.byref(self._P)) or ksk.size != self._L.fhe_ksk_words(C.byref(self._P)):
+            raise ValueError("evaluation keys do not match these parameters")
+        gad = [np.ascontiguousarray(d[f"gadget_bsk{g}"], dtype=np.uint64) if f"gadget_bsk{g}" in d else None
+               for g in (1, 2, 3, 4, 5)]
+        for g, a in enumerate(gad, 1):
+            if a is not None and a.size != self._L.fhe_fast_bsk_words(C.byref(self._P), g):
+                raise ValueError(f"gadget {g}'s key does not match these parameters")
+        ptrs = (C.c_void_p * 5)(*[a.ctypes.data if a is not None else None for a in gad])
+        self._chk(self._L.fhe_import_eval_keys(self._ctx, C.c_void_p(bsk.ctypes.data), C.c_void_p(ksk.ctypes.data),
+                                               ptrs))
+        self.has_keys = True
+        if "pack_key" in d:
+            b, L = (int(x) for x in np.asarray(d["pack_gadget"]).reshape(2))
+            self.import_pack_key(b, L, d["pack_key"])
+
+    def glwe_count(self, count: int) -> int:
+        return -(-int(count) // self.params.N)
+
+    def pack(self, ct: torch.Tensor, count: int, levels: int = 0) -> torch.Tensor:
+        """count big LWEs -> ceil(count / N) GLWEs of (k+1)N words (fhe_pack_batch)."""
+        out = torch.empty((self.glwe_count(count), (self.params.k + 1) * self.params.N), dtype=torch.int64,
+                          device=self.device)
+        self._chk(self._L.fhe_pack_batch(self._ctx, _ptr(ct), int(count), int(levels), _ptr(out),
+                                         _stream(self.device)))
+        return out
+
+    def decrypt_packed(self, glwe: torch.Tensor, count: int, mode: int = 0) -> torch.Tensor:
+        """The first count coefficients of packed GLWEs (fhe_decrypt_packed_batch):
+        mode 0 signed values, 1 bits, 2 raw phases."""
+        out = torch.empty(int(count), dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_decrypt_packed_batch(self._ctx, _ptr(glwe), int(count), int(mode), _ptr(out),
+                                                   _stream(self.device)))
+        return out
+
+    def search_query(self, qbody: torch.Tensor, id0: int, mask_key, docs8: torch.Tensor, B: int, D: int,
+                     w: torch.Tensor, cst: int, T: int, levels_bit: int = 0):
+        """fhe_search_query_batch: the server side of the two-party private
+        query; (glwe_acc, glwe_bit), each ceil(B / N) x (k+1)N words."""
+        shape = (self.glwe_count(B), (self.params.k + 1) * self.params.N)
+        ga = torch.empty(shape, dtype=torch.int64, device=self.device)
+        gb = torch.empty(shape, dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_search_query_batch(self._ctx, _ptr(qbody), C.c_uint64(int(id0)), self._key(mask_key),
+                                                 _ptr(docs8), int(B), int(D), _ptr(w), int(cst), int(T),
+                                                 int(levels_bit), _ptr(ga), _ptr(gb), _stream(self.device)))
+        return ga, gb
 
     def topk(self, acc: torch.Tensor, below: torch.Tensor | None, k: int, base_idx: int = 0):
         oa = torch.empty(k, dtype=torch.int64, device=self.device)

@@ -447,6 +447,52 @@ def ks_round_bits(p: SchemeParams) -> int:
     return 0 if p.lwe_noise_bits < 14 else 8 * min((p.lwe_noise_bits - 6) // 8, 5)
 
 
+def pack_gadget_ok(base_log: int, level: int) -> bool:
+    """A packing gadget the library accepts: int8 digits, at most 8 levels,
+    every tie coin an input bit (fheicp.hip pack_gadget_ok)."""
+    return 1 <= base_log <= 7 and 1 <= level <= 8 and base_log * level + level <= 62
+
+
+def pack_var(p: SchemeParams, count: int, base_log: int, level: int) -> float:
+    """Variance the packing key switch adds to each packed phase, in units of
+    the integer words (fheicp.hip pack_var): the key rows'
+    noise through the digits of min(count, N) inputs, plus the rounding of the
+    kN mask words to base_log * level bits."""
+    B = 2.0 ** base_log
+    big = float(p.k * p.N)
+    m = float(min(count, p.N))
+    return (m * big * level * ((B * B + 2) / 12.0) * _tuniform_var(p.glwe_noise_bits)
+            + (1.0 + big / 2.0) * 2.0 ** (2 * (64 - base_log * level)) / 12.0)
+
+
+def pack_sigmas(p: SchemeParams, count: int, in_var: float, base_log: int, level: int, margin_log: int) -> float:
+    """Decision margin 2^margin_log in sigmas of a packed phase whose inputs
+    carry variance in_var (torus units)."""
+    return 2.0 ** margin_log / math.sqrt(in_var * 2.0 ** 128 + pack_var(p, count, base_log, level))
+
+
+def pack_plan(p: SchemeParams, count: int, in_var: float = 0.0):
+    """(base_log, level, bit_levels) of the packing key switch (fhe_pack_plan):
+    the cheapest gadget, fewest levels then the largest base_log <= 7, that
+    keeps 2^(63 - msg_bits) at 9.2 sigma; bit_levels the shortest level prefix
+    that keeps a bit at 2^63 (margin 2^62) there. When no gadget reaches the
+    bar, the most precise one: check pack_sigmas and report the margin."""
+    if count < 1 or not in_var >= 0:
+        raise ValueError("pack_plan needs count >= 1 and in_var >= 0")
+    mlog = 63 - p.msg_bits
+    gadgets = [(b, L) for L in range(1, 9) for b in range(7, 0, -1) if pack_gadget_ok(b, L)]
+    pick = next((g for g in gadgets if pack_sigmas(p, count, in_var, g[0], g[1], mlog) >= 9.2), None)
+    if pick is None:
+        best = -1.0
+        for g in gadgets:
+            sg = pack_sigmas(p, count, in_var, g[0], g[1], mlog)
+            if sg > best:
+                best, pick = sg, g
+    b, L = pick
+    lb = next((l for l in range(1, L + 1) if pack_sigmas(p, count, in_var, b, l, 62) >= 9.2), L)
+    return b, L, lb
+
+
 def _variances(p: SchemeParams, group: int = 1):
     """(bootstrap, key switch, modulus switch) output variances, relative to
     the 2^64 torus, for the main gadget of p on the classic

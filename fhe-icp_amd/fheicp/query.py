@@ -139,3 +139,150 @@ class EncryptedQuerySearch:
 
     def scores(self, acc) -> np.ndarray:
         return self.corpus.scores(acc)
+
+
+# ------------------------------------------------------------- two parties --
+# The same search with the two roles in two contexts: the
+# client keeps the secret key; the server holds evaluation keys only and
+# answers with packed GLWEs.
+#
+# Reply (uint64 vector):
+#     [REPLY_MAGIC, version | P0 << 32, B, T (two's complement),
+#      GLWEs of acc - T: ceil(B / N) x (k+1)N words, GLWEs of [acc < T]: the same]
+REPLY_MAGIC = int.from_bytes(b"FHEICPRP", "little")
+REPLY_HEADER_WORDS = 4
+# variance (torus units) of the leveled accumulator the plan assumes: the
+# worst-case leveled sigma of DESIGN.md §8, 2^-33
+LEVELED_VAR = (2.0 ** -33) ** 2
+
+
+def pack_reply(glwe_acc, glwe_bit, B: int, P0: int, T: int) -> np.ndarray:
+    ga = np.asarray(glwe_acc, dtype=np.uint64).reshape(-1)
+    gb = np.asarray(glwe_bit, dtype=np.uint64).reshape(-1)
+    head = np.array([REPLY_MAGIC, 1 | (int(P0) << 32), int(B), int(T) % (1 << 64)], dtype=np.uint64)
+    return np.concatenate([head, ga, gb])
+
+
+def unpack_reply(arr) -> dict:
+    a = np.asarray(arr)
+    if a.dtype != np.uint64 or a.ndim != 1 or a.size < REPLY_HEADER_WORDS or int(a[0]) != REPLY_MAGIC:
+        raise ValueError("not an fheicp packed reply")
+    if int(a[1]) & 0xFFFFFFFF != 1:
+        raise ValueError(f"unsupported reply version {int(a[1]) & 0xFFFFFFFF}")
+    words = a.size - REPLY_HEADER_WORDS
+    if words % 2:
+        raise ValueError("reply holds an odd number of GLWE words")
+    T = int(a[3])
+    return {"P0": int(a[1]) >> 32, "B": int(a[2]), "T": T - (1 << 64) if T >> 63 else T,
+            "glwe_acc": a[REPLY_HEADER_WORDS:REPLY_HEADER_WORDS + words // 2].copy(),
+            "glwe_bit": a[REPLY_HEADER_WORDS + words // 2:].copy()}
+
+
+def save_eval_keys(path: str, keys: dict) -> None:
+    """Evaluation keys (QueryClient.eval_keys) -> one .npz of plain arrays."""
+    with open(path, "wb") as f:
+        np.savez(f, **{k: np.asarray(v) for k, v in keys.items()})
+
+
+def load_eval_keys(path: str) -> dict:
+    with np.load(path, allow_pickle=False) as z:
+        return {k: z[k] for k in z.files}
+
+
+class QueryClient:
+    """The key holder: encrypts queries, hands out evaluation keys, decrypts
+    replies. Owns the secret context of a compiled EncryptedCorpus."""
+
+    def __init__(self, corpus: EncryptedCorpus, count: int = 1024, in_var: float = LEVELED_VAR, pack_seed=None):
+        """Generates the packing key planned for replies of up to `count`
+        results per GLWE (params.pack_plan; pack_seed: the 64-bit test form)."""
+        from .params import pack_plan, pack_sigmas
+        corpus._need()
+        self.corpus = corpus
+        self.single = EncryptedQuerySearch(corpus)
+        self.cq, self.P0 = corpus.cq, corpus.P0
+        scheme = corpus.scheme.with_msg_bits(self.P0)
+        self.base_log, self.level, self.bit_levels = pack_plan(scheme, count, in_var)
+        #: the plan's margin in sigmas (below 9.2 when no gadget reaches the bar)
+        self.margin = pack_sigmas(scheme, count, in_var, self.base_log, self.level, 63 - self.P0)
+        corpus.engine.keygen_pack(self.base_log, self.level, seed=pack_seed)
+
+    def encrypt_query(self, q, id0: int | None = None) -> np.ndarray:
+        return self.single.encrypt_query(q, id0)
+
+    def eval_keys(self) -> dict:
+        """What the server gets: bsk, ksk, the gadgets' keys, the packing key
+        with its gadget and the bit prefix. No secret key."""
+        d = self.corpus.engine.export_eval_keys()
+        d["pack_bit_levels"] = np.array([self.bit_levels], dtype=np.int64)
+        return d
+
+    def decrypt_reply(self, reply):
+        """-> (acc int64 [B], below int64 [B]) device tensors."""
+        eng = self.corpus.engine
+        r = unpack_reply(reply)
+        if r["P0"] != self.P0:
+            raise ValueError("reply was computed at a different width")
+        n1 = (eng.params.k + 1) * eng.params.N
+        if r["glwe_acc"].size != eng.glwe_count(r["B"]) * n1:
+            raise ValueError("reply size does not match its document count")
+        eng.set_msg_bits(self.P0)
+        acc = eng.decrypt_packed(eng.to_dev(r["glwe_acc"]), r["B"], 0) + r["T"]
+        below = eng.decrypt_packed(eng.to_dev(r["glwe_bit"]), r["B"], 1)
+        return acc, below
+
+    def top_k(self, acc, below, k: int, base_idx: int = 0):
+        return self.corpus.engine.topk(acc, below, k, base_idx)
+
+
+class QueryServer:
+    """The document holder: evaluation keys, the CorpusQuant and P0 only."""
+
+    MAX_BITS = EncryptedQuerySearch.MAX_BITS
+
+    def __init__(self, eval_keys: dict, cq, P0: int, device: int = 0, scheme=None):
+        from .engine import Engine
+        from .params import params_for_bits
+        if "pack_key" not in eval_keys:
+            raise ValueError("the evaluation keys hold no packing key")
+        self.cq, self.P0 = cq, int(P0)
+        self.scheme = (scheme if scheme is not None else params_for_bits(self.P0)).with_msg_bits(self.P0)
+        self.engine = Engine(self.scheme, device)
+        self.engine.import_eval_keys(eval_keys)
+        self.bit_levels = int(np.asarray(eval_keys.get("pack_bit_levels", [0])).reshape(-1)[0])
+
+    @classmethod
+    def from_npz(cls, path: str, cq, P0: int, device: int = 0, scheme=None) -> "QueryServer":
+        return cls(load_eval_keys(path), cq, P0, device, scheme)
+
+    def bound(self) -> int:
+        qw = np.abs(np.asarray(self.cq.model.q_w, dtype=np.int64))
+        return int(qw.sum()) * 4 ** (self.cq.n_e - 1) + abs(self.cq.q_b)
+
+    def plan(self, min_similarity: float | None):
+        """(w, cst, T) as EncryptedQuerySearch.plan: T on the worst-case range."""
+        b = self.bound()
+        T = self.cq.threshold_int(-b, b, min_similarity) if min_similarity is not None else -b
+        return np.asarray(self.cq.model.q_w, dtype=np.int64).copy(), self.cq.q_b, T
+
+    def pack_docs(self, docs):
+        import torch
+        if self.cq.n_e > self.MAX_BITS:
+            raise ValueError(f"private-query search needs embedding bits n_e <= {self.MAX_BITS}, got {self.cq.n_e}")
+        eng = self.engine
+        dd = docs if isinstance(docs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(docs))
+        dq = eng.quantize(dd.to(eng.device).contiguous(), self.cq.s_e, 0, self.cq.qmin, self.cq.qmax)
+        return eng.pack_docs(dq)
+
+    def search(self, payload, docs8, B: int, min_similarity: float | None) -> np.ndarray:
+        """One encrypted query against B packed documents -> the reply."""
+        eng = self.engine
+        pl = unpack_query(payload)
+        if pl["P0"] != self.P0 or pl["big"] != self.scheme.k * self.scheme.N:
+            raise ValueError("query was encrypted under different parameters")
+        if pl["D"] != len(self.cq.model.q_w):
+            raise ValueError(f"query holds {pl['D']} features, the model {len(self.cq.model.q_w)}")
+        w, cst, T = self.plan(min_similarity)
+        ga, gb = eng.search_query(eng.to_dev(pl["body"]), pl["id0"], pl["mask_key"], docs8, int(B), pl["D"],
+                                  eng.to_dev(w), cst, T, self.bit_levels)
+        return pack_reply(ga.cpu().numpy().view(np.uint64), gb.cpu().numpy().view(np.uint64), B, self.P0, T)

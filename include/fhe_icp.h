@@ -145,6 +145,18 @@ int fhe_import_keys(fhe_ctx* ctx, const uint64_t* h_s_small, const uint64_t* h_s
  * gadget). FHE_E_STATE without that gadget. Synchronous. */
 size_t fhe_fast_bsk_words(const fhe_params* params, int32_t which);
 int fhe_export_fast_bsk(fhe_ctx* ctx, int32_t which, uint64_t* h_bsk);
+/* Evaluation keys only: bsk, ksk and every present gadget's key
+ * (h_gadget_bsk[g - 1] in fhe_export_fast_bsk's layout for which = g; ignored
+ * for absent gadgets, FHE_E_ARG when a present one is missing). The keys are
+ * used as given, nothing is re-encrypted. The context then holds no secret
+ * key (one it held is zeroed and freed): the encrypting, decrypting, compare,
+ * score and sign-trace entry points, fhe_keygen_pack_key and fhe_export_keys
+ * with a secret pointer return FHE_E_STATE; the leveled, key-switch,
+ * bootstrap, sign, threshold, query, top-k, pack and search entry points and
+ * fhe_export_keys(NULL, NULL, bsk, ksk) / fhe_export_fast_bsk work.
+ * Synchronous. */
+int fhe_import_eval_keys(fhe_ctx* ctx, const uint64_t* h_bsk, const uint64_t* h_ksk,
+                         const uint64_t* const h_gadget_bsk[5]);
 
 /* ---- client side: encrypt / decrypt --------------------------------------
  * Replaces the per-sample encrypt/decrypt of predict(fhe="execute")
@@ -385,6 +397,61 @@ int fhe_linear_query_batch(fhe_ctx* ctx, const uint64_t* d_ct_q, const void* d_d
 int fhe_compare_query_batch(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0, const uint32_t h_mask_key[8],
                             const void* d_docs8, int64_t B, int32_t D, const int64_t* d_w, int64_t cst, int64_t T,
                             int64_t* d_acc, int64_t* d_below, void* stream);
+
+/* ---- two-party private query: packed GLWE replies --------
+ * A server that holds evaluation keys only (fhe_import_eval_keys) cannot
+ * decrypt in place; it folds up to N result LWEs into one GLWE under the big
+ * key with a packing key switch and returns (k+1)N words per N results.
+ * All arithmetic modulo 2^64. The gadget (base_log b, level L), 1 <= b <= 7,
+ * 1 <= L <= 8, L (b + 1) <= 62, is an argument, not a field of fhe_params.
+ * Packing key row (i, l), i < kN, l = 1..L: a GLWE encryption under the big
+ * key read as k polynomials (S_c[t] = s_big[cN + t]) of the constant
+ * polynomial s_big[i] * 2^(64 - b l), noise TUniform(glwe_noise_bits), stream
+ * tags 29/30; layout [i][l][component 0..k][coef], fhe_pack_key_words words
+ * (0 for a gadget out of range). For big LWEs (a_j, b_j), j < count <= N:
+ *   out = sum_j X^j [ (0, .., 0, b_j) - sum_i sum_{l <= L'} d_{j,i,l} PK[i][l] ]
+ * negacyclic in X, d_{j,i,.} the key switch's balanced digits with tie coins
+ * of a_{j,i} on L' <= L levels. Coefficient j of the phase B - sum_c A_c S_c
+ * is LWE j's phase plus rounding and key noise; for count > N, GLWE g packs
+ * inputs gN .. gN + N - 1; coefficients past count carry noise only. */
+size_t fhe_pack_key_words(const fhe_params* params, int32_t base_log, int32_t level);
+/* Generate the context's packing key (needs the secret key; replaces any
+ * earlier one). `*_key` / seed forms as for the encrypting entry points. */
+int fhe_keygen_pack_key_key(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint32_t h_key[8], void* stream);
+int fhe_keygen_pack_key(fhe_ctx* ctx, int32_t base_log, int32_t level, uint64_t seed, void* stream);
+/* Host copy of the packing key / install one (converted once to byte planes
+ * for the i8 matrix cores). Import needs no other key. Synchronous. */
+int fhe_export_pack_key(fhe_ctx* ctx, uint64_t* h_out);
+int fhe_import_pack_key(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint64_t* h_in);
+/* Pack count big LWEs (count x (kN+1)) into ceil(count / N) GLWEs
+ * (d_glwe: each (k+1)N words [A_1 .. A_k, B]) on the first `levels` levels of
+ * the key (0: all). Needs only the packing key. Bit-exact. */
+int fhe_pack_batch(fhe_ctx* ctx, const uint64_t* d_ct, int64_t count, int32_t levels, uint64_t* d_glwe, void* stream);
+/* Decrypt the first `count` coefficients of packed GLWEs: mode 0 signed
+ * msg_bits-bit values (as fhe_decrypt_batch), 1 bits (fhe_decrypt_bits_batch),
+ * 2 raw phases (fhe_phase_batch). Needs the secret key. */
+int fhe_decrypt_packed_batch(fhe_ctx* ctx, const uint64_t* d_glwe, int64_t count, int32_t mode, int64_t* d_out,
+                             void* stream);
+/* The cheapest gadget (fewest levels, then the largest base_log <= 7) with
+ *   2^(63 - msg_bits) / sqrt(in_var 2^128 + var_pack) >= 9.2,
+ *   var_pack = min(count, N) kN L ((B^2 + 2) / 12) tuniform_var(glwe_noise_bits)
+ *              + (1 + kN / 2) 2^(2 (64 - b L)) / 12,   B = 2^b,
+ * in_var the inputs' variance in torus units; bit_levels the shortest level
+ * prefix that keeps 9.2 sigma for a bit at 2^63 (margin 2^62). When no gadget
+ * reaches the bar, the most precise one (the caller reports the margin).
+ * Host only; fheicp.params.pack_plan is the same function. */
+int fhe_pack_plan(const fhe_params* params, int64_t count, double in_var, int32_t* base_log, int32_t* level,
+                  int32_t* bit_levels);
+/* The server entry: fhe_compare_query_batch's pipeline without either
+ * decryption. Expand the query -> planes -> GEMM with cst - T -> copy of the
+ * leveled ciphertexts -> sign extraction -> pack the copies into d_glwe_acc
+ * (all levels) and the sign ciphertexts into d_glwe_bit (the first levels_bit
+ * levels, 0: all); each ceil(B / N) x (k+1)N words. Needs evaluation keys and
+ * the packing key, no secret. The client decrypts d_glwe_acc with mode 0 and
+ * adds T, and d_glwe_bit with mode 1 (= below). */
+int fhe_search_query_batch(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0, const uint32_t h_mask_key[8],
+                           const void* d_docs8, int64_t B, int32_t D, const int64_t* d_w, int64_t cst, int64_t T,
+                           int32_t levels_bit, uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream);
 /* The 64-bit-seed -> 256-bit ChaCha key expansion used by the seed forms
  * (fhe_keygen, fhe_encrypt_batch, ...; splitmix64): tests and
  * benches only. Host only. */
@@ -434,8 +501,9 @@ int fhe_stream_sync(fhe_ctx* ctx, void* stream);
  * processed for kernel "blind_rotate" (all gadgets), "blind_rotate_main",
  * "blind_rotate_fast" (fhe_params.pbs_fast_*), "blind_rotate_fast2",
  * "blind_rotate_mid", "blind_rotate_mid2", "blind_rotate_mid0", "keyswitch", "encrypt_linear"
- * (the fused client encryption + leveled dot) or "linear_query" (the
- * private-query leveled step: query planes + GEMM, one bracket around both),
+ * (the fused client encryption + leveled dot), "linear_query" (the
+ * private-query leveled step: query planes + GEMM, one bracket around both)
+ * or "pack" (the packing key switch: digits + GEMM + rotation, one bracket),
  * then resets what it read. */
 int fhe_profile_enable(fhe_ctx* ctx, int enable);
 int fhe_profile_read(fhe_ctx* ctx, const char* kernel, double* total_ms, int64_t* launches, int64_t* items);

@@ -57,6 +57,18 @@ _PROTOS = {
     "fhe_query_docs_pack": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
     "fhe_linear_query_batch": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp]),
     "fhe_compare_query_batch": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _vp]),
+    # two parties: evaluation-only server, packed GLWE replies
+    "fhe_import_eval_keys": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
+    "fhe_pack_key_words": (C.c_size_t, [C.POINTER(fhe_params), _i32, _i32]),
+    "fhe_pack_plan": (C.c_int, [C.POINTER(fhe_params), _i64, C.c_double, C.POINTER(_i32), C.POINTER(_i32),
+                                C.POINTER(_i32)]),
+    "fhe_keygen_pack_key_key": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "fhe_keygen_pack_key": (C.c_int, [_vp, _i32, _i32, _u64, _vp]),
+    "fhe_export_pack_key": (C.c_int, [_vp, _vp]),
+    "fhe_import_pack_key": (C.c_int, [_vp, _i32, _i32, _vp]),
+    "fhe_pack_batch": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "fhe_decrypt_packed_batch": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "fhe_search_query_batch": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
 }
 
 
@@ -204,6 +216,46 @@ class GpuCompare:
             self._ok(self.L.fhe_compare_query_batch(self.ctx, bufs[0], int(id0), mk, docs8, B, D, bufs[1], int(cst),
                                                     int(T), bufs[2], bufs[3], None))
             return self._to_host(bufs[2], B), self._to_host(bufs[3], B)
+        finally:
+            for d in bufs:
+                self.L.fhe_dev_free(self.ctx, d)
+
+    # ---- two parties: packed replies -----------------------------------------
+    def keygen_pack(self, count: int = 1024, in_var: float = 0.0, seed: int | None = None):
+        """Key holder: plan (fhe_pack_plan) and generate the packing key;
+        (base_log, level, bit_levels)."""
+        b, lv, lb = _i32(), _i32(), _i32()
+        self._ok(self.L.fhe_pack_plan(C.byref(self.P), count, in_var, C.byref(b), C.byref(lv), C.byref(lb)))
+        if seed is None:
+            self._ok(self.L.fhe_keygen_pack_key_key(self.ctx, b.value, lv.value, _key32(), None))
+        else:
+            self._ok(self.L.fhe_keygen_pack_key(self.ctx, b.value, lv.value, seed, None))  # tests only
+        return b.value, lv.value, lb.value
+
+    def search_query(self, body: np.ndarray, id0: int, mask_key, docs, q_w: np.ndarray, cst: int, T: int,
+                     levels_bit: int = 0):
+        """Server side without decryption: (glwe_acc, glwe_bit) uint64 host
+        arrays of ceil(B / N) * (k+1) * N words each (the reply's two blocks)."""
+        docs8, B, D = docs
+        words = -(-B // self.P.N) * (self.P.k + 1) * self.P.N
+        bufs = [self._to_dev(np.asarray(body, np.uint64)), self._to_dev(np.asarray(q_w, np.int64)),
+                self._alloc(8 * words), self._alloc(8 * words)]
+        try:
+            mk = (C.c_uint32 * 8)(*[int(x) for x in mask_key])
+            self._ok(self.L.fhe_search_query_batch(self.ctx, bufs[0], int(id0), mk, docs8, B, D, bufs[1], int(cst),
+                                                   int(T), int(levels_bit), bufs[2], bufs[3], None))
+            return self._to_host(bufs[2], words).view(np.uint64), self._to_host(bufs[3], words).view(np.uint64)
+        finally:
+            for d in bufs:
+                self.L.fhe_dev_free(self.ctx, d)
+
+    def decrypt_packed(self, glwe: np.ndarray, count: int, mode: int) -> np.ndarray:
+        """Key holder: the first count coefficients of packed GLWEs; mode 0
+        signed values, 1 bits, 2 raw phases."""
+        bufs = [self._to_dev(np.asarray(glwe, np.uint64)), self._alloc(8 * count)]
+        try:
+            self._ok(self.L.fhe_decrypt_packed_batch(self.ctx, bufs[0], count, mode, bufs[1], None))
+            return self._to_host(bufs[1], count)
         finally:
             for d in bufs:
                 self.L.fhe_dev_free(self.ctx, d)

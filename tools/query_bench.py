@@ -15,6 +15,14 @@ n_bits 6 and 8, in one process:
     oracle restatement. A shape whose worst-case width P0 has no parameter
     set (P0 > 27) reports null there.
 
+With --two-party (docs/AB_LOG_r08.md) it measures the two-party
+search instead: QueryServer.search on an evaluation-only context (host clock
+around the call: expansion, GEMM, sign extraction, both packings and the
+reply's copy to the host) interleaved step by step, in alternating order,
+with fhe_compare_query_batch on the key holder's context; the "pack" profile
+bucket per search, the reply's size, and the parity of the client's decrypted
+(acc, below) with the single-party result.
+
 The floor of the leveled step is its output, B * (kN + 1) * 8 bytes, over the
 6.29 TB/s a float4 copy reaches on the MI355X; `floor_fraction` is that floor
 over the measured time. Prints one JSON line and writes it to --out.
@@ -114,6 +122,70 @@ def end_to_end(cq, oq, B: int, D: int, n_bits: int, reps: int) -> dict:
             "pbs_per_compare": sign_pbs_count(c.scheme)}
 
 
+def two_party(cq, oq, B: int, D: int, n_bits: int, steps: int, warmup: int) -> dict:
+    """Server search (evaluation keys only, packed reply) against the
+    single-party compare, interleaved in alternating order."""
+    import numpy as np
+    import torch
+    from oracle import quant_ref as Q
+    from fheicp.corpus import EncryptedCorpus
+    from fheicp.query import EncryptedQuerySearch, QueryClient, QueryServer
+    c = EncryptedCorpus(cq).compile(key_seed=5, device=0, noise_seed=6)
+    single = EncryptedQuerySearch(c)
+    client = QueryClient(c, count=B, pack_seed=17)
+    server = QueryServer(client.eval_keys(), cq, c.P0)
+    q, docs = Q.make_corpus(D, B, seed=21)
+    docs8_c, docs8_s = single.pack_docs(docs), server.pack_docs(docs)
+    payload = client.encrypt_query(q)
+    server.engine.profile(True)
+    t_single, t_server, t_pack = [], [], []
+
+    def run_single():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = single.compare(payload, docs8_c, B, 0.5)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    def run_server():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = server.search(payload, docs8_s, B, 0.5)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    for i in range(warmup + steps):
+        if i % 2:
+            (ts, res), (tv, reply) = run_single(), run_server()
+        else:
+            (tv, reply), (ts, res) = run_server(), run_single()
+        pk = server.engine.profile_read("pack")
+        assert pk["launches"] == 2
+        if i >= warmup:
+            t_single.append(ts)
+            t_server.append(tv)
+            t_pack.append(pk["total_ms"])
+    server.engine.profile(False)
+    acc, below = client.decrypt_reply(reply)
+    ref = Q.corpus_accumulate(oq, cq.s_e, n_bits, q, docs)
+    scores = np.float64(Q.corpus_out_scale(oq, cq.s_e)) * ref.astype(np.float64)
+    parity = bool(torch.equal(acc, res[0]) and torch.equal(below, res[1]))
+    exact = bool(np.array_equal(acc.cpu().numpy(), ref) and
+                 np.array_equal(below.cpu().numpy(), (scores < 0.5).astype(np.int64)))
+    s_ms, v_ms = statistics.median(t_single) * 1e3, statistics.median(t_server) * 1e3
+    p = c.scheme
+    out = {"server_search_ms": v_ms, "server_search_min_ms": min(t_server) * 1e3, "compare_query_ms": s_ms,
+           "compare_query_min_ms": min(t_single) * 1e3, "ratio_server_over_compare": v_ms / s_ms,
+           "meets_bar": v_ms <= 1.10 * s_ms, "pack_ms_per_search": statistics.median(t_pack),
+           "pack_kernel": server.engine.kernel_name("pack"), "pack_gadget": [client.base_log, client.level],
+           "pack_bit_levels": client.bit_levels, "pack_margin_sigmas": client.margin,
+           "reply_bytes": int(reply.nbytes), "unpacked_reply_bytes": 2 * B * (p.k * p.N + 1) * 8,
+           "parity_with_compare_query": parity, "bit_exact": exact, "steps": steps, "warmup": warmup}
+    server.engine.close()
+    c.engine.close()
+    return out
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batch", type=int, default=1024)
@@ -124,6 +196,9 @@ def main() -> int:
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--no-end-to-end", action="store_true",
                     help="the leveled step only (kernel traces: no keygen, no sign extraction)")
+    ap.add_argument("--two-party", action="store_true",
+                    help="the two-party search (evaluation-only server, packed reply) against the single-party "
+                         "compare, --launches interleaved steps after --warmup")
     ap.add_argument("--out", default=str(REPO / "profiles" / "query_bench.json"))
     a = ap.parse_args()
     if a.launches < 20:
@@ -139,6 +214,12 @@ def main() -> int:
         for nb in a.n_bits:
             cq, oq = corpus_quant(D, nb)
             P0 = cq.worst_msg_bits()
+            if a.two_party:
+                row = {"B": a.batch, "D": D, "n_bits": nb, "P0": P0,
+                       "two_party": two_party(cq, oq, a.batch, D, nb, a.launches, a.warmup) if P0 <= MAX_BITS else None}
+                row["meets_bar"] = row["two_party"] is None or row["two_party"]["meets_bar"]
+                shapes.append(row)
+                continue
             # the leveled step's shape is B x D x (kN + 1): the same for every planned width
             eng = Engine(params_for_bits(min(P0, MAX_BITS)), 0)
             row = {"B": a.batch, "D": D, "n_bits": nb, "P0": P0}
