@@ -10,6 +10,8 @@
 //                     the i8 MFMA GEMM of one encrypted query x clear documents
 //   k_pack.h          LWE -> GLWE packing key switch (two-party replies): wide
 //                     digits, key generation, rotation, packed decryption
+//   k_extprod.h       both-private search: GGSW query encryption, GLWE document
+//                     digits, Toeplitz byte planes, slot extraction
 //   k_blind_rotate.h  blind rotation (external products over an f64 wave FFT):
 //                     v4 (br_v4.h, the default hot kernel), v2/v3, v1
 //   this file         context, launch selection, profiling, the C ABI
@@ -32,6 +34,7 @@
 #include "k_server.h"
 #include "k_query.h"
 #include "k_pack.h"
+#include "k_extprod.h"
 #include "k_blind_rotate.h"
 
 // ============================================================ host =========
@@ -101,6 +104,11 @@ struct fhe_ctx {
   void* pack_ws = nullptr;  // digits | zero bodies | the GEMM's count x (k+1)N result
   size_t pack_ws_bytes = 0;
   ProfAcc prof_pack;        // fhe_pack_batch: k_pack_digits + the GEMM + k_pack_rotate
+  // both-private search (k_extprod.h): the query's Toeplitz byte planes |
+  // zero bodies | the GEMM's G x (k+1)N result, allocated on first use
+  void* xp_ws = nullptr;
+  size_t xp_ws_bytes = 0;
+  ProfAcc prof_xp;          // fhe_linear_ggsw_batch: k_extprod_planes + the GEMM + k_extprod_extract
 };
 
 static std::mutex g_err_mu;
@@ -548,7 +556,7 @@ void fhe_ctx_destroy(fhe_ctx* ctx) {
                       (void*)ctx->bskf[4], (void*)ctx->bskf_fft[4],
                       (void*)ctx->ksk8, (void*)ctx->ks_ws, (void*)ctx->ks_ws1, (void*)ctx->tw4, (void*)ctx->bsk_fft_v2,
                       (void*)ctx->psi, (void*)ctx->mb_msg, ctx->lq_ws, (void*)ctx->pk, (void*)ctx->pk8,
-                      ctx->pack_ws})
+                      ctx->pack_ws, ctx->xp_ws})
       (void)hipFree(ptr);
     for (hipStream_t s : ctx->lane_st)
       if (s) (void)hipStreamDestroy(s);
@@ -560,6 +568,7 @@ void fhe_ctx_destroy(fhe_ctx* ctx) {
     free_ev(ctx->prof_enc);
     free_ev(ctx->prof_lq);
     free_ev(ctx->prof_pack);
+    free_ev(ctx->prof_xp);
   }
   delete ctx;
 }
@@ -2222,27 +2231,67 @@ struct QueryWs {
   int64_t* v;
   u64* cpy;
 };
-static int query_leveled(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0, const uint32_t h_mask_key[8],
-                         const void* d_docs8, int64_t B, int32_t D, const int64_t* d_w, int64_t cst, bool keep_copy,
-                         QueryWs* w, void* stream) {
+// the workspace above with `extra` words in the query's place
+static int leveled_ws(fhe_ctx* ctx, int64_t B, size_t extra, bool keep_copy, QueryWs* w, u64** d_extra) {
   const fhe_params& p = ctx->p;
-  hipStream_t st = (hipStream_t)stream;
   const size_t Wb = fhe_big_lwe_words(&p), Ws = fhe_small_lwe_words(&p);
-  int rc = ensure_ws(ctx, 8 * (2 * (size_t)B * Wb + (size_t)B * Ws + (size_t)B + (size_t)D * Wb + 1 +
+  int rc = ensure_ws(ctx, 8 * (2 * (size_t)B * Wb + (size_t)B * Ws + (size_t)B + extra +
                                (keep_copy ? (size_t)B * Wb : 0)));
   if (rc) return rc;
   w->ctv = (u64*)ctx->ws;
   w->sgn = w->ctv + (size_t)B * Wb;
   w->small = w->sgn + (size_t)B * Wb;
   w->v = (int64_t*)(w->small + (size_t)B * Ws);
-  u64* ctq = (u64*)(w->v + B);
+  u64* ex = (u64*)(w->v + B);
+  if (d_extra) *d_extra = ex;
+  w->cpy = keep_copy ? ex + extra : nullptr;
+  return FHE_OK;
+}
+static int query_leveled(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0, const uint32_t h_mask_key[8],
+                         const void* d_docs8, int64_t B, int32_t D, const int64_t* d_w, int64_t cst, bool keep_copy,
+                         QueryWs* w, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const size_t Wb = fhe_big_lwe_words(&ctx->p);
+  u64* ctq;
+  int rc = leveled_ws(ctx, B, (size_t)D * Wb + 1, keep_copy, w, &ctq);
+  if (rc) return rc;
   u64* idw = ctq + (size_t)D * Wb;
-  w->cpy = keep_copy ? idw + 1 : nullptr;
   hipLaunchKernelGGL(k_store_word, dim3(1), dim3(64), 0, st, idw, (u64)id0);
   HIPCHK(ctx, hipGetLastError());
   rc = fhe_expand_seeded_batch(ctx, d_qbody, idw, 1, D, h_mask_key, ctq, stream);
   if (rc) return rc;
   return fhe_linear_query_batch(ctx, ctq, d_docs8, B, D, d_w, cst, w->ctv, stream);
+}
+
+// What follows the leveled step, shared by the private-query and the
+// both-private entries. Single party: decrypt the leveled accumulator of
+// acc - T, sign extraction, decrypt the threshold bit, add T back.
+static int post_leveled_compare(fhe_ctx* ctx, const QueryWs& w, int64_t B, int64_t T, int64_t* d_acc,
+                                int64_t* d_below, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  int rc = fhe_decrypt_batch(ctx, w.ctv, B, w.v, stream);
+  if (rc) return rc;
+  rc = sign_extract_batch(ctx, w.ctv, B, w.sgn, w.small, st);
+  if (rc) return rc;
+  rc = fhe_decrypt_bits_batch(ctx, w.sgn, B, d_below, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_add_scalar, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, w.v, B, T, d_acc);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+// Evaluation-only server: copy the leveled ciphertexts (the sign extraction
+// consumes them), sign extraction, pack the copies with every level and the
+// sign ciphertexts with the first levels_bit levels (0: all).
+static int post_leveled_search(fhe_ctx* ctx, const QueryWs& w, int64_t B, int32_t levels_bit, uint64_t* d_glwe_acc,
+                               uint64_t* d_glwe_bit, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const size_t Wb = fhe_big_lwe_words(&ctx->p);
+  HIPCHK(ctx, hipMemcpyAsync(w.cpy, w.ctv, 8 * (size_t)B * Wb, hipMemcpyDeviceToDevice, st));
+  int rc = sign_extract_batch(ctx, w.ctv, B, w.sgn, w.small, st);
+  if (rc) return rc;
+  rc = pack_impl(ctx, w.cpy, B, ctx->pk_level, d_glwe_acc, st);
+  if (rc) return rc;
+  return pack_impl(ctx, w.sgn, B, levels_bit ? levels_bit : ctx->pk_level, d_glwe_bit, st);
 }
 
 int fhe_compare_query_batch(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0, const uint32_t h_mask_key[8],
@@ -2254,19 +2303,10 @@ int fhe_compare_query_batch(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0,
   if (!h_mask_key || (B > 0 && (!d_qbody || !d_docs8 || !d_w || !d_acc || !d_below)))
     return fail(ctx, FHE_E_ARG, "null compare query arguments");
   if (B == 0) return FHE_OK;
-  hipStream_t st = (hipStream_t)stream;
   QueryWs w;
   rc = query_leveled(ctx, d_qbody, id0, h_mask_key, d_docs8, B, D, d_w, cst - T, false, &w, stream);
   if (rc) return rc;
-  rc = fhe_decrypt_batch(ctx, w.ctv, B, w.v, stream);
-  if (rc) return rc;
-  rc = sign_extract_batch(ctx, w.ctv, B, w.sgn, w.small, st);
-  if (rc) return rc;
-  rc = fhe_decrypt_bits_batch(ctx, w.sgn, B, d_below, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_add_scalar, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, w.v, B, T, d_acc);
-  HIPCHK(ctx, hipGetLastError());
-  return FHE_OK;
+  return post_leveled_compare(ctx, w, B, T, d_acc, d_below, stream);
 }
 
 // The server of the two-party private query: the pipeline of
@@ -2286,17 +2326,198 @@ int fhe_search_query_batch(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0, 
   if (!h_mask_key || (B > 0 && (!d_qbody || !d_docs8 || !d_w || !d_glwe_acc || !d_glwe_bit)))
     return fail(ctx, FHE_E_ARG, "null search query arguments");
   if (B == 0) return FHE_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t Wb = fhe_big_lwe_words(&ctx->p);
   QueryWs w;
   rc = query_leveled(ctx, d_qbody, id0, h_mask_key, d_docs8, B, D, d_w, cst - T, true, &w, stream);
   if (rc) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(w.cpy, w.ctv, 8 * (size_t)B * Wb, hipMemcpyDeviceToDevice, st));
-  rc = sign_extract_batch(ctx, w.ctv, B, w.sgn, w.small, st);
+  return post_leveled_search(ctx, w, B, levels_bit, d_glwe_acc, d_glwe_bit, stream);
+}
+
+// ---- both-private search: GGSW query x GLWE documents (k_extprod.h, §8.7) --
+// the gadget bounds are the packing key switch's (int8 digits, tie coins)
+static int ggsw_args(fhe_ctx* ctx, int64_t B, int32_t D, int32_t beta, int32_t L) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  if (B < 0 || D <= 0) return fail(ctx, FHE_E_ARG, "bad ggsw arguments (B < 0 or D <= 0)");
+  if (D > ctx->p.N) return fail(ctx, FHE_E_ARG, "ggsw dimension D > N: a document must fit one GLWE");
+  if (!pack_gadget_ok(beta, L))
+    return fail(ctx, FHE_E_ARG, "ggsw gadget out of range (1 <= base_log <= 7, 1 <= level <= 8, "
+                                "level * (base_log + 1) <= 62)");
+  return FHE_OK;
+}
+size_t fhe_ggsw_words(const fhe_params* p, int32_t base_log, int32_t level) {
+  if (!p || !pack_gadget_ok(base_log, level)) return 0;
+  return (size_t)(p->k + 1) * level * (p->k + 1) * p->N;
+}
+
+// Variance of an extracted phase, integer-word units: the GGSW rows' noise
+// through the (noiseless) message and through the digits, plus the rounding
+// of the document's (k+1)N words to beta L bits times the query polynomial.
+// fheicp/params.py extprod_var is the same expression.
+static double extprod_var(const fhe_params& p, double w2, int beta, int L) {
+  const double B = std::ldexp(1.0, beta), tv = tuniform_var(p.glwe_noise_bits);
+  return w2 * tv + (double)(p.k + 1) * L * p.N * ((B * B + 2) / 12.0) * tv +
+         w2 * (1.0 + (double)p.k * p.N / 2.0) * std::ldexp(1.0, 2 * (64 - beta * L)) / 12.0;
+}
+int fhe_extprod_plan(const fhe_params* params, double w_norm2, int32_t* base_log, int32_t* level) {
+  std::string why;
+  if (validate(params, why)) return fail(nullptr, FHE_E_ARG, why);
+  if (!(w_norm2 >= 0)) return fail(nullptr, FHE_E_ARG, "bad extprod-plan arguments (w_norm2 >= 0)");
+  const fhe_params& p = *params;
+  if (base_log) *base_log = 0;
+  if (level) *level = 0;
+  for (int L = 1; L <= 8; ++L)
+    for (int beta = 7; beta >= 1; --beta)
+      if (pack_gadget_ok(beta, L) &&
+          std::ldexp(1.0, 63 - p.msg_bits) / std::sqrt(extprod_var(p, w_norm2, beta, L)) >= 9.2) {
+        if (base_log) *base_log = beta;
+        if (level) *level = L;
+        return FHE_OK;
+      }
+  return fail(nullptr, FHE_E_STATE, "no ggsw gadget keeps 2^(63 - msg_bits) at 9.2 sigma for this query norm");
+}
+
+static int encrypt_ggsw_impl(fhe_ctx* ctx, const int64_t* d_w, int32_t D, int32_t beta, int32_t L, const ChaKey& K,
+                             uint64_t id0, uint64_t* d_ggsw, void* stream) {
+  int rc = ggsw_args(ctx, 0, D, beta, L);  // argument errors first: a host-only context reports them too
   if (rc) return rc;
-  rc = pack_impl(ctx, w.cpy, B, ctx->pk_level, d_glwe_acc, st);
+  if ((rc = need_secret(ctx))) return rc;
+  if (!d_w || !d_ggsw) return fail(ctx, FHE_E_ARG, "null ggsw buffers");
+  const fhe_params& p = ctx->p;
+  hipLaunchKernelGGL(k_encrypt_ggsw, dim3((unsigned)((p.k + 1) * L)), dim3(256), 8 * (size_t)p.N + p.N,
+                     (hipStream_t)stream, K, p.N, p.k, (int)L, (int)beta, p.glwe_noise_bits, ctx->s_big, d_w, (int)D,
+                     (u64)id0, d_ggsw);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+int fhe_encrypt_ggsw(fhe_ctx* ctx, const int64_t* d_w, int32_t D, int32_t base_log, int32_t level, uint64_t seed,
+                     uint64_t id0, uint64_t* d_ggsw, void* stream) {
+  return encrypt_ggsw_impl(ctx, d_w, D, base_log, level, key_from_seed(seed), id0, d_ggsw, stream);
+}
+int fhe_encrypt_ggsw_key(fhe_ctx* ctx, const int64_t* d_w, int32_t D, int32_t base_log, int32_t level,
+                         const uint32_t h_key[8], uint64_t id0, uint64_t* d_ggsw, void* stream) {
+  ChaKey K;
+  if (!key_arg(h_key, K)) return fail(ctx, FHE_E_ARG, "null encryption key");
+  return encrypt_ggsw_impl(ctx, d_w, D, base_log, level, K, id0, d_ggsw, stream);
+}
+
+// documents per GLWE and GLWEs per batch
+static int ggsw_slots(const fhe_params& p, int32_t D) { return p.N / D; }
+static int64_t ggsw_glwes(const fhe_params& p, int64_t B, int32_t D) {
+  const int S = ggsw_slots(p, D);
+  return (B + S - 1) / S;
+}
+size_t fhe_glwe_docs_bytes(const fhe_params* p, int64_t B, int32_t D, int32_t level) {
+  if (!p || B < 0 || D <= 0 || D > p->N || level < 1 || level > 8) return 0;
+  return (size_t)((ggsw_glwes(*p, B, D) + 15) / 16) * 16 * (size_t)(p->k + 1) * p->N * level;
+}
+int fhe_glwe_docs_pack(fhe_ctx* ctx, const uint64_t* d_glwe, int64_t B, int32_t D, int32_t base_log, int32_t level,
+                       void* d_docs8, void* stream) {
+  int rc = ggsw_args(ctx, B, D, base_log, level);  // argument errors first
   if (rc) return rc;
-  return pack_impl(ctx, w.sgn, B, levels_bit ? levels_bit : ctx->pk_level, d_glwe_bit, st);
+  if ((rc = need_device(ctx))) return rc;
+  if (B > 0 && (!d_glwe || !d_docs8)) return fail(ctx, FHE_E_ARG, "null ggsw document buffers");
+  if (B == 0) return FHE_OK;
+  const fhe_params& p = ctx->p;
+  hipStream_t st = (hipStream_t)stream;
+  const int n1 = (p.k + 1) * p.N, KB = n1 * level / 64;
+  const int64_t G = ggsw_glwes(p, B, D), ncb = (G + 15) / 16;
+  if (ncb > 65535) return fail(ctx, FHE_E_ARG, "ggsw document batch too large: split the call");
+  HIPCHK(ctx, hipMemsetAsync(d_docs8, 0, fhe_glwe_docs_bytes(&p, B, D, level), st));
+  hipLaunchKernelGGL(k_glwe_digits, dim3((unsigned)(n1 / 64), (unsigned)ncb), dim3(256), 0, st, d_glwe, G, n1,
+                     (int)base_log, (int)level, KB, (uint32_t*)d_docs8);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+// planes -> GEMM -> slot extraction with cst on the body; the base log lives in
+// the operands (the digits in d_docs8, the rows' scale). Workspace (context
+// owned, allocated on first use): the query's Toeplitz byte planes
+// (8 ((k+1)N)^2 L bytes) | zero bodies (G) | the GEMM's G x (k+1)N result.
+static int linear_ggsw_impl(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t L, const void* d_docs8, int64_t B,
+                            int32_t D, int64_t cst, uint64_t* d_out, hipStream_t st) {
+  const fhe_params& p = ctx->p;
+  const int n1 = (p.k + 1) * p.N, K = n1 * L, KB = K / 64, NB = n1 / 16, S = ggsw_slots(p, D);
+  const int64_t G = ggsw_glwes(p, B, D);
+  if (B > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "ggsw document batch too large: split the call");
+  if (n1 % 64 || KB % KSM_RING) return fail(ctx, FHE_E_ARG, "ggsw product needs (k+1)N a multiple of 256");
+  const size_t pbytes = (size_t)K * n1 * 8, bbytes = 8 * (size_t)G;
+  const size_t need = pbytes + bbytes + 8 * (size_t)G * n1;
+  if (need > ctx->xp_ws_bytes) {
+    if (ctx->xp_ws) {
+      HIPCHK(ctx, hipDeviceSynchronize());
+      HIPCHK(ctx, hipFree(ctx->xp_ws));
+      ctx->xp_ws = nullptr;
+      ctx->xp_ws_bytes = 0;
+    }
+    HIPCHK(ctx, hipMalloc(&ctx->xp_ws, need));
+    ctx->xp_ws_bytes = need;
+  }
+  v4i* P8 = (v4i*)ctx->xp_ws;
+  u64* body = (u64*)((char*)ctx->xp_ws + pbytes);
+  u64* M = body + G;
+  // K split as the packing key switch's (partial sums by 64-bit atomics into
+  // the zeroed result; slices are whole ring rounds, so every slice holds at
+  // least KSM_RING k-blocks for the kernel's prologue)
+  const int64_t ctb = (G + KSM_CTS - 1) / KSM_CTS, ktiles = ctb * NB;
+  int Sk = (int)std::max<int64_t>(1, std::min<int64_t>(KB / KSM_RING, 512 / std::max<int64_t>(1, ktiles)));
+  const int kslice = (KB / KSM_RING + Sk - 1) / Sk * KSM_RING;
+  Sk = (KB + kslice - 1) / kslice;
+  if (ktiles * Sk > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "ggsw document batch too large: split the call");
+  hipEvent_t e1;
+  prof_begin(ctx, ctx->prof_xp, st, &e1);
+  ctx->prof_xp.kernel = "k_keyswitch_mfma<8, 1>";
+  HIPCHK(ctx, hipMemsetAsync(body, 0, bbytes + 8 * (size_t)G * n1, st));
+  hipLaunchKernelGGL(k_extprod_planes, dim3((unsigned)(KB * NB)), dim3(64), 0, st, d_ggsw, p.N, p.k, (int)L, NB, P8);
+  hipLaunchKernelGGL((k_keyswitch_mfma<8, 1>), dim3((unsigned)(ktiles * Sk)), dim3(256), 0, st, (const v4i*)d_docs8,
+                     (const v4i*)P8, body, G, n1, NB, KB, 0, Sk, kslice, M);
+  hipLaunchKernelGGL(k_extprod_extract, dim3((unsigned)B, (unsigned)((p.k * p.N + 256) / 256)), dim3(256), 0, st, M,
+                     S, (int)D, p.N, p.k, (u64)cst << (64 - p.msg_bits), d_out);
+  prof_end(ctx, ctx->prof_xp, st, e1, B);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+int fhe_linear_ggsw_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_log, int32_t level, const void* d_docs8,
+                          int64_t B, int32_t D, int64_t cst, uint64_t* d_out, void* stream) {
+  int rc = ggsw_args(ctx, B, D, base_log, level);  // argument errors first
+  if (rc) return rc;
+  if ((rc = need_device(ctx))) return rc;
+  if (B > 0 && (!d_ggsw || !d_docs8 || !d_out)) return fail(ctx, FHE_E_ARG, "null linear ggsw buffers");
+  if (B == 0) return FHE_OK;
+  return linear_ggsw_impl(ctx, d_ggsw, level, d_docs8, B, D, cst, d_out, (hipStream_t)stream);
+}
+
+int fhe_compare_ggsw_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_log, int32_t level, const void* d_docs8,
+                           int64_t B, int32_t D, int64_t cst, int64_t T, int64_t* d_acc, int64_t* d_below,
+                           void* stream) {
+  int rc = ggsw_args(ctx, B, D, base_log, level);  // argument errors first
+  if (rc) return rc;
+  if ((rc = need_secret(ctx))) return rc;
+  if (B > 0 && (!d_ggsw || !d_docs8 || !d_acc || !d_below)) return fail(ctx, FHE_E_ARG, "null compare ggsw arguments");
+  if (B == 0) return FHE_OK;
+  QueryWs w;
+  if ((rc = leveled_ws(ctx, B, 0, false, &w, nullptr))) return rc;
+  rc = linear_ggsw_impl(ctx, d_ggsw, level, d_docs8, B, D, cst - T, w.ctv, (hipStream_t)stream);
+  if (rc) return rc;
+  return post_leveled_compare(ctx, w, B, T, d_acc, d_below, stream);
+}
+
+int fhe_search_ggsw_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_log, int32_t level, const void* d_docs8,
+                          int64_t B, int32_t D, int64_t cst, int64_t T, int32_t levels_bit, uint64_t* d_glwe_acc,
+                          uint64_t* d_glwe_bit, void* stream) {
+  int rc = ggsw_args(ctx, B, D, base_log, level);  // argument errors first
+  if (rc) return rc;
+  if (levels_bit < 0 || levels_bit > 8) return fail(ctx, FHE_E_ARG, "bad search ggsw arguments (levels_bit outside [0, 8])");
+  if ((rc = need_eval_keys(ctx))) return rc;
+  if ((rc = need_pack_key(ctx))) return rc;
+  if (levels_bit > ctx->pk_level) return fail(ctx, FHE_E_ARG, "search ggsw levels_bit exceeds the packing key's levels");
+  if (B > 0 && (!d_ggsw || !d_docs8 || !d_glwe_acc || !d_glwe_bit))
+    return fail(ctx, FHE_E_ARG, "null search ggsw arguments");
+  if (B == 0) return FHE_OK;
+  QueryWs w;
+  if ((rc = leveled_ws(ctx, B, 0, true, &w, nullptr))) return rc;
+  rc = linear_ggsw_impl(ctx, d_ggsw, level, d_docs8, B, D, cst - T, w.ctv, (hipStream_t)stream);
+  if (rc) return rc;
+  return post_leveled_search(ctx, w, B, levels_bit, d_glwe_acc, d_glwe_bit, stream);
 }
 
 int fhe_threshold_batch(fhe_ctx* ctx, const uint64_t* d_ct_acc, int64_t count, int64_t T, uint64_t* d_bit,
@@ -2489,6 +2710,7 @@ static ProfAcc* prof_bucket(fhe_ctx* ctx, const char* kernel) {
   if (!strcmp(kernel, "encrypt_linear")) return &ctx->prof_enc;
   if (!strcmp(kernel, "linear_query")) return &ctx->prof_lq;
   if (!strcmp(kernel, "pack")) return &ctx->prof_pack;
+  if (!strcmp(kernel, "linear_ggsw")) return &ctx->prof_xp;
   return nullptr;
 }
 

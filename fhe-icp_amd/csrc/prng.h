@@ -43,6 +43,8 @@ enum StreamTag : uint32_t {
   TAG_MB6_NOISE = 28,
   TAG_PACK_MASK = 29,  // the LWE -> GLWE packing key (fhe_keygen_pack_key)
   TAG_PACK_NOISE = 30,
+  TAG_GGSW_MASK = 31,  // a GGSW-encrypted query (fhe_encrypt_ggsw; per-query stream key and id)
+  TAG_GGSW_NOISE = 32,
 };
 
 struct ChaKey {

@@ -108,6 +108,15 @@ SIGNATURES = [
                                 C.POINTER(C.c_int32)]),
     ("fhe_search_query_batch", C.c_int, [_CTXP, _vp, _u64, _vp, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _vp,
                                          _vp]),
+    ("fhe_ggsw_words", C.c_size_t, [_P, _i32, _i32]),
+    ("fhe_encrypt_ggsw_key", C.c_int, [_CTXP, _vp, _i32, _i32, _i32, _vp, _u64, _vp, _vp]),
+    ("fhe_encrypt_ggsw", C.c_int, [_CTXP, _vp, _i32, _i32, _i32, _u64, _u64, _vp, _vp]),
+    ("fhe_extprod_plan", C.c_int, [_P, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("fhe_glwe_docs_bytes", C.c_size_t, [_P, _i64, _i32, _i32]),
+    ("fhe_glwe_docs_pack", C.c_int, [_CTXP, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    ("fhe_linear_ggsw_batch", C.c_int, [_CTXP, _vp, _i32, _i32, _vp, _i64, _i32, _i64, _vp, _vp]),
+    ("fhe_compare_ggsw_batch", C.c_int, [_CTXP, _vp, _i32, _i32, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp]),
+    ("fhe_search_ggsw_batch", C.c_int, [_CTXP, _vp, _i32, _i32, _vp, _i64, _i32, _i64, _i64, _i32, _vp, _vp, _vp]),
     ("fhe_key_from_seed", None, [_u64, _vp]),
     ("fhe_quantize_pairs", C.c_int, [_CTXP, _vp, _i32, _vp, _i32, _i64, _i32, C.c_double, _i64, _i64, _i64, _vp, _vp]),
     ("fhe_dequantize", C.c_int, [_CTXP, _vp, _i64, C.c_double, _vp, _vp]),

@@ -512,6 +512,94 @@ class Engine:
                                                  int(levels_bit), _ptr(ga), _ptr(gb), _stream(self.device)))
         return ga, gb
 
+    # ------------- both-private search: GGSW query x GLWE documents (§8.7) --
+    def ggsw_words(self, base_log: int, level: int) -> int:
+        return self._L.fhe_ggsw_words(C.byref(self._P), int(base_log), int(level))
+
+    def doc_slots(self, D: int) -> int:
+        """Documents of D features per GLWE."""
+        if not 0 < D <= self.params.N:
+            raise ValueError(f"a document of D = {D} features does not fit one GLWE (N = {self.params.N})")
+        return self.params.N // D
+
+    def doc_glwes(self, B: int, D: int) -> int:
+        return -(-int(B) // self.doc_slots(D))
+
+    def encrypt_docs_glwe(self, dq, enc, id0: int = 0) -> torch.Tensor:
+        """Quantized documents (int64 [B, D]) -> ceil(B / S) GLWEs, S = N // D
+        documents each, feature j of document i at coefficient i D + j
+        (fhe_encrypt_packed_batch[_key] on rows of S D values). `enc` is an int
+        seed (tests) or a 256-bit stream key; GLWE g uses stream id id0 + g."""
+        m = self.to_dev(dq)
+        B, D = m.shape
+        S, G = self.doc_slots(D), self.doc_glwes(B, D)
+        rows = torch.zeros((G * S, D), dtype=torch.int64, device=self.device)
+        rows[:B] = m
+        rows = rows.reshape(G, S * D).contiguous()
+        out = torch.empty((G, (self.params.k + 1) * self.params.N), dtype=torch.int64, device=self.device)
+        if isinstance(enc, (int, np.integer)):
+            rc = self._L.fhe_encrypt_packed_batch(self._ctx, _ptr(rows), G, S * D, C.c_uint64(int(enc)),
+                                                  C.c_uint64(id0), _ptr(out), _stream(self.device))
+        else:
+            rc = self._L.fhe_encrypt_packed_batch_key(self._ctx, _ptr(rows), G, S * D, self._key(enc),
+                                                      C.c_uint64(id0), _ptr(out), _stream(self.device))
+        self._chk(rc)
+        return out
+
+    def encrypt_ggsw(self, w, base_log: int, level: int, enc, id0: int = 0) -> torch.Tensor:
+        """GGSW of Q = sum_j w[j] X^-j (fhe_encrypt_ggsw[_key]): int64
+        [(k+1) level, k+1, N] words. `enc` as in encrypt_docs_glwe."""
+        wd = self.to_dev(np.asarray(w, dtype=np.int64) if not isinstance(w, torch.Tensor) else w).reshape(-1)
+        p = self.params
+        out = torch.empty(((p.k + 1) * int(level), p.k + 1, p.N), dtype=torch.int64, device=self.device)
+        if isinstance(enc, (int, np.integer)):
+            rc = self._L.fhe_encrypt_ggsw(self._ctx, _ptr(wd), wd.numel(), int(base_log), int(level),
+                                          C.c_uint64(int(enc)), C.c_uint64(id0), _ptr(out), _stream(self.device))
+        else:
+            rc = self._L.fhe_encrypt_ggsw_key(self._ctx, _ptr(wd), wd.numel(), int(base_log), int(level),
+                                              self._key(enc), C.c_uint64(id0), _ptr(out), _stream(self.device))
+        self._chk(rc)
+        return out
+
+    def pack_docs_glwe(self, glwe: torch.Tensor, B: int, D: int, base_log: int, level: int) -> torch.Tensor:
+        """Document GLWEs -> the i8 digit operand of linear_ggsw / compare_ggsw
+        / search_ggsw (fhe_glwe_docs_pack), once per resident corpus."""
+        n = self._L.fhe_glwe_docs_bytes(C.byref(self._P), int(B), int(D), int(level))
+        docs8 = torch.empty(n, dtype=torch.uint8, device=self.device)
+        self._chk(self._L.fhe_glwe_docs_pack(self._ctx, _ptr(glwe), int(B), int(D), int(base_log), int(level),
+                                             _ptr(docs8), _stream(self.device)))
+        return docs8
+
+    def linear_ggsw(self, ggsw: torch.Tensor, base_log: int, level: int, docs8: torch.Tensor, B: int, D: int,
+                    cst: int) -> torch.Tensor:
+        """The exact external product and slot extraction (fhe_linear_ggsw_batch): B x (kN+1)."""
+        out = self.empty_big(B)
+        self._chk(self._L.fhe_linear_ggsw_batch(self._ctx, _ptr(ggsw), int(base_log), int(level), _ptr(docs8), int(B),
+                                                int(D), int(cst), _ptr(out), _stream(self.device)))
+        return out
+
+    def compare_ggsw(self, ggsw: torch.Tensor, base_log: int, level: int, docs8: torch.Tensor, B: int, D: int,
+                     cst: int, T: int):
+        """fhe_compare_ggsw_batch: (acc int64[B], below int64[B])."""
+        acc = torch.empty(B, dtype=torch.int64, device=self.device)
+        below = torch.empty(B, dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_compare_ggsw_batch(self._ctx, _ptr(ggsw), int(base_log), int(level), _ptr(docs8), int(B),
+                                                 int(D), int(cst), int(T), _ptr(acc), _ptr(below),
+                                                 _stream(self.device)))
+        return acc, below
+
+    def search_ggsw(self, ggsw: torch.Tensor, base_log: int, level: int, docs8: torch.Tensor, B: int, D: int,
+                    cst: int, T: int, levels_bit: int = 0):
+        """fhe_search_ggsw_batch: the untrusted host's entry; (glwe_acc,
+        glwe_bit), each ceil(B / N) x (k+1)N words."""
+        shape = (self.glwe_count(B), (self.params.k + 1) * self.params.N)
+        ga = torch.empty(shape, dtype=torch.int64, device=self.device)
+        gb = torch.empty(shape, dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_search_ggsw_batch(self._ctx, _ptr(ggsw), int(base_log), int(level), _ptr(docs8), int(B),
+                                                int(D), int(cst), int(T), int(levels_bit), _ptr(ga), _ptr(gb),
+                                                _stream(self.device)))
+        return ga, gb
+
     def topk(self, acc: torch.Tensor, below: torch.Tensor | None, k: int, base_idx: int = 0):
         oa = torch.empty(k, dtype=torch.int64, device=self.device)
         oi = torch.empty(k, dtype=torch.int64, device=self.device)

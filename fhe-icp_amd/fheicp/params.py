@@ -493,6 +493,32 @@ def pack_plan(p: SchemeParams, count: int, in_var: float = 0.0):
     return b, L, lb
 
 
+def extprod_var(p: SchemeParams, w_norm2: float, base_log: int, level: int) -> float:
+    """Variance of an extracted phase of the GGSW x GLWE product, in units of
+    the integer words (fheicp.hip extprod_var): the rows'
+    noise through the message and through the (k+1) N level digits, plus the
+    rounding of the document's words to base_log * level bits times the query
+    polynomial of squared norm w_norm2."""
+    B = 2.0 ** base_log
+    tv = _tuniform_var(p.glwe_noise_bits)
+    return (w_norm2 * tv + float(p.k + 1) * level * p.N * ((B * B + 2) / 12.0) * tv
+            + w_norm2 * (1.0 + float(p.k) * p.N / 2.0) * 2.0 ** (2 * (64 - base_log * level)) / 12.0)
+
+
+def extprod_plan(p: SchemeParams, w_norm2: float):
+    """(base_log, level) of the both-private query's GGSW (fhe_extprod_plan):
+    fewest levels, then the largest base_log <= 7, that keeps 2^(63 - msg_bits)
+    at 9.2 sigma for a query of squared norm w_norm2 (plan for the worst case
+    4^(n_e - 1) sum q_w^2); None when no gadget does."""
+    if not w_norm2 >= 0:
+        raise ValueError("extprod_plan needs w_norm2 >= 0")
+    for L in range(1, 9):
+        for b in range(7, 0, -1):
+            if pack_gadget_ok(b, L) and 2.0 ** (63 - p.msg_bits) / math.sqrt(extprod_var(p, w_norm2, b, L)) >= 9.2:
+                return b, L
+    return None
+
+
 def _variances(p: SchemeParams, group: int = 1):
     """(bootstrap, key switch, modulus switch) output variances, relative to
     the 2^64 torus, for the main gadget of p on the classic

@@ -1,0 +1,191 @@
+"""Both-private search: a GGSW-encrypted query against GLWE-encrypted documents.
+
+The fourth deployment shape: the host that stores and scores
+sees neither the documents nor the query.
+
+  * the client quantizes documents with the corpus quantizer,
+    ``dq = E.quant(d)`` (fheicp.corpus.CorpusQuant), and encrypts S = N // D
+    of them per GLWE at the worst-case width P0, feature j of document i at
+    coefficient i D + j (fhe_encrypt_packed_batch);
+  * it quantizes a query the same way, folds it into the model's weights,
+    ``W_j = q_w[j] * qq_j``, and sends one GGSW of ``Q = sum_j W_j X^-j``
+    (fhe_encrypt_ggsw) with the gadget of params.extprod_plan;
+  * the server decomposes the documents once (fhe_glwe_docs_pack) and
+    computes ``acc_b = sum_j W_j * dq[b, j] + q_b'`` as one exact external
+    product modulo 2^64 on the i8 matrix cores, then the sign extraction of
+    ``acc - T`` and the packed replies of the two-party private query
+    (fhe_search_ggsw_batch); it holds evaluation keys, the CorpusQuant and P0.
+
+The expected values are the bilinear restatement of fheicp.corpus
+(oracle/quant_ref.py, ``corpus_*``); reply format and packing plan are
+fheicp.query's.
+
+Query payload (uint64 vector):
+    [QUERY_MAGIC, 1, D, P0, base_log | level << 32, N | k << 32,
+     GGSW words [c][l][component][coef]]
+Document block (uint64 vector):
+    [DOCS_MAGIC, 1, B, D, P0, N | k << 32, ceil(B / (N // D)) GLWEs of (k+1)N words]
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+from .corpus import EncryptedCorpus
+from .query import QueryClient, QueryServer, pack_reply
+
+QUERY_MAGIC = int.from_bytes(b"FHEICPGQ", "little")
+DOCS_MAGIC = int.from_bytes(b"FHEICPGD", "little")
+HEADER_WORDS = 6
+
+
+def pack_ggsw_query(ggsw, D: int, P0: int, base_log: int, level: int, N: int, k: int) -> np.ndarray:
+    g = np.asarray(ggsw, dtype=np.uint64).reshape(-1)
+    head = np.array([QUERY_MAGIC, 1, D, P0, int(base_log) | (int(level) << 32), int(N) | (int(k) << 32)], np.uint64)
+    return np.concatenate([head, g])
+
+
+def unpack_ggsw_query(arr) -> dict:
+    a = np.asarray(arr)
+    if a.dtype != np.uint64 or a.ndim != 1 or a.size < HEADER_WORDS or int(a[0]) != QUERY_MAGIC:
+        raise ValueError("not an fheicp GGSW query payload")
+    if int(a[1]) != 1:
+        raise ValueError(f"unsupported GGSW query payload version {int(a[1])}")
+    base_log, level = int(a[4]) & 0xFFFFFFFF, int(a[4]) >> 32
+    N, k = int(a[5]) & 0xFFFFFFFF, int(a[5]) >> 32
+    if a.size != HEADER_WORDS + (k + 1) * level * (k + 1) * N:
+        raise ValueError("GGSW query payload size does not match its gadget and parameters")
+    return {"D": int(a[2]), "P0": int(a[3]), "base_log": base_log, "level": level, "N": N, "k": k,
+            "ggsw": a[HEADER_WORDS:].copy()}
+
+
+def pack_doc_block(glwe, B: int, D: int, P0: int, N: int, k: int) -> np.ndarray:
+    g = np.asarray(glwe, dtype=np.uint64).reshape(-1)
+    head = np.array([DOCS_MAGIC, 1, B, D, P0, int(N) | (int(k) << 32)], np.uint64)
+    return np.concatenate([head, g])
+
+
+def unpack_doc_block(arr) -> dict:
+    a = np.asarray(arr)
+    if a.dtype != np.uint64 or a.ndim != 1 or a.size < HEADER_WORDS or int(a[0]) != DOCS_MAGIC:
+        raise ValueError("not an fheicp GLWE document block")
+    if int(a[1]) != 1:
+        raise ValueError(f"unsupported document block version {int(a[1])}")
+    B, D = int(a[2]), int(a[3])
+    N, k = int(a[5]) & 0xFFFFFFFF, int(a[5]) >> 32
+    if not 0 < D <= N:
+        raise ValueError(f"document block of D = {D} features does not fit one GLWE (N = {N})")
+    if a.size != HEADER_WORDS + -(-B // (N // D)) * (k + 1) * N:
+        raise ValueError("document block size does not match its document count")
+    return {"B": B, "D": D, "P0": int(a[4]), "N": N, "k": k, "glwe": a[HEADER_WORDS:].copy()}
+
+
+def worst_norm2(cq) -> float:
+    """The squared query norm the gadget is planned for, over every query
+    (|qq_j| <= 2^(n_e - 1)). The model of params.extprod_var takes the
+    rounding errors at the D coefficients a slot sums as independent; under a
+    binary key neighbouring coefficients' errors correlate at about 1/2
+    (DESIGN.md §8.7), which turns ||W||^2 into (||W||^2 + (sum_j W_j)^2) / 2
+    in the dominant term. The plan gets the worst case of that,
+    4^(n_e - 1) (sum_j q_w[j]^2 + (sum_j |q_w[j]|)^2) / 2."""
+    qw = np.abs(np.asarray(cq.model.q_w, dtype=np.float64))
+    return float(4.0 ** (cq.n_e - 1) * 0.5 * (np.sum(qw * qw) + np.sum(qw) ** 2))
+
+
+def plan_gadget(scheme, cq):
+    """(base_log, level) of this model's GGSW queries at scheme.msg_bits, or a
+    ValueError that says why there is none."""
+    from .params import extprod_plan
+    g = extprod_plan(scheme, worst_norm2(cq))
+    if g is None:
+        raise ValueError(f"both-private search has no GGSW gadget at P0 = {scheme.msg_bits}: the int8 digits stop at "
+                         "base_log * level = 49 bits, whose rounding exceeds the 9.2-sigma margin of this width "
+                         "(DESIGN.md §8.7); use fewer embedding bits or dimensions")
+    return g
+
+
+class PrivateClient(QueryClient):
+    """The key holder: encrypts document blocks and queries, hands out
+    evaluation keys, decrypts replies (QueryClient's). Owns the secret context
+    of a compiled EncryptedCorpus."""
+
+    def __init__(self, corpus: EncryptedCorpus, count: int = 1024, pack_seed=None, enc_seed: int | None = None):
+        """enc_seed: the 64-bit test form of the session's encryption key."""
+        from .params import extprod_var
+        corpus._need()
+        scheme = corpus.scheme.with_msg_bits(corpus.P0)
+        self.base_log, self.level = self.gadget = plan_gadget(scheme, corpus.cq)
+        # the packing plan sees the leveled step's worst-case variance
+        in_var = extprod_var(scheme, worst_norm2(corpus.cq), *self.gadget) / 2.0 ** 128
+        super().__init__(corpus, count, in_var, pack_seed)
+        self.pack_base_log, self.pack_level = corpus.engine.pack_gadget
+        self.base_log, self.level = self.gadget
+        self._enc_key = (np.frombuffer(os.urandom(32), np.uint32).copy() if enc_seed is None
+                         else corpus.engine.key_from_seed(enc_seed))
+
+    def _ids(self, id0):
+        return int.from_bytes(os.urandom(8), "little") if id0 is None else int(id0)
+
+    def encrypt_docs(self, docs, id0: int | None = None) -> np.ndarray:
+        """docs f32/f64 [B, D] -> one document block (GLWE g under stream id id0 + g)."""
+        import torch
+        eng = self.corpus.engine
+        docs = np.ascontiguousarray(docs)
+        B, D = docs.shape
+        eng.set_msg_bits(self.P0)
+        dq = eng.quantize(torch.from_numpy(docs).to(eng.device), self.cq.s_e, 0, self.cq.qmin, self.cq.qmax)
+        glwe = eng.encrypt_docs_glwe(dq, self._enc_key, self._ids(id0))
+        return pack_doc_block(glwe.cpu().numpy().view(np.uint64), B, D, self.P0, eng.params.N, eng.params.k)
+
+    def decrypt_docs(self, block) -> np.ndarray:
+        """The quantized documents of a block (the key holder's view; tests)."""
+        eng = self.corpus.engine
+        bl = unpack_doc_block(block)
+        eng.set_msg_bits(self.P0)
+        S = bl["N"] // bl["D"]
+        G = -(-bl["B"] // S)
+        v = eng.decrypt_packed(eng.to_dev(bl["glwe"]), G * bl["N"], 0).cpu().numpy().reshape(G, bl["N"])
+        return v[:, :S * bl["D"]].reshape(G * S, bl["D"])[:bl["B"]]
+
+    def encrypt_query(self, q, id0: int | None = None) -> np.ndarray:
+        """A reduced query vector -> the GGSW payload sent to the server."""
+        eng = self.corpus.engine
+        W = self.cq.weights(self.cq.quant(np.asarray(q).reshape(-1)))
+        eng.set_msg_bits(self.P0)
+        g = eng.encrypt_ggsw(W, self.base_log, self.level, self._enc_key, self._ids(id0))
+        return pack_ggsw_query(g.cpu().numpy().view(np.uint64), len(W), self.P0, self.base_log, self.level,
+                               eng.params.N, eng.params.k)
+
+
+class PrivateServer(QueryServer):
+    """The untrusted host: evaluation keys, the CorpusQuant and P0 only."""
+
+    def __init__(self, eval_keys: dict, cq, P0: int, device: int = 0, scheme=None):
+        super().__init__(eval_keys, cq, P0, device, scheme)
+        self.base_log, self.level = plan_gadget(self.scheme, cq)
+
+    def _check(self, pl: dict, what: str) -> None:
+        if pl["P0"] != self.P0 or pl["N"] != self.scheme.N or pl["k"] != self.scheme.k:
+            raise ValueError(f"{what} was encrypted under different parameters")
+        if pl["D"] != len(self.cq.model.q_w):
+            raise ValueError(f"{what} holds {pl['D']} features, the model {len(self.cq.model.q_w)}")
+
+    def pack_docs(self, block):
+        """A document block -> (the device-resident digit operand, B)."""
+        bl = unpack_doc_block(block)
+        self._check(bl, "document block")
+        eng = self.engine
+        return eng.pack_docs_glwe(eng.to_dev(bl["glwe"]), bl["B"], bl["D"], self.base_log, self.level), bl["B"]
+
+    def search(self, payload, docs8, B: int, min_similarity: float | None) -> np.ndarray:
+        """One GGSW query against B packed encrypted documents -> the reply."""
+        eng = self.engine
+        pl = unpack_ggsw_query(payload)
+        self._check(pl, "query")
+        if (pl["base_log"], pl["level"]) != (self.base_log, self.level):
+            raise ValueError("query gadget differs from the one the documents were packed for")
+        _, cst, T = self.plan(min_similarity)
+        ga, gb = eng.search_ggsw(eng.to_dev(pl["ggsw"]), self.base_log, self.level, docs8, int(B), pl["D"], cst, T,
+                                 self.bit_levels)
+        return pack_reply(ga.cpu().numpy().view(np.uint64), gb.cpu().numpy().view(np.uint64), B, self.P0, T)

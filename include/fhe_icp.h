@@ -452,6 +452,66 @@ int fhe_pack_plan(const fhe_params* params, int64_t count, double in_var, int32_
 int fhe_search_query_batch(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0, const uint32_t h_mask_key[8],
                            const void* d_docs8, int64_t B, int32_t D, const int64_t* d_w, int64_t cst, int64_t T,
                            int32_t levels_bit, uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream);
+/* ---- both-private search: GGSW query x GLWE documents -----
+ * The fourth deployment shape: the host sees neither the documents nor the
+ * query. Everything is exact arithmetic modulo 2^64 on the i8 matrix cores.
+ * Documents: S = floor(N / D) documents share one GLWE under the big key,
+ * feature j of document i at coefficient i D + j, encoded at Delta =
+ * 2^(64 - msg_bits): fhe_encrypt_packed_batch on rows of S D values (unused
+ * coefficients 0), G = ceil(B / S) GLWEs per B documents. D <= N.
+ * Query: the client forms W_j = q_w[j] qq_j (plain integers) and sends one
+ * GGSW of Q = sum_j W_j X^-j under the big key with gadget (base_log b,
+ * level L; the packing gadget's bounds): row (c, l), c <= k, l = 1..L, is a
+ * GLWE encryption of Q 2^(64 - b l) for c = k and of -S_c Q 2^(64 - b l) for
+ * c < k, noise TUniform(glwe_noise_bits), stream tags 31/32 (row r = c L +
+ * (l - 1): masks from stream id0 + r k + component, noise from id0 + r; a
+ * GGSW consumes ids id0 .. id0 + (k+1) L k - 1). Layout
+ * [c][l][component 0..k][coef], fhe_ggsw_words words (0 for a gadget out of
+ * range). The encrypting entries need the secret key: FHE_E_DEVICE on a
+ * host-only context, FHE_E_STATE on an evaluation-only one. `*_key` / seed
+ * forms as for the other encrypting entry points. d_w: D int64 (device). */
+size_t fhe_ggsw_words(const fhe_params* params, int32_t base_log, int32_t level);
+int fhe_encrypt_ggsw_key(fhe_ctx* ctx, const int64_t* d_w, int32_t D, int32_t base_log, int32_t level,
+                         const uint32_t h_key[8], uint64_t id0, uint64_t* d_ggsw, void* stream);
+int fhe_encrypt_ggsw(fhe_ctx* ctx, const int64_t* d_w, int32_t D, int32_t base_log, int32_t level, uint64_t seed,
+                     uint64_t id0, uint64_t* d_ggsw, void* stream);
+/* The cheapest gadget (fewest levels, then the largest base_log <= 7; level
+ * <= 8, level (base_log + 1) <= 62) with 2^(63 - msg_bits) / sqrt(var) >= 9.2,
+ *   var = w_norm2 tv + (k+1) L N ((B^2 + 2) / 12) tv
+ *         + w_norm2 (1 + kN / 2) 2^(2 (64 - b L)) / 12,
+ * tv = tuniform_var(glwe_noise_bits), B = 2^b, w_norm2 the worst-case
+ * sum_j W_j^2 (4^(n_e - 1) sum_j q_w[j]^2). FHE_E_STATE (outputs 0) when no
+ * gadget reaches the bar. Host only; fheicp.params.extprod_plan is the same. */
+int fhe_extprod_plan(const fhe_params* params, double w_norm2, int32_t* base_log, int32_t* level);
+/* The documents' digits as the GEMM's left operand, once per resident corpus:
+ * d_glwe holds the G = ceil(B / floor(N / D)) document GLWEs, d_docs8 receives
+ * fhe_glwe_docs_bytes bytes (G padded to a multiple of 16, one byte per word
+ * and level; 0 for bad arguments). Needs no keys. */
+size_t fhe_glwe_docs_bytes(const fhe_params* params, int64_t B, int32_t D, int32_t level);
+int fhe_glwe_docs_pack(fhe_ctx* ctx, const uint64_t* d_glwe, int64_t B, int32_t D, int32_t base_log, int32_t level,
+                       void* d_docs8, void* stream);
+/* The leveled step: with d_{c,.} the key switch's balanced digits with tie
+ * coins of component c (masks and body alike) of a document GLWE,
+ *   out = sum_{c <= k} sum_{l <= L} d_{c,l}(X) Row(c, l)   (negacyclic, mod 2^64),
+ * coefficient i D of whose phase is sum_j W_j dq[i, j] Delta plus noise; that
+ * coefficient is sample-extracted and trivial(cst Delta) added: d_out is
+ * B x (kN+1), what fhe_sign_batch and fhe_pack_batch take. Bit-exact. Needs
+ * no keys. The query's negacyclic Toeplitz byte planes (8 ((k+1)N)^2 L bytes:
+ * 528 MB at N = 1024, k = 2, L = 7) live in context-owned workspace allocated
+ * on first use. (base_log, level) are the query's and the packed digits'. */
+int fhe_linear_ggsw_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_log, int32_t level, const void* d_docs8,
+                          int64_t B, int32_t D, int64_t cst, uint64_t* d_out, void* stream);
+/* fhe_compare_query_batch with both sides encrypted (single party: decrypts):
+ * leveled step with cst - T -> decrypt the accumulator -> sign extraction ->
+ * decrypt the threshold bit. Same outputs as fhe_compare_query_batch. */
+int fhe_compare_ggsw_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_log, int32_t level, const void* d_docs8,
+                           int64_t B, int32_t D, int64_t cst, int64_t T, int64_t* d_acc, int64_t* d_below,
+                           void* stream);
+/* The untrusted host's entry: fhe_search_query_batch with both sides
+ * encrypted. Evaluation keys and the packing key only; replies as there. */
+int fhe_search_ggsw_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_log, int32_t level, const void* d_docs8,
+                          int64_t B, int32_t D, int64_t cst, int64_t T, int32_t levels_bit, uint64_t* d_glwe_acc,
+                          uint64_t* d_glwe_bit, void* stream);
 /* The 64-bit-seed -> 256-bit ChaCha key expansion used by the seed forms
  * (fhe_keygen, fhe_encrypt_batch, ...; splitmix64): tests and
  * benches only. Host only. */
@@ -503,8 +563,9 @@ int fhe_stream_sync(fhe_ctx* ctx, void* stream);
  * "blind_rotate_mid", "blind_rotate_mid2", "blind_rotate_mid0", "keyswitch", "encrypt_linear"
  * (the fused client encryption + leveled dot), "linear_query" (the
  * private-query leveled step: query planes + GEMM, one bracket around both)
- * or "pack" (the packing key switch: digits + GEMM + rotation, one bracket),
- * then resets what it read. */
+ * "pack" (the packing key switch: digits + GEMM + rotation, one bracket) or
+ * "linear_ggsw" (the both-private leveled step: Toeplitz planes + GEMM +
+ * slot extraction, one bracket), then resets what it read. */
 int fhe_profile_enable(fhe_ctx* ctx, int enable);
 int fhe_profile_read(fhe_ctx* ctx, const char* kernel, double* total_ms, int64_t* launches, int64_t* items);
 /* The kernel last launched for that bucket, as rocprofv3 names it (e.g.

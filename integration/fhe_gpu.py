@@ -69,6 +69,18 @@ _PROTOS = {
     "fhe_pack_batch": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
     "fhe_decrypt_packed_batch": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
     "fhe_search_query_batch": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    # both sides encrypted: GGSW query x GLWE documents
+    "fhe_encrypt_packed_batch_key": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _u64, _vp, _vp]),
+    "fhe_encrypt_packed_batch": (C.c_int, [_vp, _vp, _i64, _i32, _u64, _u64, _vp, _vp]),
+    "fhe_ggsw_words": (C.c_size_t, [C.POINTER(fhe_params), _i32, _i32]),
+    "fhe_encrypt_ggsw_key": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _u64, _vp, _vp]),
+    "fhe_encrypt_ggsw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _u64, _u64, _vp, _vp]),
+    "fhe_extprod_plan": (C.c_int, [C.POINTER(fhe_params), C.c_double, C.POINTER(_i32), C.POINTER(_i32)]),
+    "fhe_glwe_docs_bytes": (C.c_size_t, [C.POINTER(fhe_params), _i64, _i32, _i32]),
+    "fhe_glwe_docs_pack": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "fhe_linear_ggsw_batch": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _i32, _i64, _vp, _vp]),
+    "fhe_compare_ggsw_batch": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp]),
+    "fhe_search_ggsw_batch": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _i32, _i64, _i64, _i32, _vp, _vp, _vp]),
 }
 
 
@@ -256,6 +268,97 @@ class GpuCompare:
         try:
             self._ok(self.L.fhe_decrypt_packed_batch(self.ctx, bufs[0], count, mode, bufs[1], None))
             return self._to_host(bufs[1], count)
+        finally:
+            for d in bufs:
+                self.L.fhe_dev_free(self.ctx, d)
+
+    # ---- both sides encrypted: GGSW query x GLWE documents -------------------
+    def ggsw_plan(self, w_norm2: float):
+        """(base_log, level) of the query's GGSW for the worst-case squared
+        norm of W = q_w * qq (fhe_extprod_plan); raises when no gadget keeps
+        the margin at this msg_bits."""
+        b, lv = _i32(), _i32()
+        self._ok(self.L.fhe_extprod_plan(C.byref(self.P), float(w_norm2), C.byref(b), C.byref(lv)))
+        return b.value, lv.value
+
+    def encrypt_docs_glwe(self, dq: np.ndarray) -> np.ndarray:
+        """Key holder: quantized documents (int64 [B, D], D <= N) -> the
+        ceil(B / (N // D)) document GLWEs (uint64 host array)."""
+        dq = np.asarray(dq, np.int64)
+        B, D = dq.shape
+        S = self.P.N // D
+        G = -(-B // S)
+        rows = np.zeros((G * S, D), np.int64)
+        rows[:B] = dq
+        words = G * (self.P.k + 1) * self.P.N
+        bufs = [self._to_dev(rows), self._alloc(8 * words)]
+        try:
+            id0 = self._take_ids(G)
+            if self.enc_key is not None:
+                rc = self.L.fhe_encrypt_packed_batch_key(self.ctx, bufs[0], G, S * D, self.enc_key, id0, bufs[1], None)
+            else:
+                rc = self.L.fhe_encrypt_packed_batch(self.ctx, bufs[0], G, S * D, self.enc_seed, id0, bufs[1], None)
+            self._ok(rc)
+            return self._to_host(bufs[1], words).view(np.uint64)
+        finally:
+            for d in bufs:
+                self.L.fhe_dev_free(self.ctx, d)
+
+    def encrypt_ggsw(self, W: np.ndarray, base_log: int, level: int) -> np.ndarray:
+        """Key holder: W_j = q_w[j] * qq_j (int64 [D]) -> the query's GGSW
+        (uint64 host array of fhe_ggsw_words words)."""
+        W = np.asarray(W, np.int64).reshape(-1)
+        words = self.L.fhe_ggsw_words(C.byref(self.P), base_log, level)
+        bufs = [self._to_dev(W), self._alloc(8 * words)]
+        try:
+            id0 = self._take_ids((self.P.k + 1) * level * self.P.k)
+            if self.enc_key is not None:
+                rc = self.L.fhe_encrypt_ggsw_key(self.ctx, bufs[0], W.size, base_log, level, self.enc_key, id0,
+                                                 bufs[1], None)
+            else:
+                rc = self.L.fhe_encrypt_ggsw(self.ctx, bufs[0], W.size, base_log, level, self.enc_seed, id0, bufs[1],
+                                             None)
+            self._ok(rc)
+            return self._to_host(bufs[1], words).view(np.uint64)
+        finally:
+            for d in bufs:
+                self.L.fhe_dev_free(self.ctx, d)
+
+    def pack_docs_glwe(self, glwe: np.ndarray, B: int, D: int, base_log: int, level: int):
+        """Server: document GLWEs -> the device-resident digit operand
+        (handle, B, D); free it with free_docs."""
+        src = self._to_dev(np.asarray(glwe, np.uint64))
+        try:
+            docs8 = self._alloc(self.L.fhe_glwe_docs_bytes(C.byref(self.P), B, D, level))
+            self._ok(self.L.fhe_glwe_docs_pack(self.ctx, src, B, D, base_log, level, docs8, None))
+            self._to_host(docs8, 1)  # fhe_memcpy_d2h synchronises: the pack is done before src is freed
+            return docs8, B, D
+        finally:
+            self.L.fhe_dev_free(self.ctx, src)
+
+    def compare_ggsw(self, ggsw: np.ndarray, base_log: int, level: int, docs, cst: int, T: int):
+        """Single party: (acc, below) of the GGSW query against packed
+        encrypted documents (fhe_compare_ggsw_batch)."""
+        docs8, B, D = docs
+        bufs = [self._to_dev(np.asarray(ggsw, np.uint64)), self._alloc(8 * B), self._alloc(8 * B)]
+        try:
+            self._ok(self.L.fhe_compare_ggsw_batch(self.ctx, bufs[0], base_log, level, docs8, B, D, int(cst), int(T),
+                                                   bufs[1], bufs[2], None))
+            return self._to_host(bufs[1], B), self._to_host(bufs[2], B)
+        finally:
+            for d in bufs:
+                self.L.fhe_dev_free(self.ctx, d)
+
+    def search_ggsw(self, ggsw: np.ndarray, base_log: int, level: int, docs, cst: int, T: int, levels_bit: int = 0):
+        """Untrusted host: (glwe_acc, glwe_bit) as search_query's
+        (fhe_search_ggsw_batch; evaluation keys and the packing key only)."""
+        docs8, B, D = docs
+        words = -(-B // self.P.N) * (self.P.k + 1) * self.P.N
+        bufs = [self._to_dev(np.asarray(ggsw, np.uint64)), self._alloc(8 * words), self._alloc(8 * words)]
+        try:
+            self._ok(self.L.fhe_search_ggsw_batch(self.ctx, bufs[0], base_log, level, docs8, B, D, int(cst), int(T),
+                                                  int(levels_bit), bufs[1], bufs[2], None))
+            return self._to_host(bufs[1], words).view(np.uint64), self._to_host(bufs[2], words).view(np.uint64)
         finally:
             for d in bufs:
                 self.L.fhe_dev_free(self.ctx, d)

@@ -23,6 +23,13 @@ with fhe_compare_query_batch on the key holder's context; the "pack" profile
 bucket per search, the reply's size, and the parity of the client's decrypted
 (acc, below) with the single-party result.
 
+With --both-private (docs/AB_LOG_r09.md) it measures the
+both-private compare: fhe_compare_ggsw_batch (a GGSW query against packed GLWE
+documents; payload parse and upload, Toeplitz planes, GEMM, slot extraction,
+sign extraction, both decryptions) interleaved step by step, in alternating
+order, with fhe_compare_query_batch on the same context, the "linear_ggsw"
+profile bucket per compare, and the parity of the two results.
+
 The floor of the leveled step is its output, B * (kN + 1) * 8 bytes, over the
 6.29 TB/s a float4 copy reaches on the MI355X; `floor_fraction` is that floor
 over the measured time. Prints one JSON line and writes it to --out.
@@ -186,6 +193,76 @@ def two_party(cq, oq, B: int, D: int, n_bits: int, steps: int, warmup: int) -> d
     return out
 
 
+def both_private(cq, oq, B: int, D: int, n_bits: int, steps: int, warmup: int) -> dict:
+    """fhe_compare_ggsw_batch against fhe_compare_query_batch on one context,
+    interleaved in alternating order."""
+    import numpy as np
+    import torch
+    from oracle import quant_ref as Q
+    from fheicp.corpus import EncryptedCorpus
+    from fheicp.private import PrivateClient, unpack_doc_block, unpack_ggsw_query
+    from fheicp.query import EncryptedQuerySearch
+    c = EncryptedCorpus(cq).compile(key_seed=5, device=0, noise_seed=6)
+    eng = c.engine
+    single = EncryptedQuerySearch(c)
+    client = PrivateClient(c, count=B, pack_seed=17, enc_seed=18)
+    beta, L = client.gadget
+    q, docs = Q.make_corpus(D, B, seed=21)
+    docs8_q = single.pack_docs(docs)
+    docs8_g = eng.pack_docs_glwe(eng.to_dev(unpack_doc_block(client.encrypt_docs(docs))["glwe"]), B, D, beta, L)
+    payload_q, payload_g = single.encrypt_query(q), client.encrypt_query(q)
+    _, cst, T = single.plan(0.5)
+    eng.set_msg_bits(c.P0)
+    eng.profile(True)
+    t_query, t_ggsw, t_lin = [], [], []
+
+    def run_query():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = single.compare(payload_q, docs8_q, B, 0.5)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    def run_ggsw():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pl = unpack_ggsw_query(payload_g)
+        out = eng.compare_ggsw(eng.to_dev(pl["ggsw"]), beta, L, docs8_g, B, D, cst, T)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    for i in range(warmup + steps):
+        if i % 2:
+            (tq, res_q), (tg, res_g) = run_query(), run_ggsw()
+        else:
+            (tg, res_g), (tq, res_q) = run_ggsw(), run_query()
+        lin = eng.profile_read("linear_ggsw")
+        assert lin["launches"] == 1
+        eng.profile_read("linear_query")
+        if i >= warmup:
+            t_query.append(tq)
+            t_ggsw.append(tg)
+            t_lin.append(lin["total_ms"])
+    eng.profile(False)
+    ref = Q.corpus_accumulate(oq, cq.s_e, n_bits, q, docs)
+    scores = np.float64(Q.corpus_out_scale(oq, cq.s_e)) * ref.astype(np.float64)
+    parity = bool(torch.equal(res_g[0], res_q[0]) and torch.equal(res_g[1], res_q[1]))
+    exact = bool(np.array_equal(res_g[0].cpu().numpy(), ref) and
+                 np.array_equal(res_g[1].cpu().numpy(), (scores < 0.5).astype(np.int64)))
+    q_ms, g_ms = statistics.median(t_query) * 1e3, statistics.median(t_ggsw) * 1e3
+    p = c.scheme
+    n1 = (p.k + 1) * p.N
+    out = {"compare_ggsw_ms": g_ms, "compare_ggsw_min_ms": min(t_ggsw) * 1e3, "compare_query_ms": q_ms,
+           "compare_query_min_ms": min(t_query) * 1e3, "ratio_ggsw_over_query": g_ms / q_ms,
+           "meets_bar": g_ms <= 1.10 * q_ms, "linear_ggsw_ms": statistics.median(t_lin),
+           "linear_ggsw_min_ms": min(t_lin), "kernel": eng.kernel_name("linear_ggsw"), "ggsw_gadget": [beta, L],
+           "ggsw_bytes": int(payload_g.nbytes), "plane_bytes": n1 * L * n1 * 8,
+           "doc_glwes": eng.doc_glwes(B, D), "parity_with_compare_query": parity, "bit_exact": exact,
+           "steps": steps, "warmup": warmup}
+    c.engine.close()
+    return out
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batch", type=int, default=1024)
@@ -198,6 +275,9 @@ def main() -> int:
                     help="the leveled step only (kernel traces: no keygen, no sign extraction)")
     ap.add_argument("--two-party", action="store_true",
                     help="the two-party search (evaluation-only server, packed reply) against the single-party "
+                         "compare, --launches interleaved steps after --warmup")
+    ap.add_argument("--both-private", action="store_true",
+                    help="the both-private compare (GGSW query, GLWE documents) against the private-query "
                          "compare, --launches interleaved steps after --warmup")
     ap.add_argument("--out", default=str(REPO / "profiles" / "query_bench.json"))
     a = ap.parse_args()
@@ -214,6 +294,19 @@ def main() -> int:
         for nb in a.n_bits:
             cq, oq = corpus_quant(D, nb)
             P0 = cq.worst_msg_bits()
+            if a.both_private:
+                from fheicp.private import plan_gadget
+                row = {"B": a.batch, "D": D, "n_bits": nb, "P0": P0, "both_private": None}
+                if P0 <= MAX_BITS:
+                    try:
+                        plan_gadget(params_for_bits(P0), cq)
+                    except ValueError as e:          # no gadget at this width: recorded, not measured
+                        row["no_gadget"] = str(e)
+                    else:
+                        row["both_private"] = both_private(cq, oq, a.batch, D, nb, a.launches, a.warmup)
+                row["meets_bar"] = row["both_private"] is None or row["both_private"]["meets_bar"]
+                shapes.append(row)
+                continue
             if a.two_party:
                 row = {"B": a.batch, "D": D, "n_bits": nb, "P0": P0,
                        "two_party": two_party(cq, oq, a.batch, D, nb, a.launches, a.warmup) if P0 <= MAX_BITS else None}
