@@ -147,6 +147,8 @@ class GpuBert:
         if B and int(mask[:, 0].min()) != 1:
             raise ValueError("every sequence needs its first token ([CLS]) unmasked")
         tt = self._dev_i32(token_type_ids) if token_type_ids is not None else None
+        if tt is not None and tt.shape != ids.shape:
+            raise ValueError("token_type_ids must be [B, S] like input_ids")
         if tt is not None and B and (int(tt.min()) < 0 or int(tt.max()) >= self.cfg["type_vocab_size"]):
             raise ValueError("token type id out of range")
         H = self.hidden_size
