@@ -508,6 +508,37 @@ class BatchProcessor:
         out = [(ids[i], s) for i, s in hits]
         return out[:top_k]
 
+    def search_similar_many(self, texts: List[str], top_k: int = 5,
+                            min_similarity: float = 0.5) -> List[List[Tuple[str, float]]]:
+        """search_similar for several texts: embeds them and calls search_vectors."""
+        self._require_model()
+        embedder, reducer = self._upstream()
+        self._check_provenance(list(self.storage.index.keys()), self._tags())
+        qs = [reducer.transform(np.asarray(embedder.get_embedding(t)).reshape(1, -1))[0] for t in texts]
+        return self.search_vectors(qs, top_k, min_similarity)
+
+    def search_vectors(self, queries, top_k: int = 5, min_similarity: float = 0.5) -> List[List[Tuple[str, float]]]:
+        """[search_vector(q, top_k, min_similarity) for q in queries]. With
+        encrypt_query on one rank the queries are encrypted together and
+        scored in one batched pass per document chunk (fheicp.query
+        compare_many), then one top-k per query; every other mode, and a
+        torch.distributed group, loops over search_vector."""
+        queries = [np.asarray(q) for q in queries]
+        if not queries or not self.config.encrypt_query or _world()[0] > 1 or self.storage.holds_ciphertexts():
+            return [self.search_vector(q, top_k, min_similarity) for q in queries]
+        self._require_model()
+        ids, E = self.storage.corpus()
+        if not ids:
+            return [[] for _ in queries]
+        for q in queries:
+            if q.shape != (E.shape[1],):
+                raise ValueError(f"query shape {q.shape} does not match corpus width {E.shape[1]}")
+        k = len(ids) if top_k < 0 else min(int(top_k), len(ids))
+        if k == 0:
+            return [[] for _ in queries]
+        hits = self._search_private_queries(queries, E, k, min_similarity)
+        return [[(ids[i], s) for i, s in h][:top_k] for h in hits]
+
     def _search_ciphertexts(self, query, top_k: int, t: float) -> List[Tuple[str, float]]:
         """Search over a store of seeded-LWE documents (fheicp.corpus): the
         corpus stays encrypted in HBM (one body word per feature); every rank
@@ -574,14 +605,9 @@ class BatchProcessor:
         world, rank = _world()
         n = E.shape[0]
         lo, hi = rank * n // world, (rank + 1) * n // world
-        r = self._resident_q
-        if r is None or r[0] is not E or r[1] != (lo, hi):
-            step = self.config.batch_size
-            chunks = [(qs.pack_docs(E[s:min(hi, s + step)]), min(hi, s + step) - s) for s in range(lo, hi, step)]
-            r = self._resident_q = (E, (lo, hi), chunks)
         payload = qs.encrypt_query(query)
         accs, belows = [], []
-        for docs8, nb in r[2]:
+        for docs8, nb in self._resident_query_docs(qs, E, lo, hi):
             acc, below = qs.compare(payload, docs8, nb, t)
             accs.append(acc)
             belows.append(below)
@@ -594,6 +620,44 @@ class BatchProcessor:
         oa, oi = oa.cpu().numpy(), oi.cpu().numpy()
         s = np.float64(c.cq.out_scale)
         return [(int(i), float(s * np.float64(a))) for a, i in zip(oa, oi) if i >= 0]
+
+    def _resident_query_docs(self, qs, E, lo: int, hi: int):
+        """The packed, device-resident quantized documents [lo, hi) in
+        batch_size chunks: [(docs8, count)], rebuilt when the store changes."""
+        r = self._resident_q
+        if r is None or r[0] is not E or r[1] != (lo, hi):
+            step = self.config.batch_size
+            chunks = [(qs.pack_docs(E[s:min(hi, s + step)]), min(hi, s + step) - s) for s in range(lo, hi, step)]
+            r = self._resident_q = (E, (lo, hi), chunks)
+        return r[2]
+
+    def _search_private_queries(self, queries, E, k: int, t: float):
+        """_search_private_query for several queries on one rank: one
+        encryption call, one batched compare per document chunk
+        (EncryptedQuerySearch.compare_many), one top-k per query segment."""
+        import torch
+        from fheicp.query import EncryptedQuerySearch
+        from fheicp.search import sharded_topk
+        c = self.corpus_engine
+        if c is None:
+            raise RuntimeError("encrypt_query needs BatchConfig(encrypt_query=True, fhe='execute')")
+        qs = EncryptedQuerySearch(c)
+        eng = c.engine
+        payloads = qs.encrypt_queries(np.stack(queries))
+        accs, belows = [], []
+        for docs8, nb in self._resident_query_docs(qs, E, 0, E.shape[0]):
+            acc, below = qs.compare_many(payloads, docs8, nb, t)
+            accs.append(acc)
+            belows.append(below)
+        acc, below = torch.cat(accs, dim=1), torch.cat(belows, dim=1)
+        s = np.float64(c.cq.out_scale)
+        out = []
+        for q in range(len(queries)):
+            oa, oi = sharded_topk(acc[q].contiguous(), below[q].contiguous(), k, 0,
+                                  lambda a, b, kk, base: eng.topk(a, b, kk, base), 1)
+            oa, oi = oa.cpu().numpy(), oi.cpu().numpy()
+            out.append([(int(i), float(s * np.float64(a))) for a, i in zip(oa, oi) if i >= 0])
+        return out
 
     @staticmethod
     def _search_clear_sharded(m, query, E, k, t):

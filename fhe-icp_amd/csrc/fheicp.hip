@@ -2000,6 +2000,79 @@ int fhe_linear_query_batch(fhe_ctx* ctx, const uint64_t* d_ct_q, const void* d_d
   return FHE_OK;
 }
 
+// ---- several queries of one key holder in one pass -------
+static int queries_args(fhe_ctx* ctx, int64_t Q, int64_t B, int32_t D) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  if (Q < 1 || B < 1 || D <= 0) return fail(ctx, FHE_E_ARG, "bad queries arguments (Q < 1, B < 1 or D <= 0)");
+  if (D > 65536) return fail(ctx, FHE_E_ARG, "queries dimension D > 65536 overflows the i32 accumulators");
+  // the query is a grid dimension of the plane and GEMM launches
+  if (Q > 65535) return fail(ctx, FHE_E_ARG, "queries batch Q > 65535: split the call");
+  if (B > (int64_t)1 << 40) return fail(ctx, FHE_E_ARG, "queries document batch too large: split the call");
+  return FHE_OK;
+}
+// n host words -> device, 32 per launch as kernel arguments (stream-ordered,
+// no host buffer to keep alive, no synchronisation)
+static int store_words(fhe_ctx* ctx, u64* d_dst, const u64* h_src, int64_t n, hipStream_t st) {
+  for (int64_t i = 0; i < n; i += 32) {
+    Words32 w;
+    const int m = (int)std::min<int64_t>(32, n - i);
+    for (int j = 0; j < 32; ++j) w.v[j] = j < m ? h_src[i + j] : 0;
+    hipLaunchKernelGGL(k_store_words, dim3(1), dim3(64), 0, st, d_dst + i, m, w);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+int fhe_linear_queries_batch(fhe_ctx* ctx, const uint64_t* d_ct_q, int64_t Q, const void* d_docs8, int64_t B,
+                             int32_t D, const int64_t* d_w, const int64_t* h_cst, uint64_t* d_out, void* stream) {
+  int rc = queries_args(ctx, Q, B, D);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  if ((rc = need_device(ctx))) return rc;
+  if (!d_ct_q || !d_docs8 || !d_w || !h_cst || !d_out) return fail(ctx, FHE_E_ARG, "null linear queries buffers");
+  const fhe_params& p = ctx->p;
+  hipStream_t st = (hipStream_t)stream;
+  const int W = p.k * p.N + 1, NB = (W + 15) / 16, KB = query_kb(D);
+  const int64_t rblocks = ((B + 15) / 16 + 4 * LQ_RB - 1) / (4 * LQ_RB);
+  if (rblocks > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "queries document batch too large: split the call");
+  // Q plane sets (KB * 64 rows x NB * 16 columns x 8 planes each), then the Q
+  // pre-scaled constants
+  const size_t planes = (size_t)KB * 64 * NB * 16 * 8 * (size_t)Q, need = planes + 8 * (size_t)Q;
+  if (need > ctx->lq_ws_bytes) {
+    if (ctx->lq_ws) {
+      HIPCHK(ctx, hipDeviceSynchronize());
+      HIPCHK(ctx, hipFree(ctx->lq_ws));
+      ctx->lq_ws = nullptr;
+      ctx->lq_ws_bytes = 0;
+    }
+    if (hipMalloc(&ctx->lq_ws, need) != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->lq_ws = nullptr;
+      return fail(ctx, FHE_E_NOMEM, "queries plane workspace: out of device memory (fewer queries per call)");
+    }
+    ctx->lq_ws_bytes = need;
+  }
+  u64* d_cst = (u64*)((char*)ctx->lq_ws + planes);
+  std::vector<u64> cs((size_t)Q);
+  for (int64_t q = 0; q < Q; ++q) cs[(size_t)q] = (u64)h_cst[q] << (64 - p.msg_bits);
+  if ((rc = store_words(ctx, d_cst, cs.data(), Q, st))) return rc;
+  hipEvent_t e1;
+  prof_begin(ctx, ctx->prof_lq, st, &e1);
+  ctx->prof_lq.kernel = "k_linear_queries_mfma";
+  hipLaunchKernelGGL(k_query_planes, dim3((unsigned)(KB * NB), (unsigned)Q), dim3(64), 0, st, d_ct_q, (int)D, W, NB, KB,
+                     d_w, (v4i*)ctx->lq_ws);
+#ifdef FHEICP_LQ_QLOOP
+  const unsigned qgrid = 1;  // A/B: the waves loop over the queries
+#else
+  const unsigned qgrid = (unsigned)Q;
+#endif
+  hipLaunchKernelGGL(k_linear_queries_mfma, dim3((unsigned)rblocks, (unsigned)((NB + LQ_CB - 1) / LQ_CB), qgrid),
+                     dim3(256), 0, st, (const v4i*)d_docs8, (const v4i*)ctx->lq_ws, B, W, NB, KB, (const u64*)d_cst,
+                     d_out, (int)Q);
+  prof_end(ctx, ctx->prof_lq, st, e1, Q * B);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
 // ---- LWE -> GLWE packing key switch (k_pack.h) ------------
 // gadget (beta, L) of a packing key: int8 digits, at most 8 levels, and every
 // tie coin (input bit 62 - beta L - s, s < L) an input bit
@@ -2330,6 +2403,73 @@ int fhe_search_query_batch(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0, 
   rc = query_leveled(ctx, d_qbody, id0, h_mask_key, d_docs8, B, D, d_w, cst - T, true, &w, stream);
   if (rc) return rc;
   return post_leveled_search(ctx, w, B, levels_bit, d_glwe_acc, d_glwe_bit, stream);
+}
+
+// Q queries of one key holder in one pass: the workspace of
+// query_leveled for Q B results with, in the query's place, the Q D expanded
+// ciphertexts and the Q thresholds; one expansion (k_expand_seeded's B = Q),
+// one GEMM launch with cst - T_q on query q's bodies, into ct_v (query-major).
+static int queries_leveled(fhe_ctx* ctx, const uint64_t* d_qbody, const uint64_t* d_id0, const uint32_t h_mask_key[8],
+                           int64_t Q, const void* d_docs8, int64_t B, int32_t D, const int64_t* d_w, int64_t cst,
+                           const int64_t* h_T, bool keep_copy, QueryWs* w, int64_t** d_T, void* stream) {
+  const size_t Wb = fhe_big_lwe_words(&ctx->p);
+  u64* ctq;
+  int rc = leveled_ws(ctx, Q * B, (size_t)Q * D * Wb + (size_t)Q, keep_copy, w, &ctq);
+  if (rc) return rc;
+  *d_T = (int64_t*)(ctq + (size_t)Q * D * Wb);
+  std::vector<int64_t> cs((size_t)Q);
+  for (int64_t q = 0; q < Q; ++q) cs[(size_t)q] = cst - h_T[q];
+  if ((rc = store_words(ctx, (u64*)*d_T, (const u64*)h_T, Q, (hipStream_t)stream))) return rc;
+  rc = fhe_expand_seeded_batch(ctx, d_qbody, d_id0, Q, D, h_mask_key, ctq, stream);
+  if (rc) return rc;
+  return fhe_linear_queries_batch(ctx, ctq, Q, d_docs8, B, D, d_w, cs.data(), w->ctv, stream);
+}
+
+int fhe_compare_queries_batch(fhe_ctx* ctx, const uint64_t* d_qbody, const uint64_t* d_id0,
+                              const uint32_t h_mask_key[8], int64_t Q, const void* d_docs8, int64_t B, int32_t D,
+                              const int64_t* d_w, int64_t cst, const int64_t* h_T, int64_t* d_acc, int64_t* d_below,
+                              void* stream) {
+  int rc = queries_args(ctx, Q, B, D);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  if ((rc = need_secret(ctx))) return rc;
+  if (!h_mask_key || !h_T || !d_qbody || !d_id0 || !d_docs8 || !d_w || !d_acc || !d_below)
+    return fail(ctx, FHE_E_ARG, "null compare queries arguments");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n = Q * B;
+  QueryWs w;
+  int64_t* d_T;
+  rc = queries_leveled(ctx, d_qbody, d_id0, h_mask_key, Q, d_docs8, B, D, d_w, cst, h_T, false, &w, &d_T, stream);
+  if (rc) return rc;
+  // post_leveled_compare with query q's own threshold added back
+  if ((rc = fhe_decrypt_batch(ctx, w.ctv, n, w.v, stream))) return rc;
+  if ((rc = sign_extract_batch(ctx, w.ctv, n, w.sgn, w.small, st))) return rc;
+  if ((rc = fhe_decrypt_bits_batch(ctx, w.sgn, n, d_below, stream))) return rc;
+  hipLaunchKernelGGL(k_add_query_scalar, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w.v, n, B, d_T, d_acc);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+int fhe_search_queries_batch(fhe_ctx* ctx, const uint64_t* d_qbody, const uint64_t* d_id0,
+                             const uint32_t h_mask_key[8], int64_t Q, const void* d_docs8, int64_t B, int32_t D,
+                             const int64_t* d_w, int64_t cst, const int64_t* h_T, int32_t levels_bit,
+                             uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream) {
+  int rc = queries_args(ctx, Q, B, D);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  if (levels_bit < 0 || levels_bit > 8)
+    return fail(ctx, FHE_E_ARG, "bad search queries arguments (levels_bit outside [0, 8])");
+  if ((rc = need_eval_keys(ctx))) return rc;
+  if ((rc = need_pack_key(ctx))) return rc;
+  if (levels_bit > ctx->pk_level)
+    return fail(ctx, FHE_E_ARG, "search queries levels_bit exceeds the packing key's levels");
+  if (!h_mask_key || !h_T || !d_qbody || !d_id0 || !d_docs8 || !d_w || !d_glwe_acc || !d_glwe_bit)
+    return fail(ctx, FHE_E_ARG, "null search queries arguments");
+  QueryWs w;
+  int64_t* d_T;
+  rc = queries_leveled(ctx, d_qbody, d_id0, h_mask_key, Q, d_docs8, B, D, d_w, cst, h_T, true, &w, &d_T, stream);
+  if (rc) return rc;
+  // result q B + b is ciphertext q B + b of the batch: coefficient (q B + b) mod N
+  // of GLWE (q B + b) / N
+  return post_leveled_search(ctx, w, Q * B, levels_bit, d_glwe_acc, d_glwe_bit, stream);
 }
 
 // ---- both-private search: GGSW query x GLWE documents (k_extprod.h, §8.7) --

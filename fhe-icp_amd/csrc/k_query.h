@@ -11,6 +11,8 @@
 // a multiple of 2^64), each plane an i8 GEMM with i32 accumulation
 // (|sum| <= D * 2^14, D <= 65536), recombined as sum_q acc_q << 8q modulo 2^64
 // in the epilogue: bit-identical to the plain u64 sum.
+// Several queries of one key holder share the documents in one launch, the
+// query a grid dimension of the plane and GEMM kernels.
 #pragma once
 
 #include "common.h"
@@ -47,10 +49,14 @@ __global__ void __launch_bounds__(256) k_query_docs_pack(const int64_t* __restri
 // one thread per fragment lane: 16 words in, eight 16-byte stores out (the
 // wave writes 1 KB runs). The loads are unconditional (rows clamped to D - 1,
 // their weight zeroed), so a lane has all 16 in flight at once; at D = 16 the
-// grid is 129 waves, spread over as many CUs.
+// grid is 129 waves, spread over as many CUs. A batch of queries
+// (ct [Q][D][W]) puts the query on grid y: the same layout once per query,
+// [q][kb][nb][plane][lane].
 __global__ void __launch_bounds__(64) k_query_planes(const u64* __restrict__ ct, int D, int W, int NB, int KB,
                                                      const int64_t* __restrict__ w, v4i* __restrict__ out) {
-  const int lane = threadIdx.x, f = blockIdx.x;  // grid = KB * NB
+  const int lane = threadIdx.x, f = blockIdx.x;  // grid = KB * NB x Q
+  ct += (size_t)blockIdx.y * D * W;
+  out += (size_t)blockIdx.y * KB * NB * 8 * 64;
   const int kb = f / NB, nb = f - kb * NB;
   const int col = nb * 16 + (lane & 15);
   const int r0 = kb * 64 + 16 * (lane >> 4);
@@ -101,9 +107,11 @@ __global__ void __launch_bounds__(64) k_query_planes(const u64* __restrict__ ct,
 #define FHEICP_LQ_CB 1
 #endif
 constexpr int LQ_RB = FHEICP_LQ_RB, LQ_CB = FHEICP_LQ_CB;
-__global__ void __launch_bounds__(256, 2) k_linear_query_mfma(const v4i* __restrict__ A, const v4i* __restrict__ P8,
-                                                           int64_t B, int W, int NB, int KB, u64 cst_scaled,
-                                                           u64* __restrict__ out) {
+// KBC: the k-block count as a compile-time constant (0: KB at run time)
+template <int KBC = 0>
+__device__ __forceinline__ void lq_wave_tile(const v4i* __restrict__ A, const v4i* __restrict__ P8, int64_t B, int W,
+                                             int NB, int KB, u64 cst_scaled, u64* __restrict__ out) {
+  if (KBC) KB = KBC;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t ncb = (B + 15) / 16;
   const int64_t rg0 = ((int64_t)blockIdx.x * 4 + wv) * LQ_RB;
@@ -161,7 +169,60 @@ __global__ void __launch_bounds__(256, 2) k_linear_query_mfma(const v4i* __restr
   }
 }
 
+__global__ void __launch_bounds__(256, 2) k_linear_query_mfma(const v4i* __restrict__ A, const v4i* __restrict__ P8,
+                                                           int64_t B, int W, int NB, int KB, u64 cst_scaled,
+                                                           u64* __restrict__ out) {
+  lq_wave_tile(A, P8, B, W, NB, KB, cst_scaled, out);
+}
+
+// Q queries against the same documents, the query on grid z: query q reads
+// its own planes (P8 + q KB NB 8 fragments) and constant (cst_scaled[q], a
+// device array) and owns output rows [q B, (q + 1) B). The document fragments
+// are the same lines for every q. B need not be a multiple of 16, so a
+// query's rows do not start on a 16-row boundary: the row guard stays
+// `row < B` inside the query (lq_wave_tile), the q B offset is added after it,
+// and a wave's padded rows never reach the next query's.
+// -DFHEICP_LQ_QLOOP (A/B builds) launches grid z = 1 instead and lets each
+// wave loop over the Q queries, its document fragments loop-invariant (in
+// registers at one k-block, from the L1 beyond). Measured slower at every
+// shape tried: Q = 8, B = 128: 23.0 against 17.5 us at D = 16 (it leaves 129
+// workgroups for 256 CUs), 154.1 against 73.4 us at D = 768
+// (docs/AB_LOG_r11.md).
+__global__ void __launch_bounds__(256, 2) k_linear_queries_mfma(const v4i* __restrict__ A, const v4i* __restrict__ P8,
+                                                             int64_t B, int W, int NB, int KB,
+                                                             const u64* __restrict__ cst_scaled,
+                                                             u64* __restrict__ out, int Q) {
+#ifdef FHEICP_LQ_QLOOP
+  for (size_t q = 0; q < (size_t)Q; ++q) {
+    if (KB == 1)
+      lq_wave_tile<1>(A, P8 + q * NB * 8 * 64, B, W, NB, 1, cst_scaled[q], out + q * (size_t)B * W);
+    else
+      lq_wave_tile(A, P8 + q * KB * NB * 8 * 64, B, W, NB, KB, cst_scaled[q], out + q * (size_t)B * W);
+  }
+#else
+  const size_t q = blockIdx.z;
+  (void)Q;
+  lq_wave_tile(A, P8 + q * KB * NB * 8 * 64, B, W, NB, KB, cst_scaled[q], out + q * (size_t)B * W);
+#endif
+}
+
 // one device word (the stream id of a seeded query for k_expand_seeded)
 __global__ void k_store_word(u64* __restrict__ p, u64 v) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *p = v;
+}
+
+// up to 32 device words from the kernel's arguments (a batch of queries'
+// pre-scaled constants and thresholds): no host buffer outlives the call
+struct Words32 {
+  u64 v[32];
+};
+__global__ void k_store_words(u64* __restrict__ p, int n, Words32 w) {
+  if (blockIdx.x == 0 && (int)threadIdx.x < n) p[threadIdx.x] = w.v[threadIdx.x];
+}
+
+// out[i] = v[i] + T[i / B]: query i / B's threshold back onto its B results
+__global__ void k_add_query_scalar(const int64_t* __restrict__ v, int64_t n, int64_t B, const int64_t* __restrict__ T,
+                                   int64_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = v[i] + T[i / B];
 }

@@ -133,6 +133,11 @@ SIGNATURES = [
     ("fhe_profile_read", C.c_int, [_CTXP, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(_i64)]),
     ("fhe_profile_kernel_name", C.c_int, [_CTXP, C.c_char_p, C.c_char_p, C.c_size_t]),
     ("fhe_build_info", C.c_char_p, []),
+    ("fhe_linear_queries_batch", C.c_int, [_CTXP, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    ("fhe_compare_queries_batch", C.c_int, [_CTXP, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp,
+                                            _vp]),
+    ("fhe_search_queries_batch", C.c_int, [_CTXP, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i32, _vp,
+                                           _vp, _vp]),
     # include/fhe_bert.h: the embedding stage's encoder (fheicp.bert)
     ("fhe_bert_create", C.c_int, [_vp, C.c_int, C.POINTER(C.c_void_p)]),
     ("fhe_bert_destroy", None, [_vp]),

@@ -512,6 +512,54 @@ class Engine:
                                                  int(levels_bit), _ptr(ga), _ptr(gb), _stream(self.device)))
         return ga, gb
 
+    # --------------- several queries of one key holder in one pass (§8.8) --
+    @staticmethod
+    def _i64s(vals):
+        a = np.ascontiguousarray([int(v) for v in vals], dtype=np.int64)
+        return a, C.c_void_p(a.ctypes.data)
+
+    def linear_queries(self, ct_q: torch.Tensor, Q: int, docs8: torch.Tensor, B: int, D: int, w, csts,
+                       out: torch.Tensor | None = None) -> torch.Tensor:
+        """fhe_linear_queries_batch: ct_q Q * D x (kN+1), csts Q host
+        constants; Q * B x (kN+1), query-major."""
+        wd = self.to_dev(w)
+        if out is None:
+            out = self.empty_big(Q * B)
+        keep, hc = self._i64s(csts)
+        if keep.size != Q:
+            raise ValueError(f"{keep.size} constants for {Q} queries")
+        self._chk(self._L.fhe_linear_queries_batch(self._ctx, _ptr(ct_q), int(Q), _ptr(docs8), int(B), int(D),
+                                                   _ptr(wd), hc, _ptr(out), _stream(self.device)))
+        return out
+
+    def compare_queries(self, qbody: torch.Tensor, id0: torch.Tensor, mask_key, docs8: torch.Tensor, B: int, D: int,
+                        w: torch.Tensor, cst: int, Ts):
+        """fhe_compare_queries_batch: Q seeded queries (qbody [Q, D], id0 [Q],
+        both on the device) against packed clear documents;
+        (acc int64 [Q, B], below int64 [Q, B])."""
+        keep, hT = self._i64s(Ts)
+        Q = keep.size
+        acc = torch.empty((Q, B), dtype=torch.int64, device=self.device)
+        below = torch.empty((Q, B), dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_compare_queries_batch(self._ctx, _ptr(qbody), _ptr(id0), self._key(mask_key), Q,
+                                                    _ptr(docs8), int(B), int(D), _ptr(w), int(cst), hT, _ptr(acc),
+                                                    _ptr(below), _stream(self.device)))
+        return acc, below
+
+    def search_queries(self, qbody: torch.Tensor, id0: torch.Tensor, mask_key, docs8: torch.Tensor, B: int, D: int,
+                       w: torch.Tensor, cst: int, Ts, levels_bit: int = 0):
+        """fhe_search_queries_batch: the evaluation-only form;
+        (glwe_acc, glwe_bit), each ceil(Q B / N) x (k+1)N words."""
+        keep, hT = self._i64s(Ts)
+        Q = keep.size
+        shape = (self.glwe_count(Q * B), (self.params.k + 1) * self.params.N)
+        ga = torch.empty(shape, dtype=torch.int64, device=self.device)
+        gb = torch.empty(shape, dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_search_queries_batch(self._ctx, _ptr(qbody), _ptr(id0), self._key(mask_key), Q,
+                                                   _ptr(docs8), int(B), int(D), _ptr(w), int(cst), hT,
+                                                   int(levels_bit), _ptr(ga), _ptr(gb), _stream(self.device)))
+        return ga, gb
+
     # ------------- both-private search: GGSW query x GLWE documents (§8.7) --
     def ggsw_words(self, base_log: int, level: int) -> int:
         return self._L.fhe_ggsw_words(C.byref(self._P), int(base_log), int(level))

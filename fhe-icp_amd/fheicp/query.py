@@ -23,6 +23,11 @@ worst-case range [-bound, bound].
 
 Query payload (uint64 vector):
     [MAGIC, 1, D, P0, id0, mask key (4 words), k*N, body_0 .. body_{D-1}]
+
+Several queries of one key holder against the same documents go through in
+one pass: encrypt_queries, compare_many, and for two parties
+QueryServer.search_many / QueryClient.decrypt_replies. A batch is a list of
+the payloads above whose stream-id ranges [id0, id0 + D) are disjoint.
 """
 from __future__ import annotations
 
@@ -54,6 +59,53 @@ def unpack_query(arr) -> dict:
         raise ValueError(f"query payload holds {a.size - HEADER_WORDS} bodies, header says {D}")
     return {"D": D, "P0": int(a[3]), "id0": int(a[4]), "mask_key": a[5:9].copy().view(np.uint32),
             "big": int(a[9]), "body": a[HEADER_WORDS:].copy()}
+
+
+# ------------------------------------------------------ batches of queries --
+# Several queries of one key holder answered in one pass: a
+# batch is a list of the payloads above, no new format.
+MAX_RESULTS = 8192  # results (Q * B) one library call carries, unless B alone is larger
+
+
+def check_query_batch(pls) -> None:
+    """The unpacked payloads of one batch agree in P0, big, D and mask key,
+    and no two stream-id ranges [id0, id0 + D) overlap modulo 2^64 (an id must
+    not repeat under one mask key). ValueError names the offending query."""
+    if not pls:
+        raise ValueError("an empty batch of queries")
+    first = pls[0]
+    for i, pl in enumerate(pls[1:], 1):
+        for field, what in (("P0", "width P0"), ("big", "ciphertext size"), ("D", "dimension D")):
+            if pl[field] != first[field]:
+                raise ValueError(f"query {i}: {what} {pl[field]} differs from query 0's {first[field]}")
+        if not np.array_equal(pl["mask_key"], first["mask_key"]):
+            raise ValueError(f"query {i}: mask key differs from query 0's")
+    D = int(first["D"])
+    order = sorted(range(len(pls)), key=lambda i: int(pls[i]["id0"]))
+    for a, b in zip(order, order[1:] + order[:1]):
+        if a == b:
+            break  # one query: its D <= 65536 ids cannot meet themselves
+        if (int(pls[b]["id0"]) - int(pls[a]["id0"])) % (1 << 64) < D:
+            raise ValueError(f"query {max(a, b)}: stream ids [id0, id0 + {D}) overlap query {min(a, b)}'s")
+
+
+def query_chunks(Q: int, B: int, cap: int = MAX_RESULTS) -> list:
+    """range(Q) split into consecutive ranges of max(1, cap // B) queries: one
+    library call carries at most max(B, cap) results."""
+    if Q < 0 or B < 1 or cap < 1:
+        raise ValueError("query_chunks needs Q >= 0, B >= 1, cap >= 1")
+    step = max(1, cap // B)
+    return [range(s, min(Q, s + step)) for s in range(0, Q, step)]
+
+
+def thresholds_for(min_similarity, Q: int) -> list:
+    """A float, None, or a sequence of Q of them -> a list of Q."""
+    if min_similarity is None or np.isscalar(min_similarity):
+        return [min_similarity] * Q
+    ts = list(min_similarity)
+    if len(ts) != Q:
+        raise ValueError(f"{len(ts)} thresholds for {Q} queries")
+    return ts
 
 
 class EncryptedQuerySearch:
@@ -140,6 +192,54 @@ class EncryptedQuerySearch:
     def scores(self, acc) -> np.ndarray:
         return self.corpus.scores(acc)
 
+    # -------------------------------------------------- batches of queries --
+    def encrypt_queries(self, vectors, id0: int | None = None) -> list:
+        """Q reduced query vectors [Q, D] -> Q payloads in one encryption
+        call. Query q takes the stream ids [id0 + q D, id0 + (q + 1) D)
+        modulo 2^64 from a fresh random id0: disjoint within the batch."""
+        c = self.corpus
+        c._need()
+        eng = c.engine
+        qq = self.cq.quant(np.atleast_2d(np.asarray(vectors)))
+        Q, D = qq.shape
+        if id0 is None:
+            id0 = int.from_bytes(os.urandom(8), "little")
+        ids = [(int(id0) + q * D) % (1 << 64) for q in range(Q)]
+        eng.set_msg_bits(self.P0)
+        body = eng.encrypt_seeded(eng.to_dev(qq), c.mask_key, c._noise_key, eng.to_dev(np.array(ids, dtype=np.uint64)))
+        body = body.cpu().numpy().view(np.uint64)
+        return [pack_query(body[q], ids[q], self.P0, c.mask_key, c.scheme.k * c.scheme.N) for q in range(Q)]
+
+    def plan_many(self, min_similarity, Q: int):
+        """(w, cst, [T_0 .. T_{Q-1}]): plan() per query threshold."""
+        w, cst, _ = self.plan(None)
+        return w, cst, [self.plan(t)[2] for t in thresholds_for(min_similarity, Q)]
+
+    def compare_many(self, payloads, docs8, B: int, min_similarity=None):
+        """Q payloads of this key holder against the same packed documents
+        in one pass per chunk of query_chunks(Q, B) (fhe_compare_queries_batch)
+        -> (acc int64 [Q, B], below int64 [Q, B]) device tensors.
+        min_similarity: a float, None, or a sequence of Q of them."""
+        import torch
+        self.corpus._need()
+        eng = self.corpus.engine
+        pls = [unpack_query(p) for p in payloads]
+        check_query_batch(pls)
+        self.check(pls[0])
+        Q, D = len(pls), pls[0]["D"]
+        w, cst, Ts = self.plan_many(min_similarity, Q)
+        eng.set_msg_bits(self.P0)
+        wd = eng.to_dev(w)
+        accs, belows = [], []
+        for ch in query_chunks(Q, int(B)):
+            body = eng.to_dev(np.stack([pls[q]["body"] for q in ch]))
+            ids = eng.to_dev(np.array([pls[q]["id0"] for q in ch], dtype=np.uint64))
+            acc, below = eng.compare_queries(body, ids, pls[0]["mask_key"], docs8, int(B), D, wd, cst,
+                                             [Ts[q] for q in ch])
+            accs.append(acc)
+            belows.append(below)
+        return torch.cat(accs), torch.cat(belows)
+
 
 # ------------------------------------------------------------- two parties --
 # The same search with the two roles in two contexts (DESIGN.md §8.6): the
@@ -176,6 +276,40 @@ def unpack_reply(arr) -> dict:
     return {"P0": int(a[1]) >> 32, "B": int(a[2]), "T": T - (1 << 64) if T >> 63 else T,
             "glwe_acc": a[REPLY_HEADER_WORDS:REPLY_HEADER_WORDS + words // 2].copy(),
             "glwe_bit": a[REPLY_HEADER_WORDS + words // 2:].copy()}
+
+
+# Reply to a batch of queries, version 2 (uint64 vector):
+#     [REPLY_MAGIC, 2 | P0 << 32, B, Q, T_0 .. T_{Q-1} (two's complement),
+#      GLWEs of acc - T_q: ceil(Q B / N) x (k+1)N words, GLWEs of the bits: the same]
+# Result (q, b) is coefficient (q B + b) mod N of GLWE (q B + b) / N.
+def pack_replies(glwe_acc, glwe_bit, B: int, P0: int, Ts) -> np.ndarray:
+    ga = np.asarray(glwe_acc, dtype=np.uint64).reshape(-1)
+    gb = np.asarray(glwe_bit, dtype=np.uint64).reshape(-1)
+    head = np.array([REPLY_MAGIC, 2 | (int(P0) << 32), int(B), len(Ts)] + [int(T) % (1 << 64) for T in Ts],
+                    dtype=np.uint64)
+    return np.concatenate([head, ga, gb])
+
+
+def unpack_replies(arr, glwe_words: int | None = None, N: int | None = None) -> dict:
+    """A version-2 reply. With glwe_words = (k+1)N and N it also rejects a
+    size that does not match ceil(Q B / N) GLWEs per block."""
+    a = np.asarray(arr)
+    if a.dtype != np.uint64 or a.ndim != 1 or a.size < REPLY_HEADER_WORDS or int(a[0]) != REPLY_MAGIC:
+        raise ValueError("not an fheicp packed reply")
+    if int(a[1]) & 0xFFFFFFFF != 2:
+        raise ValueError(f"unsupported batched reply version {int(a[1]) & 0xFFFFFFFF}")
+    B, Q = int(a[2]), int(a[3])
+    if B < 1 or Q < 1 or a.size < REPLY_HEADER_WORDS + Q:
+        raise ValueError(f"reply header names {Q} queries of {B} documents in {a.size} words")
+    words = a.size - REPLY_HEADER_WORDS - Q
+    if words % 2:
+        raise ValueError("reply holds an odd number of GLWE words")
+    if glwe_words is not None and words // 2 != -(-(Q * B) // int(N)) * int(glwe_words):
+        raise ValueError(f"reply size does not match {Q} queries of {B} documents")
+    Ts = [int(t) - (1 << 64) if int(t) >> 63 else int(t) for t in a[REPLY_HEADER_WORDS:REPLY_HEADER_WORDS + Q]]
+    g0 = REPLY_HEADER_WORDS + Q
+    return {"P0": int(a[1]) >> 32, "B": B, "Q": Q, "T": Ts, "glwe_acc": a[g0:g0 + words // 2].copy(),
+            "glwe_bit": a[g0 + words // 2:].copy()}
 
 
 def save_eval_keys(path: str, keys: dict) -> None:
@@ -230,6 +364,31 @@ class QueryClient:
         acc = eng.decrypt_packed(eng.to_dev(r["glwe_acc"]), r["B"], 0) + r["T"]
         below = eng.decrypt_packed(eng.to_dev(r["glwe_bit"]), r["B"], 1)
         return acc, below
+
+    def encrypt_queries(self, vectors, id0: int | None = None) -> list:
+        """[Q, D] query vectors -> Q payloads with fresh, disjoint stream ids."""
+        return self.single.encrypt_queries(vectors, id0)
+
+    def decrypt_replies(self, replies):
+        """The list QueryServer.search_many returns (or one version-2 reply)
+        -> (acc int64 [Q, B], below int64 [Q, B]) device tensors, the chunks'
+        queries in order. Adds T_q back per query."""
+        import torch
+        eng = self.corpus.engine
+        if isinstance(replies, np.ndarray):
+            replies = [replies]
+        n1 = (eng.params.k + 1) * eng.params.N
+        eng.set_msg_bits(self.P0)
+        accs, belows = [], []
+        for reply in replies:
+            r = unpack_replies(reply, n1, eng.params.N)
+            if r["P0"] != self.P0:
+                raise ValueError("reply was computed at a different width")
+            Q, B = r["Q"], r["B"]
+            T = eng.to_dev(np.array(r["T"], dtype=np.int64)).reshape(Q, 1)
+            accs.append(eng.decrypt_packed(eng.to_dev(r["glwe_acc"]), Q * B, 0).reshape(Q, B) + T)
+            belows.append(eng.decrypt_packed(eng.to_dev(r["glwe_bit"]), Q * B, 1).reshape(Q, B))
+        return torch.cat(accs), torch.cat(belows)
 
     def top_k(self, acc, below, k: int, base_idx: int = 0):
         return self.corpus.engine.topk(acc, below, k, base_idx)
@@ -286,3 +445,33 @@ class QueryServer:
         ga, gb = eng.search_query(eng.to_dev(pl["body"]), pl["id0"], pl["mask_key"], docs8, int(B), pl["D"],
                                   eng.to_dev(w), cst, T, self.bit_levels)
         return pack_reply(ga.cpu().numpy().view(np.uint64), gb.cpu().numpy().view(np.uint64), B, self.P0, T)
+
+    def search_many(self, payloads, docs8, B: int, min_similarity=None) -> list:
+        """Q encrypted queries of one key holder against B packed documents
+        in one pass (fhe_search_queries_batch) -> a LIST of version-2 replies,
+        always: one per chunk of query_chunks(Q, B), so a single element
+        unless Q * B exceeds max(B, 8192) results. min_similarity: a float,
+        None, or a sequence of Q of them. QueryClient.decrypt_replies takes
+        the list."""
+        eng = self.engine
+        pls = [unpack_query(p) for p in payloads]
+        check_query_batch(pls)
+        pl = pls[0]
+        if pl["P0"] != self.P0 or pl["big"] != self.scheme.k * self.scheme.N:
+            raise ValueError("query 0 was encrypted under different parameters")
+        if pl["D"] != len(self.cq.model.q_w):
+            raise ValueError(f"query 0 holds {pl['D']} features, the model {len(self.cq.model.q_w)}")
+        Q = len(pls)
+        w, cst, _ = self.plan(None)
+        Ts = [self.plan(t)[2] for t in thresholds_for(min_similarity, Q)]
+        wd = eng.to_dev(w)
+        out = []
+        for ch in query_chunks(Q, int(B)):
+            body = eng.to_dev(np.stack([pls[q]["body"] for q in ch]))
+            ids = eng.to_dev(np.array([pls[q]["id0"] for q in ch], dtype=np.uint64))
+            Tc = [Ts[q] for q in ch]
+            ga, gb = eng.search_queries(body, ids, pl["mask_key"], docs8, int(B), pl["D"], wd, cst, Tc,
+                                        self.bit_levels)
+            out.append(pack_replies(ga.cpu().numpy().view(np.uint64), gb.cpu().numpy().view(np.uint64), B, self.P0,
+                                    Tc))
+        return out

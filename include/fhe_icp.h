@@ -575,6 +575,42 @@ int fhe_profile_kernel_name(fhe_ctx* ctx, const char* kernel, char* h_buf, size_
 /* "libfheicp gfx950 ab=0" for the shipped build; ab=1 for A/B builds
  * (tools/build_variant.sh -DFHEICP_AB: extra v4 shapes, v3, timing kernels). */
 const char* fhe_build_info(void);
+
+/* ---- private-query search: several queries in one pass ----
+ * Q encrypted queries of ONE key holder (one context, one set of evaluation
+ * keys, one mask key) against the same B packed documents: one leveled GEMM
+ * launch, one sign extraction over Q * B ciphertexts, one packing. Results
+ * are query-major: result (q, b) is row / element q * B + b. Q >= 1, B >= 1,
+ * 0 < D <= 65536, Q <= 65535; bad arguments return FHE_E_ARG, missing keys
+ * FHE_E_STATE, as in the single-query entries. The stream ids of one batch
+ * must not overlap: id ranges [id0_q, id0_q + D) are disjoint modulo 2^64
+ * (no id repeats under one mask key).
+ *
+ * The leveled step alone: d_ct_q holds Q * D full ciphertexts ([Q][D][kN+1]),
+ * h_cst Q host constants (one per query), d_out Q * B x (kN+1) with
+ *   out[q B + b] = sum_j dq[b][j] * (d_w[j] * ct_q[q][j]) + trivial(h_cst[q] * Delta),
+ * word for word what Q calls of fhe_linear_query_batch write. Needs no keys.
+ * The plane workspace grows to Q times the single-query size; timing goes to
+ * the "linear_query" profile bucket. */
+int fhe_linear_queries_batch(fhe_ctx* ctx, const uint64_t* d_ct_q, int64_t Q, const void* d_docs8, int64_t B,
+                             int32_t D, const int64_t* d_w, const int64_t* h_cst, uint64_t* d_out, void* stream);
+/* fhe_compare_query_batch for Q seeded queries: d_qbody Q x D body words,
+ * d_id0 Q stream ids (device), one public mask key, h_T Q thresholds (host).
+ * Query q runs with cst - h_T[q]; d_acc[q B + b] is the accumulator and
+ * d_below[q B + b] = 1 iff acc < h_T[q]. Single party: needs the secret key. */
+int fhe_compare_queries_batch(fhe_ctx* ctx, const uint64_t* d_qbody, const uint64_t* d_id0,
+                              const uint32_t h_mask_key[8], int64_t Q, const void* d_docs8, int64_t B, int32_t D,
+                              const int64_t* d_w, int64_t cst, const int64_t* h_T, int64_t* d_acc, int64_t* d_below,
+                              void* stream);
+/* fhe_search_query_batch for Q seeded queries: result q B + b goes to
+ * coefficient (q B + b) mod N of GLWE (q B + b) / N; d_glwe_acc (the values
+ * acc - h_T[q]) and d_glwe_bit are ceil(Q B / N) x (k+1)N words each. Needs
+ * evaluation keys and the packing key, no secret: works on a context made by
+ * fhe_import_eval_keys. */
+int fhe_search_queries_batch(fhe_ctx* ctx, const uint64_t* d_qbody, const uint64_t* d_id0,
+                             const uint32_t h_mask_key[8], int64_t Q, const void* d_docs8, int64_t B, int32_t D,
+                             const int64_t* d_w, int64_t cst, const int64_t* h_T, int32_t levels_bit,
+                             uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,12 @@ _PROTOS = {
     "fhe_pack_batch": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
     "fhe_decrypt_packed_batch": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
     "fhe_search_query_batch": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    # several queries of one key holder in one pass
+    "fhe_linear_queries_batch": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "fhe_compare_queries_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp,
+                                            _vp]),
+    "fhe_search_queries_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i32, _vp, _vp,
+                                           _vp]),
     # both sides encrypted: GGSW query x GLWE documents
     "fhe_encrypt_packed_batch_key": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _u64, _vp, _vp]),
     "fhe_encrypt_packed_batch": (C.c_int, [_vp, _vp, _i64, _i32, _u64, _u64, _vp, _vp]),
@@ -268,6 +274,48 @@ class GpuCompare:
         try:
             self._ok(self.L.fhe_decrypt_packed_batch(self.ctx, bufs[0], count, mode, bufs[1], None))
             return self._to_host(bufs[1], count)
+        finally:
+            for d in bufs:
+                self.L.fhe_dev_free(self.ctx, d)
+
+    # ---- several queries of one key holder in one pass ---
+    def compare_queries(self, bodies: np.ndarray, id0s, mask_key, docs, q_w: np.ndarray, cst: int, Ts):
+        """Q seeded queries (bodies uint64 [Q, D], Q stream ids with disjoint
+        ranges [id0, id0 + D), one mask key) against a packed corpus:
+        (acc int64 [Q, B], below int64 [Q, B]); query q uses threshold Ts[q]."""
+        docs8, B, D = docs
+        bodies = np.ascontiguousarray(bodies, np.uint64).reshape(-1, D)
+        Q = bodies.shape[0]
+        hT = np.ascontiguousarray([int(t) for t in Ts], np.int64)
+        bufs = [self._to_dev(bodies), self._to_dev(np.asarray(id0s, np.uint64).reshape(Q)),
+                self._to_dev(np.asarray(q_w, np.int64)), self._alloc(8 * Q * B), self._alloc(8 * Q * B)]
+        try:
+            mk = (C.c_uint32 * 8)(*[int(x) for x in mask_key])
+            self._ok(self.L.fhe_compare_queries_batch(self.ctx, bufs[0], bufs[1], mk, Q, docs8, B, D, bufs[2],
+                                                      int(cst), hT.ctypes.data, bufs[3], bufs[4], None))
+            return self._to_host(bufs[3], Q * B).reshape(Q, B), self._to_host(bufs[4], Q * B).reshape(Q, B)
+        finally:
+            for d in bufs:
+                self.L.fhe_dev_free(self.ctx, d)
+
+    def search_queries(self, bodies: np.ndarray, id0s, mask_key, docs, q_w: np.ndarray, cst: int, Ts,
+                       levels_bit: int = 0):
+        """Server side without decryption for Q queries: (glwe_acc, glwe_bit)
+        uint64 host arrays of ceil(Q B / N) * (k+1) * N words each; result
+        (q, b) is coefficient (q B + b) mod N of GLWE (q B + b) / N."""
+        docs8, B, D = docs
+        bodies = np.ascontiguousarray(bodies, np.uint64).reshape(-1, D)
+        Q = bodies.shape[0]
+        hT = np.ascontiguousarray([int(t) for t in Ts], np.int64)
+        words = -(-(Q * B) // self.P.N) * (self.P.k + 1) * self.P.N
+        bufs = [self._to_dev(bodies), self._to_dev(np.asarray(id0s, np.uint64).reshape(Q)),
+                self._to_dev(np.asarray(q_w, np.int64)), self._alloc(8 * words), self._alloc(8 * words)]
+        try:
+            mk = (C.c_uint32 * 8)(*[int(x) for x in mask_key])
+            self._ok(self.L.fhe_search_queries_batch(self.ctx, bufs[0], bufs[1], mk, Q, docs8, B, D, bufs[2],
+                                                     int(cst), hT.ctypes.data, int(levels_bit), bufs[3], bufs[4],
+                                                     None))
+            return self._to_host(bufs[3], words).view(np.uint64), self._to_host(bufs[4], words).view(np.uint64)
         finally:
             for d in bufs:
                 self.L.fhe_dev_free(self.ctx, d)

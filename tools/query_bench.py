@@ -30,6 +30,13 @@ sign extraction, both decryptions) interleaved step by step, in alternating
 order, with fhe_compare_query_batch on the same context, the "linear_ggsw"
 profile bucket per compare, and the parity of the two results.
 
+With --multi-query (docs/AB_LOG_r11.md) it measures several
+queries in one batched call, two-party, at 16 dimensions, n_bits 6 (P0 = 21):
+QueryServer.search_many with Q = 8, B = 128 against eight sequential
+QueryServer.search calls at B = 128 and one at B = 1024, 24 steps after 4
+warm-up in rotating order, with the "linear_query" and "blind_rotate"
+buckets and the reply bytes of each; it writes profiles/r11/multi_query.json.
+
 The floor of the leveled step is its output, B * (kN + 1) * 8 bytes, over the
 6.29 TB/s a float4 copy reaches on the MI355X; `floor_fraction` is that floor
 over the measured time. Prints one JSON line and writes it to --out.
@@ -193,6 +200,85 @@ def two_party(cq, oq, B: int, D: int, n_bits: int, steps: int, warmup: int) -> d
     return out
 
 
+def multi_query(cq, oq, D: int, n_bits: int, steps: int, warmup: int, Qn: int = 8, B: int = 128,
+                B_full: int = 1024) -> dict:
+    """Two-party, one process, three things interleaved in rotating order:
+    (a) QueryServer.search_many with Qn queries against B documents, (b) Qn
+    sequential QueryServer.search calls against the same B documents, (c) one
+    QueryServer.search against B_full = Qn * B documents (the same ciphertext
+    count as (a)). Host clock around each (reply copies included), the
+    "linear_query" and "blind_rotate" profile buckets per run, reply bytes,
+    and the parity of (a)'s decrypted reply with (b)'s and the restatement."""
+    import numpy as np
+    import torch
+    from oracle import quant_ref as Q
+    from fheicp.corpus import EncryptedCorpus
+    from fheicp.query import QueryClient, QueryServer
+    assert Qn * B == B_full
+    c = EncryptedCorpus(cq).compile(key_seed=5, device=0, noise_seed=6)
+    client = QueryClient(c, count=B_full, pack_seed=17)
+    server = QueryServer(client.eval_keys(), cq, c.P0)
+    eng = server.engine
+    _, docs = Q.make_corpus(D, B_full, seed=21)
+    qs = np.stack([Q.make_corpus(D, 1, seed=100 + i)[0] for i in range(Qn)])
+    docs8_small, docs8_full = server.pack_docs(docs[:B]), server.pack_docs(docs)
+    payloads = client.encrypt_queries(qs)
+    eng.profile(True)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        sec = time.perf_counter() - t0
+        return sec, out, eng.profile_read("linear_query"), eng.profile_read("blind_rotate")
+
+    runs = {"a": lambda: server.search_many(payloads, docs8_small, B, 0.5),
+            "b": lambda: [server.search(p, docs8_small, B, 0.5) for p in payloads],
+            "c": lambda: server.search(payloads[0], docs8_full, B_full, 0.5)}
+    orders = ("abc", "cba", "bca", "acb", "cab", "bac")
+    t = {k: [] for k in runs}
+    lq = {k: [] for k in runs}
+    br = {k: [] for k in runs}
+    last = {}
+    for i in range(warmup + steps):
+        for k in orders[i % len(orders)]:
+            sec, out, r_lq, r_br = timed(runs[k])
+            last[k] = (out, r_lq, r_br)
+            if i >= warmup:
+                t[k].append(sec)
+                lq[k].append(r_lq["total_ms"])
+                br[k].append(r_br["total_ms"])
+    eng.profile(False)
+    assert last["a"][1]["launches"] == 1 and last["b"][1]["launches"] == Qn and last["c"][1]["launches"] == 1
+    acc_a, below_a = client.decrypt_replies(last["a"][0])
+    singles = [client.decrypt_reply(r) for r in last["b"][0]]
+    parity = bool(all(torch.equal(acc_a[q], s[0]) and torch.equal(below_a[q], s[1]) for q, s in enumerate(singles)))
+    ref = np.stack([Q.corpus_accumulate(oq, cq.s_e, n_bits, q, docs[:B]) for q in qs])
+    scores = np.float64(Q.corpus_out_scale(oq, cq.s_e)) * ref.astype(np.float64)
+    exact = bool(np.array_equal(acc_a.cpu().numpy(), ref) and
+                 np.array_equal(below_a.cpu().numpy(), (scores < 0.5).astype(np.int64)))
+    med = {k: statistics.median(v) * 1e3 for k, v in t.items()}
+    out = {"Q": Qn, "B": B, "B_full": B_full,
+           "a_search_many_ms": med["a"], "a_min_ms": min(t["a"]) * 1e3,
+           "b_sequential_searches_ms": med["b"], "b_min_ms": min(t["b"]) * 1e3, "b_per_search_ms": med["b"] / Qn,
+           "c_full_search_ms": med["c"], "c_min_ms": min(t["c"]) * 1e3,
+           "ratio_a_over_c": med["a"] / med["c"], "meets_bar_a_over_c": med["a"] <= 1.10 * med["c"],
+           "ratio_a_over_b": med["a"] / med["b"], "meets_bar_a_over_b": med["a"] <= 0.5 * med["b"],
+           "small_search_over_full_search": med["b"] / Qn / med["c"],
+           "linear_query_ms": {k: statistics.median(v) for k, v in lq.items()},
+           "linear_query_kernel_last": eng.kernel_name("linear_query"),
+           "blind_rotate_ms": {k: statistics.median(v) for k, v in br.items()},
+           "blind_rotate_launches": {k: last[k][2]["launches"] for k in runs},
+           "reply_bytes": {"a": int(sum(r.nbytes for r in last["a"][0])),
+                           "b": int(sum(r.nbytes for r in last["b"][0])), "c": int(last["c"][0].nbytes)},
+           "parity_with_sequential": parity, "bit_exact": exact, "steps": steps, "warmup": warmup}
+    out["meets_bar"] = out["meets_bar_a_over_c"] and out["meets_bar_a_over_b"]
+    server.engine.close()
+    c.engine.close()
+    return out
+
+
 def both_private(cq, oq, B: int, D: int, n_bits: int, steps: int, warmup: int) -> dict:
     """fhe_compare_ggsw_batch against fhe_compare_query_batch on one context,
     interleaved in alternating order."""
@@ -279,8 +365,15 @@ def main() -> int:
     ap.add_argument("--both-private", action="store_true",
                     help="the both-private compare (GGSW query, GLWE documents) against the private-query "
                          "compare, --launches interleaved steps after --warmup")
-    ap.add_argument("--out", default=str(REPO / "profiles" / "query_bench.json"))
+    ap.add_argument("--multi-query", action="store_true",
+                    help="several queries in one batched call (16-dim, n_bits 6, two-party): search_many with "
+                         "Q = 8, B = 128 against eight sequential searches and one B = 1024 search, 24 "
+                         "interleaved steps after 4 warm-up; writes profiles/r11/multi_query.json")
+    ap.add_argument("--out", default=None, help="default profiles/query_bench.json "
+                                                "(--multi-query: profiles/r11/multi_query.json)")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = str(REPO / "profiles" / ("r11/multi_query.json" if a.multi_query else "query_bench.json"))
     if a.launches < 20:
         ap.error("--launches must be >= 20 (the medians compared are of at least 20 launches)")
     import torch
@@ -289,6 +382,16 @@ def main() -> int:
         return 2
     from fheicp.engine import Engine
     from fheicp.params import params_for_bits
+    if a.multi_query:
+        cq, oq = corpus_quant(16, 6)
+        mq = multi_query(cq, oq, 16, 6, steps=24, warmup=4)
+        res = {"bench": "query_bench --multi-query", "device": torch.cuda.get_device_name(0), "D": 16, "n_bits": 6,
+               "P0": cq.worst_msg_bits(), "multi_query": mq, "meets_bar": mq["meets_bar"]}
+        line = json.dumps(res)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(line + "\n")
+        print(line)
+        return 0
     shapes = []
     for D in a.dims:
         for nb in a.n_bits:
