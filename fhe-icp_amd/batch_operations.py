@@ -521,9 +521,16 @@ class BatchProcessor:
         """[search_vector(q, top_k, min_similarity) for q in queries]. With
         encrypt_query on one rank the queries are encrypted together and
         scored in one batched pass per document chunk (fheicp.query
-        compare_many), then one top-k per query; every other mode, and a
+        compare_many), then one top-k per query; a ciphertext store
+        (store_ciphertexts, fhe="execute") on one rank likewise scores all
+        queries in one batched pass per search_chunk
+        (EncryptedCorpus.compare_many); every other mode, and a
         torch.distributed group, loops over search_vector."""
         queries = [np.asarray(q) for q in queries]
+        if (queries and self.config.store_ciphertexts and self.config.fhe == "execute" and _world()[0] == 1
+                and self.storage.holds_ciphertexts()):
+            self._require_model()
+            return self._search_ciphertexts_many(queries, top_k, min_similarity)
         if not queries or not self.config.encrypt_query or _world()[0] > 1 or self.storage.holds_ciphertexts():
             return [self.search_vector(q, top_k, min_similarity) for q in queries]
         self._require_model()
@@ -565,12 +572,7 @@ class BatchProcessor:
         n = len(ids)
         lo, hi = rank * n // world, (rank + 1) * n // world
         eng = c.engine
-        r = self._resident_ct
-        if r is None or r[0] is not bodies or r[1] != (lo, hi):
-            r = self._resident_ct = (bodies, (lo, hi), (
-                torch.from_numpy(np.ascontiguousarray(bodies[lo:hi]).view(np.int64)).to(eng.device),
-                torch.from_numpy(np.ascontiguousarray(id0[lo:hi]).view(np.int64)).to(eng.device)))
-        bd, idd = r[2]
+        bd, idd = self._resident_ciphertexts(bodies, id0, lo, hi)
         accs, belows = [], []
         for s in range(0, hi - lo, self.config.search_chunk):
             e = min(hi - lo, s + self.config.search_chunk)
@@ -587,6 +589,57 @@ class BatchProcessor:
         s = np.float64(c.cq.out_scale)
         hits = [(ids[int(i)], float(s * np.float64(a))) for a, i in zip(oa, oi) if i >= 0]
         return hits[:top_k]
+
+    def _resident_ciphertexts(self, bodies, id0, lo: int, hi: int):
+        """The device-resident bodies and stream ids of documents [lo, hi),
+        re-uploaded when the store changes."""
+        import torch
+        dev = self.corpus_engine.engine.device
+        r = self._resident_ct
+        if r is None or r[0] is not bodies or r[1] != (lo, hi):
+            r = self._resident_ct = (bodies, (lo, hi), (
+                torch.from_numpy(np.ascontiguousarray(bodies[lo:hi]).view(np.int64)).to(dev),
+                torch.from_numpy(np.ascontiguousarray(id0[lo:hi]).view(np.int64)).to(dev)))
+        return r[2]
+
+    def _search_ciphertexts_many(self, queries, top_k: int, t: float) -> List[List[Tuple[str, float]]]:
+        """_search_ciphertexts for several queries on one rank: one batched
+        compare per search_chunk of the resident corpus
+        (EncryptedCorpus.compare_many), one top-k per query segment."""
+        import torch
+        from fheicp.search import sharded_topk
+        c = self.corpus_engine
+        if c is None:
+            raise RuntimeError("ciphertext documents need BatchConfig(store_ciphertexts=True, fhe='execute')")
+        ids, bodies, id0, head = self.storage.encrypted_corpus()
+        if not ids:
+            return [[] for _ in queries]
+        c.check_payload(head)
+        for q in queries:
+            if q.shape != (bodies.shape[1],):
+                raise ValueError(f"query shape {q.shape} does not match corpus width {bodies.shape[1]}")
+        k = len(ids) if top_k < 0 else min(int(top_k), len(ids))
+        if k == 0:
+            return [[] for _ in queries]
+        n = len(ids)
+        eng = c.engine
+        bd, idd = self._resident_ciphertexts(bodies, id0, 0, n)
+        qs = np.stack(queries)
+        accs, belows = [], []
+        for s in range(0, n, self.config.search_chunk):
+            e = min(n, s + self.config.search_chunk)
+            acc, below, _ = c.compare_many(bd[s:e], idd[s:e], qs, t)
+            accs.append(acc)
+            belows.append(below)
+        acc, below = torch.cat(accs, dim=1), torch.cat(belows, dim=1)
+        sc = np.float64(c.cq.out_scale)
+        out = []
+        for q in range(len(queries)):
+            oa, oi = sharded_topk(acc[q].contiguous(), below[q].contiguous(), k, 0,
+                                  lambda a, b, kk, base: eng.topk(a, b, kk, base), 1)
+            oa, oi = oa.cpu().numpy(), oi.cpu().numpy()
+            out.append([(ids[int(i)], float(sc * np.float64(a))) for a, i in zip(oa, oi) if i >= 0][:top_k])
+        return out
 
     def _search_private_query(self, query, E, k: int, t: float):
         """The private-query search (fheicp.query): the client side encrypts

@@ -78,6 +78,9 @@ struct fhe_ctx {
   ProfAcc prof_lq;                        // private-query leveled step: k_query_planes + k_linear_query_mfma
   void* lq_ws = nullptr;                  // its query byte planes (grown on demand)
   size_t lq_ws_bytes = 0;
+  ProfAcc prof_ls;                        // stored-ciphertext leveled step, batched: k_linear_seeded_queries
+  void* lsq_cst = nullptr;                // fhe_linear_seeded_queries_batch's Q scaled constants (grown on demand)
+  size_t lsq_cst_words = 0;
   int br_variant = 4;  // N=1024 blind rotation: 4 = a wave per GLWE component (k = 2, default), 2
                        // (two waves per ciphertext; forced by FHEICP_BR_VARIANT=2)
   // A/B builds only (FHEICP_AB, tools/build_variant.sh): other v4 shapes
@@ -556,7 +559,7 @@ void fhe_ctx_destroy(fhe_ctx* ctx) {
                       (void*)ctx->bskf[4], (void*)ctx->bskf_fft[4],
                       (void*)ctx->ksk8, (void*)ctx->ks_ws, (void*)ctx->ks_ws1, (void*)ctx->tw4, (void*)ctx->bsk_fft_v2,
                       (void*)ctx->psi, (void*)ctx->mb_msg, ctx->lq_ws, (void*)ctx->pk, (void*)ctx->pk8,
-                      ctx->pack_ws, ctx->xp_ws})
+                      ctx->pack_ws, ctx->xp_ws, ctx->lsq_cst})
       (void)hipFree(ptr);
     for (hipStream_t s : ctx->lane_st)
       if (s) (void)hipStreamDestroy(s);
@@ -567,6 +570,7 @@ void fhe_ctx_destroy(fhe_ctx* ctx) {
     free_ev(ctx->prof_ks);
     free_ev(ctx->prof_enc);
     free_ev(ctx->prof_lq);
+    free_ev(ctx->prof_ls);
     free_ev(ctx->prof_pack);
     free_ev(ctx->prof_xp);
   }
@@ -2405,6 +2409,22 @@ int fhe_search_query_batch(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0, 
   return post_leveled_search(ctx, w, B, levels_bit, d_glwe_acc, d_glwe_bit, stream);
 }
 
+// post_leveled_compare over the Q B query-major ciphertexts of a batch, with
+// query q's own threshold (d_T[q], device) added back: shared by the
+// private-query (§8.8) and the stored-ciphertext (§8.9) batched entries.
+static int post_leveled_compare_queries(fhe_ctx* ctx, const QueryWs& w, int64_t Q, int64_t B, const int64_t* d_T,
+                                        int64_t* d_acc, int64_t* d_below, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n = Q * B;
+  int rc;
+  if ((rc = fhe_decrypt_batch(ctx, w.ctv, n, w.v, stream))) return rc;
+  if ((rc = sign_extract_batch(ctx, w.ctv, n, w.sgn, w.small, st))) return rc;
+  if ((rc = fhe_decrypt_bits_batch(ctx, w.sgn, n, d_below, stream))) return rc;
+  hipLaunchKernelGGL(k_add_query_scalar, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w.v, n, B, d_T, d_acc);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
 // Q queries of one key holder in one pass: the workspace of
 // query_leveled for Q B results with, in the query's place, the Q D expanded
 // ciphertexts and the Q thresholds; one expansion (k_expand_seeded's B = Q),
@@ -2434,19 +2454,11 @@ int fhe_compare_queries_batch(fhe_ctx* ctx, const uint64_t* d_qbody, const uint6
   if ((rc = need_secret(ctx))) return rc;
   if (!h_mask_key || !h_T || !d_qbody || !d_id0 || !d_docs8 || !d_w || !d_acc || !d_below)
     return fail(ctx, FHE_E_ARG, "null compare queries arguments");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t n = Q * B;
   QueryWs w;
   int64_t* d_T;
   rc = queries_leveled(ctx, d_qbody, d_id0, h_mask_key, Q, d_docs8, B, D, d_w, cst, h_T, false, &w, &d_T, stream);
   if (rc) return rc;
-  // post_leveled_compare with query q's own threshold added back
-  if ((rc = fhe_decrypt_batch(ctx, w.ctv, n, w.v, stream))) return rc;
-  if ((rc = sign_extract_batch(ctx, w.ctv, n, w.sgn, w.small, st))) return rc;
-  if ((rc = fhe_decrypt_bits_batch(ctx, w.sgn, n, d_below, stream))) return rc;
-  hipLaunchKernelGGL(k_add_query_scalar, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w.v, n, B, d_T, d_acc);
-  HIPCHK(ctx, hipGetLastError());
-  return FHE_OK;
+  return post_leveled_compare_queries(ctx, w, Q, B, d_T, d_acc, d_below, stream);
 }
 
 int fhe_search_queries_batch(fhe_ctx* ctx, const uint64_t* d_qbody, const uint64_t* d_id0,
@@ -2469,6 +2481,120 @@ int fhe_search_queries_batch(fhe_ctx* ctx, const uint64_t* d_qbody, const uint64
   if (rc) return rc;
   // result q B + b is ciphertext q B + b of the batch: coefficient (q B + b) mod N
   // of GLWE (q B + b) / N
+  return post_leveled_search(ctx, w, Q * B, levels_bit, d_glwe_acc, d_glwe_bit, stream);
+}
+
+// ---- stored-ciphertext search: Q clear queries in one pass --
+static int seeded_queries_args(fhe_ctx* ctx, int64_t Q, int64_t B, int32_t D) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  if (Q < 1 || B < 1 || D < 1) return fail(ctx, FHE_E_ARG, "bad seeded queries arguments (Q < 1, B < 1 or D < 1)");
+  // the query tile is a grid dimension of the leveled launch
+  if (Q > 65535) return fail(ctx, FHE_E_ARG, "seeded queries batch Q > 65535: split the call");
+  if (B > 0x7fffffffLL || B * (int64_t)D > 0x7fffffffLL)
+    return fail(ctx, FHE_E_ARG, "seeded queries corpus batch too large (B*D >= 2^31)");
+  if (Q * B > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "seeded queries result count too large (Q*B >= 2^31)");
+  return FHE_OK;
+}
+// the leveled launch: d_cst holds the Q scaled constants on the device
+static int linear_seeded_queries_launch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t B,
+                                        int32_t D, const uint32_t h_mask_key[8], int64_t Q, const int64_t* d_W,
+                                        const u64* d_cst, uint64_t* d_out, hipStream_t st) {
+  const fhe_params& p = ctx->p;
+  ChaKey Km;
+  for (int i = 0; i < 8; ++i) Km.w[i] = h_mask_key[i];
+  constexpr int QT = FHEICP_LSQ_QT;
+  hipEvent_t e1;
+  prof_begin(ctx, ctx->prof_ls, st, &e1);
+  ctx->prof_ls.kernel = "k_linear_seeded_queries";
+  hipLaunchKernelGGL(k_linear_seeded_queries<QT>, dim3((unsigned)B, (unsigned)((Q + QT - 1) / QT)), dim3(256), 0, st,
+                     Km, p.k * p.N, d_body, d_id0, (int)D, (int)Q, d_W, d_cst, d_out);
+  prof_end(ctx, ctx->prof_ls, st, e1, Q * B);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+// h_cst[q] (minus h_T[q] when given) scaled to the encoding, to d_cst through k_store_words
+static int store_scaled_csts(fhe_ctx* ctx, u64* d_cst, int64_t Q, const int64_t* h_cst, int64_t cst,
+                             const int64_t* h_T, hipStream_t st) {
+  std::vector<u64> cs((size_t)Q);
+  for (int64_t q = 0; q < Q; ++q)
+    cs[(size_t)q] = (u64)(h_cst ? h_cst[q] : cst - h_T[q]) << (64 - ctx->p.msg_bits);
+  return store_words(ctx, d_cst, cs.data(), Q, st);
+}
+
+int fhe_linear_seeded_queries_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t B, int32_t D,
+                                    const uint32_t h_mask_key[8], int64_t Q, const int64_t* d_W,
+                                    const int64_t* h_cst, uint64_t* d_out, void* stream) {
+  int rc = seeded_queries_args(ctx, Q, B, D);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  if (!d_body || !d_id0 || !h_mask_key || !d_W || !h_cst || !d_out)
+    return fail(ctx, FHE_E_ARG, "null linear seeded queries arguments");
+  if ((rc = need_device(ctx))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((size_t)Q > ctx->lsq_cst_words) {
+    if (ctx->lsq_cst) {
+      HIPCHK(ctx, hipDeviceSynchronize());
+      HIPCHK(ctx, hipFree(ctx->lsq_cst));
+      ctx->lsq_cst = nullptr;
+      ctx->lsq_cst_words = 0;
+    }
+    HIPCHK(ctx, hipMalloc(&ctx->lsq_cst, 8 * (size_t)Q));
+    ctx->lsq_cst_words = (size_t)Q;
+  }
+  if ((rc = store_scaled_csts(ctx, (u64*)ctx->lsq_cst, Q, h_cst, 0, nullptr, st))) return rc;
+  return linear_seeded_queries_launch(ctx, d_body, d_id0, B, D, h_mask_key, Q, d_W, (const u64*)ctx->lsq_cst, d_out,
+                                      st);
+}
+
+// The leveled part of the compare and search entries: the workspace of the
+// §8.8 entries for Q B results with, in the query's place, the Q thresholds
+// and the Q scaled constants cst - T_q; one launch into ct_v (query-major).
+static int seeded_queries_leveled(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t B, int32_t D,
+                                  const uint32_t h_mask_key[8], int64_t Q, const int64_t* d_W, int64_t cst,
+                                  const int64_t* h_T, bool keep_copy, QueryWs* w, int64_t** d_T, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  u64* ex;
+  int rc = leveled_ws(ctx, Q * B, 2 * (size_t)Q, keep_copy, w, &ex);
+  if (rc) return rc;
+  *d_T = (int64_t*)ex;
+  if ((rc = store_words(ctx, ex, (const u64*)h_T, Q, st))) return rc;
+  if ((rc = store_scaled_csts(ctx, ex + Q, Q, nullptr, cst, h_T, st))) return rc;
+  return linear_seeded_queries_launch(ctx, d_body, d_id0, B, D, h_mask_key, Q, d_W, ex + Q, w->ctv, st);
+}
+
+int fhe_compare_seeded_queries_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t B,
+                                     int32_t D, const uint32_t h_mask_key[8], int64_t Q, const int64_t* d_W,
+                                     int64_t cst, const int64_t* h_T, int64_t* d_acc, int64_t* d_below,
+                                     void* stream) {
+  int rc = seeded_queries_args(ctx, Q, B, D);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  if (!d_body || !d_id0 || !h_mask_key || !d_W || !h_T || !d_acc || !d_below)
+    return fail(ctx, FHE_E_ARG, "null compare seeded queries arguments");
+  if ((rc = need_secret(ctx))) return rc;
+  QueryWs w;
+  int64_t* d_T;
+  rc = seeded_queries_leveled(ctx, d_body, d_id0, B, D, h_mask_key, Q, d_W, cst, h_T, false, &w, &d_T, stream);
+  if (rc) return rc;
+  return post_leveled_compare_queries(ctx, w, Q, B, d_T, d_acc, d_below, stream);
+}
+
+int fhe_search_seeded_queries_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t B,
+                                    int32_t D, const uint32_t h_mask_key[8], int64_t Q, const int64_t* d_W,
+                                    int64_t cst, const int64_t* h_T, int32_t levels_bit, uint64_t* d_glwe_acc,
+                                    uint64_t* d_glwe_bit, void* stream) {
+  int rc = seeded_queries_args(ctx, Q, B, D);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  if (levels_bit < 0 || levels_bit > 8)
+    return fail(ctx, FHE_E_ARG, "bad search seeded queries arguments (levels_bit outside [0, 8])");
+  if (!d_body || !d_id0 || !h_mask_key || !d_W || !h_T || !d_glwe_acc || !d_glwe_bit)
+    return fail(ctx, FHE_E_ARG, "null search seeded queries arguments");
+  if ((rc = need_eval_keys(ctx))) return rc;
+  if ((rc = need_pack_key(ctx))) return rc;
+  if (levels_bit > ctx->pk_level)
+    return fail(ctx, FHE_E_ARG, "search seeded queries levels_bit exceeds the packing key's levels");
+  QueryWs w;
+  int64_t* d_T;
+  rc = seeded_queries_leveled(ctx, d_body, d_id0, B, D, h_mask_key, Q, d_W, cst, h_T, true, &w, &d_T, stream);
+  if (rc) return rc;
   return post_leveled_search(ctx, w, Q * B, levels_bit, d_glwe_acc, d_glwe_bit, stream);
 }
 
@@ -2849,6 +2975,7 @@ static ProfAcc* prof_bucket(fhe_ctx* ctx, const char* kernel) {
   if (!strcmp(kernel, "keyswitch")) return &ctx->prof_ks;
   if (!strcmp(kernel, "encrypt_linear")) return &ctx->prof_enc;
   if (!strcmp(kernel, "linear_query")) return &ctx->prof_lq;
+  if (!strcmp(kernel, "linear_seeded")) return &ctx->prof_ls;
   if (!strcmp(kernel, "pack")) return &ctx->prof_pack;
   if (!strcmp(kernel, "linear_ggsw")) return &ctx->prof_xp;
   return nullptr;

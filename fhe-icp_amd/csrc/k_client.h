@@ -555,6 +555,64 @@ __global__ void __launch_bounds__(256) k_linear_seeded(ChaKey Km, int dim, const
   }
 }
 
+// k_linear_seeded for Q weight rows over the same corpus:
+// out[q B + b] = sum_j W[q][j] * ct(b, j) + cst_scaled[q], query-major. One
+// workgroup per (document: grid x, tile of QT queries: grid y); a thread owns
+// one 8-word mask block as above, generates it ONCE per feature and applies
+// the tile's QT weights to it, so Q queries cost ceil(Q / QT) ChaCha passes
+// instead of Q. acc is QT x 8 words, every index static (registers, no
+// scratch). The weights are wave-uniform: row pointers and loads are scalar.
+// Tail tile: a row q >= Q reads row Q - 1's weights (never past W) and is not
+// stored. At Q = 1 the words are k_linear_seeded's.
+#ifndef FHEICP_LSQ_QT
+#define FHEICP_LSQ_QT 8
+#endif
+template <int QT>
+__global__ void __launch_bounds__(256) k_linear_seeded_queries(ChaKey Km, int dim, const u64* __restrict__ body,
+                                                               const u64* __restrict__ id0, int D, int Q,
+                                                               const int64_t* __restrict__ W,
+                                                               const u64* __restrict__ cst_scaled,
+                                                               u64* __restrict__ out) {
+  const int64_t b = blockIdx.x, B = gridDim.x;
+  const int q0 = (int)blockIdx.y * QT;
+  const u64 base = id0[b];
+  const int64_t* wr[QT];
+#pragma unroll
+  for (int t = 0; t < QT; ++t) wr[t] = W + (size_t)(q0 + t < Q ? q0 + t : Q - 1) * D;
+  for (int blk = threadIdx.x; blk < dim / 8; blk += 256) {
+    u64 acc[QT][8];
+#pragma unroll
+    for (int t = 0; t < QT; ++t)
+#pragma unroll
+      for (int q = 0; q < 8; ++q) acc[t][q] = 0;
+    for (int j = 0; j < D; ++j) {
+      u64 m[8];
+      stream_block(Km, TAG_ENC_MASK, base + (u64)j, (uint32_t)blk, m);
+#pragma unroll
+      for (int t = 0; t < QT; ++t) {
+        const u64 wj = (u64)wr[t][j];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc[t][q] += wj * m[q];
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < QT; ++t)
+      if (q0 + t < Q) {
+        u64* o = out + ((size_t)(q0 + t) * B + b) * (dim + 1);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) o[8 * blk + q] = acc[t][q];
+      }
+  }
+  // the bodies: lane t of the first wave takes query q0 + t
+  if (threadIdx.x < QT && q0 + (int)threadIdx.x < Q) {
+    const int qi = q0 + (int)threadIdx.x;
+    const int64_t* w = W + (size_t)qi * D;
+    u64 acc = cst_scaled[qi];
+    for (int j = 0; j < D; ++j) acc += (u64)w[j] * body[(size_t)b * D + j];
+    out[((size_t)qi * B + b) * (dim + 1) + dim] = acc;
+  }
+}
+
 // The rotation exponent a blind rotation will apply to small LWE c, i.e. its
 // phase modulus-switched to 2N exactly as the rotation rounds it (measurement
 // only: it reads the small secret key, like k_decrypt): phi = b~ - sum a~_S

@@ -27,6 +27,10 @@ parity bar for this mode is bit-exactness against its restatement
 (oracle/quant_ref.py, ``corpus_*``), checked on the GPU in
 tests/test_gpu_corpus.py.
 
+Several clear queries against the same stored documents go through in one
+pass: plan_many / compare_many here, and for two parties
+(a host with evaluation keys only) fheicp.stored.
+
 Stored payload (EncryptedDocument with ``model_version == PAYLOAD_VERSION``):
 ``encrypted_embedding`` is a uint64 vector
     [MAGIC, 1, D, P0, id0, mask key (4 words), k*N, body_0 .. body_{D-1}]
@@ -252,6 +256,50 @@ class EncryptedCorpus:
         eng.set_msg_bits(P)
         acc, below = eng.compare_seeded(body_dev, id_dev, self.mask_key, eng.to_dev(Wr), cst, T)
         return acc, below, P
+
+    # -------------------------------------------------- batches of queries --
+    def plan_many(self, queries, min_similarity=None):
+        """query_plan for a batch: (Wr int64 [Q, D], cst,
+        [T_q], P). P = max_q P_q is the batch's width and every row carries the
+        2^(P0 - P) rescale; T_q sits on query q's own [lo_q, hi_q + 1], so
+        acc - T_q fits P_q <= P bits. min_similarity: a float, None, or Q of
+        them."""
+        from .query import thresholds_for
+        queries = np.atleast_2d(np.asarray(queries))
+        Q = queries.shape[0]
+        if Q < 1:
+            raise ValueError("an empty batch of queries")
+        ts = thresholds_for(min_similarity, Q)
+        plans = [self.query_plan(queries[q], ts[q]) for q in range(Q)]
+        P = max(p[3] for p in plans)
+        # query_plan's row is W << (P0 - P_q): an exact arithmetic shift brings it to W << (P0 - P)
+        Wr = np.stack([p[0] >> np.int64(P - p[3]) for p in plans])
+        return Wr, self.cq.q_b, [int(p[2]) for p in plans], P
+
+    def compare_many(self, body_dev, id_dev, queries, min_similarity=None):
+        """Q clear queries against the same stored documents, one pass per
+        chunk of query.query_chunks(Q, B) (fhe_compare_seeded_queries_batch)
+        -> (acc int64 [Q, B], below int64 [Q, B]) device tensors and the
+        largest width used. Each chunk is planned on its own; decrypted values
+        do not depend on the width, so this equals Q calls of compare."""
+        import torch
+        from .query import query_chunks, thresholds_for
+        self._need()
+        eng = self.engine
+        queries = np.atleast_2d(np.asarray(queries))
+        Q, B = queries.shape[0], int(body_dev.shape[0])
+        ts = thresholds_for(min_similarity, Q)
+        accs, belows, Pmax = [], [], 0
+        for ch in query_chunks(Q, B):
+            Wr, cst, Ts, P = self.plan_many(queries[ch.start:ch.stop], [ts[q] for q in ch])
+            eng.set_msg_bits(P)
+            acc, below = eng.compare_seeded_queries(body_dev, id_dev, self.mask_key, eng.to_dev(Wr), cst, Ts)
+            accs.append(acc)
+            belows.append(below)
+            Pmax = max(Pmax, P)
+        if not accs:
+            raise ValueError("an empty batch of queries")
+        return torch.cat(accs), torch.cat(belows), Pmax
 
     def scores(self, acc) -> np.ndarray:
         return np.float64(self.cq.out_scale) * np.asarray(acc, dtype=np.float64)

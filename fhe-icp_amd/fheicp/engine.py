@@ -560,6 +560,56 @@ class Engine:
                                                    int(levels_bit), _ptr(ga), _ptr(gb), _stream(self.device)))
         return ga, gb
 
+    # --------- stored-ciphertext search: several clear queries in one pass (§8.9) --
+    def linear_seeded_queries(self, body: torch.Tensor, id0: torch.Tensor, mask_key, W, csts,
+                              out: torch.Tensor | None = None) -> torch.Tensor:
+        """fhe_linear_seeded_queries_batch: body [B, D], id0 [B], W int64
+        [Q, D], csts Q host constants; Q * B x (kN+1), query-major."""
+        B, D = body.shape
+        Wd = self.to_dev(W).reshape(-1, D).contiguous()
+        Q = Wd.shape[0]
+        keep, hc = self._i64s(csts)
+        if keep.size != Q:
+            raise ValueError(f"{keep.size} constants for {Q} queries")
+        if out is None:
+            out = self.empty_big(Q * B)
+        self._chk(self._L.fhe_linear_seeded_queries_batch(self._ctx, _ptr(body), _ptr(id0), int(B), int(D),
+                                                          self._key(mask_key), int(Q), _ptr(Wd), hc, _ptr(out),
+                                                          _stream(self.device)))
+        return out
+
+    def compare_seeded_queries(self, body: torch.Tensor, id0: torch.Tensor, mask_key, W: torch.Tensor, cst: int, Ts):
+        """fhe_compare_seeded_queries_batch: W int64 [Q, D] (device), Ts Q host
+        thresholds; (acc int64 [Q, B], below int64 [Q, B])."""
+        B, D = body.shape
+        keep, hT = self._i64s(Ts)
+        Q = keep.size
+        if tuple(W.shape) != (Q, D):
+            raise ValueError(f"weights {tuple(W.shape)} for {Q} thresholds of {D} features")
+        acc = torch.empty((Q, B), dtype=torch.int64, device=self.device)
+        below = torch.empty((Q, B), dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_compare_seeded_queries_batch(self._ctx, _ptr(body), _ptr(id0), int(B), int(D),
+                                                           self._key(mask_key), Q, _ptr(W), int(cst), hT, _ptr(acc),
+                                                           _ptr(below), _stream(self.device)))
+        return acc, below
+
+    def search_seeded_queries(self, body: torch.Tensor, id0: torch.Tensor, mask_key, W: torch.Tensor, cst: int, Ts,
+                              levels_bit: int = 0):
+        """fhe_search_seeded_queries_batch: the evaluation-only form;
+        (glwe_acc, glwe_bit), each ceil(Q B / N) x (k+1)N words."""
+        B, D = body.shape
+        keep, hT = self._i64s(Ts)
+        Q = keep.size
+        if tuple(W.shape) != (Q, D):
+            raise ValueError(f"weights {tuple(W.shape)} for {Q} thresholds of {D} features")
+        shape = (self.glwe_count(Q * B), (self.params.k + 1) * self.params.N)
+        ga = torch.empty(shape, dtype=torch.int64, device=self.device)
+        gb = torch.empty(shape, dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_search_seeded_queries_batch(self._ctx, _ptr(body), _ptr(id0), int(B), int(D),
+                                                          self._key(mask_key), Q, _ptr(W), int(cst), hT,
+                                                          int(levels_bit), _ptr(ga), _ptr(gb), _stream(self.device)))
+        return ga, gb
+
     # ------------- both-private search: GGSW query x GLWE documents (§8.7) --
     def ggsw_words(self, base_log: int, level: int) -> int:
         return self._L.fhe_ggsw_words(C.byref(self._P), int(base_log), int(level))

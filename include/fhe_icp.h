@@ -563,9 +563,11 @@ int fhe_stream_sync(fhe_ctx* ctx, void* stream);
  * "blind_rotate_mid", "blind_rotate_mid2", "blind_rotate_mid0", "keyswitch", "encrypt_linear"
  * (the fused client encryption + leveled dot), "linear_query" (the
  * private-query leveled step: query planes + GEMM, one bracket around both)
- * "pack" (the packing key switch: digits + GEMM + rotation, one bracket) or
+ * "pack" (the packing key switch: digits + GEMM + rotation, one bracket),
  * "linear_ggsw" (the both-private leveled step: Toeplitz planes + GEMM +
- * slot extraction, one bracket), then resets what it read. */
+ * slot extraction, one bracket) or "linear_seeded" (the stored-ciphertext
+ * leveled step of the batched entries, k_linear_seeded_queries), then resets
+ * what it read. */
 int fhe_profile_enable(fhe_ctx* ctx, int enable);
 int fhe_profile_read(fhe_ctx* ctx, const char* kernel, double* total_ms, int64_t* launches, int64_t* items);
 /* The kernel last launched for that bucket, as rocprofv3 names it (e.g.
@@ -611,6 +613,37 @@ int fhe_search_queries_batch(fhe_ctx* ctx, const uint64_t* d_qbody, const uint64
                              const uint32_t h_mask_key[8], int64_t Q, const void* d_docs8, int64_t B, int32_t D,
                              const int64_t* d_w, int64_t cst, const int64_t* h_T, int32_t levels_bit,
                              uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream);
+
+/* ---- stored-ciphertext search: several queries in one pass -
+ * Q CLEAR queries against the same B documents stored as seeded LWEs
+ * (fhe_encrypt_seeded_batch: d_body B x D, d_id0 B stream ids, the public mask
+ * key). Every mask block is regenerated once and meets the Q weight rows in
+ * registers. Results are query-major (row / element q * B + b). Q >= 1,
+ * B >= 1, D >= 1, Q <= 65535, B * D < 2^31, Q * B < 2^31, no null pointers:
+ * otherwise FHE_E_ARG ("seeded queries ..." in fhe_last_error), reported before
+ * the device and key checks; missing keys return FHE_E_STATE.
+ *
+ * The leveled step alone; needs no keys. d_W: Q x D (row-major, the caller has
+ * folded 2^(P0-P) in), h_cst: Q host constants, d_out: Q*B x (kN+1):
+ *   out[q B + b] = sum_j d_W[q][j] * ct(b, j) + trivial(h_cst[q] * Delta).
+ * At Q = 1 word for word fhe_linear_seeded_batch. Timing goes to the
+ * "linear_seeded" profile bucket. */
+int fhe_linear_seeded_queries_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t B, int32_t D,
+                                    const uint32_t h_mask_key[8], int64_t Q, const int64_t* d_W,
+                                    const int64_t* h_cst, uint64_t* d_out, void* stream);
+/* fhe_compare_seeded_batch for Q weight rows: query q runs with cst - h_T[q];
+ * d_acc[q B + b], d_below[q B + b] = [acc < h_T[q]]. Needs the secret key. */
+int fhe_compare_seeded_queries_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t B,
+                                     int32_t D, const uint32_t h_mask_key[8], int64_t Q, const int64_t* d_W,
+                                     int64_t cst, const int64_t* h_T, int64_t* d_acc, int64_t* d_below,
+                                     void* stream);
+/* evaluation-only: no decryption; result q B + b in coefficient (q B + b) mod N of GLWE (q B + b) / N,
+ * ceil(Q B / N) GLWEs each for acc - h_T[q] (all levels) and the bits (levels_bit prefix; 0: all).
+ * Needs evaluation keys and the packing key, no secret. */
+int fhe_search_seeded_queries_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t B,
+                                    int32_t D, const uint32_t h_mask_key[8], int64_t Q, const int64_t* d_W,
+                                    int64_t cst, const int64_t* h_T, int32_t levels_bit, uint64_t* d_glwe_acc,
+                                    uint64_t* d_glwe_bit, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,12 @@ _PROTOS = {
                                             _vp]),
     "fhe_search_queries_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i32, _vp, _vp,
                                            _vp]),
+    # stored-ciphertext search, several clear queries in one pass
+    "fhe_linear_seeded_queries_batch": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "fhe_compare_seeded_queries_batch": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                                   _vp]),
+    "fhe_search_seeded_queries_batch": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _vp,
+                                                  _vp, _vp]),
     # both sides encrypted: GGSW query x GLWE documents
     "fhe_encrypt_packed_batch_key": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _u64, _vp, _vp]),
     "fhe_encrypt_packed_batch": (C.c_int, [_vp, _vp, _i64, _i32, _u64, _u64, _vp, _vp]),

@@ -37,6 +37,16 @@ QueryServer.search calls at B = 128 and one at B = 1024, 24 steps after 4
 warm-up in rotating order, with the "linear_query" and "blind_rotate"
 buckets and the reply bytes of each; it writes profiles/r11/multi_query.json.
 
+With --stored-queries (docs/AB_LOG_r12.md) it measures the
+stored-ciphertext search for several clear queries, two-party, at 16
+dimensions, n_bits 6 (P0 = 21): CorpusServer.search_many with Q = 8, B = 128
+against eight sequential CorpusServer.search calls at B = 128 and one
+EncryptedCorpus.compare at B = 1024, 24 steps after 4 warm-up in rotating
+order; then the "linear_seeded" bucket of the batched leveled step against
+HIP events around eight fhe_linear_seeded_batch calls on the same documents at
+B = 128 and B = 1024, with the outputs compared; it writes
+profiles/r12/stored_queries.json (--no-end-to-end: the leveled step only).
+
 The floor of the leveled step is its output, B * (kN + 1) * 8 bytes, over the
 6.29 TB/s a float4 copy reaches on the MI355X; `floor_fraction` is that floor
 over the measured time. Prints one JSON line and writes it to --out.
@@ -279,6 +289,131 @@ def multi_query(cq, oq, D: int, n_bits: int, steps: int, warmup: int, Qn: int = 
     return out
 
 
+def stored_leveled(eng, D: int, steps: int, warmup: int, Qn: int = 8, sizes=(128, 1024)) -> dict:
+    """The stored-ciphertext leveled step for Qn queries, per document count:
+    one fhe_linear_seeded_queries_batch (the "linear_seeded" bucket, and HIP
+    events around the call) against Qn fhe_linear_seeded_batch calls on the
+    same documents (HIP events around the Qn calls), interleaved in
+    alternating order; the outputs compared word for word. Needs no keys."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(5)
+    mk = np.arange(8, dtype=np.uint32) + 5
+    out = {}
+    eng.profile(True)
+    for B in sizes:
+        body = eng.to_dev(rng.integers(0, 2 ** 63, (B, D), dtype=np.int64))
+        ids = eng.to_dev(rng.integers(0, 2 ** 63, B, dtype=np.int64))
+        W = rng.integers(-(2 ** 20), 2 ** 20, (Qn, D), dtype=np.int64)
+        Wd, rows = eng.to_dev(W), [eng.to_dev(W[q]) for q in range(Qn)]
+        cst = list(range(Qn))
+        buf = eng.empty_big(Qn * B)
+
+        def ev(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = fn()
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1), r
+
+        runs = {"batched": lambda: eng.linear_seeded_queries(body, ids, mk, Wd, cst, out=buf),
+                "sequential": lambda: [eng.linear_seeded(body, ids, mk, rows[q], cst[q]) for q in range(Qn)]}
+        t = {k: [] for k in runs}
+        bucket, last = [], {}
+        for i in range(warmup + steps):
+            for k in (("batched", "sequential") if i % 2 else ("sequential", "batched")):
+                ms, last[k] = ev(runs[k])
+                if k == "batched":
+                    r = eng.profile_read("linear_seeded")
+                    assert r["launches"] == 1 and r["items"] == Qn * B
+                if i >= warmup:
+                    t[k].append(ms)
+                    if k == "batched":
+                        bucket.append(r["total_ms"])
+        equal = bool(torch.equal(last["batched"], torch.cat(last["sequential"])))
+        b_ms, s_ms = statistics.median(bucket), statistics.median(t["sequential"])
+        out[f"B{B}"] = {"Q": Qn, "B": B, "D": D, "linear_seeded_bucket_ms": b_ms, "bucket_min_ms": min(bucket),
+                        "batched_call_ms": statistics.median(t["batched"]), "sequential_calls_ms": s_ms,
+                        "sequential_min_ms": min(t["sequential"]), "ratio_batched_over_sequential": b_ms / s_ms,
+                        "meets_bar": b_ms < s_ms, "equal_words": equal}
+    eng.profile(False)
+    out["kernel"] = eng.kernel_name("linear_seeded")
+    return out
+
+
+def stored_queries(cq, oq, D: int, n_bits: int, steps: int, warmup: int, Qn: int = 8, B: int = 128,
+                   B_full: int = 1024) -> dict:
+    """The stored-ciphertext search for several queries, one
+    process, three things interleaved in rotating order as multi_query does:
+    (a) CorpusServer.search_many with Qn queries against B resident
+    documents, (b) Qn sequential CorpusServer.search calls against the same
+    documents, (c) one EncryptedCorpus.compare against B_full = Qn * B
+    documents on the key holder's context (the same ciphertext count as (a)).
+    Host clock around each with a device synchronise (reply copies included),
+    and the parity of (a)'s decrypted replies with (b)'s and the restatement."""
+    import numpy as np
+    import torch
+    from oracle import quant_ref as Q
+    from fheicp.corpus import EncryptedCorpus
+    from fheicp.stored import CorpusClient, CorpusServer
+    assert Qn * B == B_full
+    c = EncryptedCorpus(cq).compile(key_seed=5, device=0, noise_seed=6)
+    client = CorpusClient(c, count=B_full, pack_seed=17)
+    server = CorpusServer(client.eval_keys(), cq, c.P0, c.mask_key)
+    _, docs = Q.make_corpus(D, B_full, seed=21)
+    qs = np.stack([Q.make_corpus(D, 1, seed=100 + i)[0] for i in range(Qn)])
+    bodies, ids = client.encrypt_docs(docs)
+    server.load(bodies[:B], ids[:B])
+    bd_full, id_full = c.engine.to_dev(bodies), c.engine.to_dev(ids)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    runs = {"a": lambda: server.search_many(qs, 0.5),
+            "b": lambda: [server.search(q, 0.5) for q in qs],
+            "c": lambda: c.compare(bd_full, id_full, qs[0], 0.5)}
+    orders = ("abc", "cba", "bca", "acb", "cab", "bac")
+    t = {k: [] for k in runs}
+    last = {}
+    for i in range(warmup + steps):
+        for k in orders[i % len(orders)]:
+            sec, last[k] = timed(runs[k])
+            if i >= warmup:
+                t[k].append(sec)
+    acc_a, below_a = client.decrypt_replies(last["a"])
+    singles = [client.decrypt_replies(r) for r in last["b"]]
+    parity = bool(all(torch.equal(acc_a[q], s[0][0]) and torch.equal(below_a[q], s[1][0])
+                      for q, s in enumerate(singles)))
+    ref = np.stack([Q.corpus_accumulate(oq, cq.s_e, n_bits, q, docs[:B]) for q in qs])
+    scores = np.float64(Q.corpus_out_scale(oq, cq.s_e)) * ref.astype(np.float64)
+    exact = bool(np.array_equal(acc_a.cpu().numpy(), ref) and
+                 np.array_equal(below_a.cpu().numpy(), (scores < 0.5).astype(np.int64)))
+    ref_c = Q.corpus_accumulate(oq, cq.s_e, n_bits, qs[0], docs)
+    exact_c = bool(np.array_equal(last["c"][0].cpu().numpy(), ref_c))
+    med = {k: statistics.median(v) * 1e3 for k, v in t.items()}
+    out = {"Q": Qn, "B": B, "B_full": B_full, "pack_gadget": [client.base_log, client.level],
+           "pack_margin_sigmas": client.margin, "in_var": client.in_var,
+           "a_search_many_ms": med["a"], "a_min_ms": min(t["a"]) * 1e3,
+           "b_sequential_searches_ms": med["b"], "b_min_ms": min(t["b"]) * 1e3, "b_per_search_ms": med["b"] / Qn,
+           "c_full_compare_ms": med["c"], "c_min_ms": min(t["c"]) * 1e3,
+           "ratio_a_over_b": med["a"] / med["b"], "meets_bar_a_over_b": med["a"] <= 0.5 * med["b"],
+           "ratio_a_over_c": med["a"] / med["c"], "meets_bar_a_over_c": med["a"] <= 1.10 * med["c"],
+           "reply_bytes": {"a": int(sum(r.nbytes for r in last["a"])), "b": int(sum(r.nbytes for r in last["b"]))},
+           "parity_with_sequential": parity, "bit_exact": exact, "full_compare_bit_exact": exact_c,
+           "steps": steps, "warmup": warmup}
+    out["leveled"] = stored_leveled(server.engine, D, steps, warmup, Qn, (B, B_full))
+    out["meets_bar"] = bool(out["meets_bar_a_over_b"] and out["meets_bar_a_over_c"] and
+                            all(v["meets_bar"] for k, v in out["leveled"].items() if k != "kernel"))
+    server.engine.close()
+    c.engine.close()
+    return out
+
+
 def both_private(cq, oq, B: int, D: int, n_bits: int, steps: int, warmup: int) -> dict:
     """fhe_compare_ggsw_batch against fhe_compare_query_batch on one context,
     interleaved in alternating order."""
@@ -369,11 +504,19 @@ def main() -> int:
                     help="several queries in one batched call (16-dim, n_bits 6, two-party): search_many with "
                          "Q = 8, B = 128 against eight sequential searches and one B = 1024 search, 24 "
                          "interleaved steps after 4 warm-up; writes profiles/r11/multi_query.json")
+    ap.add_argument("--stored-queries", action="store_true",
+                    help="the stored-ciphertext search for several clear queries (16-dim, n_bits 6, two-party): "
+                         "CorpusServer.search_many with Q = 8, B = 128 against eight sequential searches and one "
+                         "B = 1024 compare, and the batched leveled step against eight single calls at B = 128 "
+                         "and 1024; 24 interleaved steps after 4 warm-up; writes profiles/r12/stored_queries.json "
+                         "(with --no-end-to-end: the leveled step only, no keys)")
     ap.add_argument("--out", default=None, help="default profiles/query_bench.json "
-                                                "(--multi-query: profiles/r11/multi_query.json)")
+                                                "(--multi-query: profiles/r11/multi_query.json, "
+                                                "--stored-queries: profiles/r12/stored_queries.json)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = str(REPO / "profiles" / ("r11/multi_query.json" if a.multi_query else "query_bench.json"))
+        a.out = str(REPO / "profiles" / ("r11/multi_query.json" if a.multi_query else
+                                         "r12/stored_queries.json" if a.stored_queries else "query_bench.json"))
     if a.launches < 20:
         ap.error("--launches must be >= 20 (the medians compared are of at least 20 launches)")
     import torch
@@ -387,6 +530,25 @@ def main() -> int:
         mq = multi_query(cq, oq, 16, 6, steps=24, warmup=4)
         res = {"bench": "query_bench --multi-query", "device": torch.cuda.get_device_name(0), "D": 16, "n_bits": 6,
                "P0": cq.worst_msg_bits(), "multi_query": mq, "meets_bar": mq["meets_bar"]}
+        line = json.dumps(res)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(line + "\n")
+        print(line)
+        return 0
+    if a.stored_queries:
+        cq, oq = corpus_quant(16, 6)
+        P0 = cq.worst_msg_bits()
+        if a.no_end_to_end:
+            eng = Engine(params_for_bits(P0), 0)
+            sq = {"leveled": stored_leveled(eng, 16, steps=24, warmup=4)}
+            sq["meets_bar"] = all(v["meets_bar"] for k, v in sq["leveled"].items() if k != "kernel")
+            eng.close()
+        else:
+            sq = stored_queries(cq, oq, 16, 6, steps=24, warmup=4)
+        from fheicp import _lib
+        res = {"bench": "query_bench --stored-queries", "device": torch.cuda.get_device_name(0), "D": 16, "n_bits": 6,
+               "P0": P0, "build": _lib.lib().fhe_build_info().decode(), "stored_queries": sq,
+               "meets_bar": sq["meets_bar"]}
         line = json.dumps(res)
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(line + "\n")
