@@ -12,6 +12,8 @@
 //                     digits, key generation, rotation, packed decryption
 //   k_extprod.h       both-private search: GGSW query encryption, GLWE document
 //                     digits, Toeplitz byte planes, slot extraction
+//   k_extprod_q.h     both-private search, Q queries in one pass: reversed
+//                     document digits, GGSW byte planes, the transposed i8 GEMM
 //   k_blind_rotate.h  blind rotation (external products over an f64 wave FFT):
 //                     v4 (br_v4.h, the default hot kernel), v2/v3, v1
 //   this file         context, launch selection, profiling, the C ABI
@@ -35,6 +37,7 @@
 #include "k_query.h"
 #include "k_pack.h"
 #include "k_extprod.h"
+#include "k_extprod_q.h"
 #include "k_blind_rotate.h"
 
 // ============================================================ host =========
@@ -112,6 +115,9 @@ struct fhe_ctx {
   void* xp_ws = nullptr;
   size_t xp_ws_bytes = 0;
   ProfAcc prof_xp;          // fhe_linear_ggsw_batch: k_extprod_planes + the GEMM + k_extprod_extract
+  // the batched entries (k_extprod_q.h) use xp_ws as: the Q queries' byte
+  // planes | the Q x G x (k+1)N result | the Q scaled constants
+  ProfAcc prof_xq;          // fhe_linear_ggsws_batch: k_ggsws_planes + the GEMM + k_extprod_extract_queries
 };
 
 static std::mutex g_err_mu;
@@ -573,6 +579,7 @@ void fhe_ctx_destroy(fhe_ctx* ctx) {
     free_ev(ctx->prof_ls);
     free_ev(ctx->prof_pack);
     free_ev(ctx->prof_xp);
+    free_ev(ctx->prof_xq);
   }
   delete ctx;
 }
@@ -2786,6 +2793,175 @@ int fhe_search_ggsw_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_log
   return post_leveled_search(ctx, w, B, levels_bit, d_glwe_acc, d_glwe_bit, stream);
 }
 
+// ---- both-private search: Q GGSW queries in one pass (k_extprod_q.h, §8.10) --
+static int ggsws_args(fhe_ctx* ctx, int64_t Q, int64_t B, int32_t D, int32_t beta, int32_t L) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  if (Q < 1 || B < 1 || D <= 0) return fail(ctx, FHE_E_ARG, "bad ggsw queries arguments (Q < 1, B < 1 or D <= 0)");
+  if (D > ctx->p.N) return fail(ctx, FHE_E_ARG, "ggsw queries dimension D > N: a document must fit one GLWE");
+  // the query is a grid dimension of the extraction
+  if (Q > 65535) return fail(ctx, FHE_E_ARG, "ggsw queries batch Q > 65535: split the call");
+  if (B > 0x7fffffffLL || Q * B > 0x7fffffffLL)
+    return fail(ctx, FHE_E_ARG, "ggsw queries result count too large (Q*B >= 2^31)");
+  if (!pack_gadget_ok(beta, L))
+    return fail(ctx, FHE_E_ARG, "ggsw queries gadget out of range (1 <= base_log <= 7, 1 <= level <= 8, "
+                                "level * (base_log + 1) <= 62)");
+  if (ctx->p.N % 256) return fail(ctx, FHE_E_ARG, "ggsw queries product needs N a multiple of 256");
+  return FHE_OK;
+}
+size_t fhe_glwe_docs_queries_bytes(const fhe_params* p, int64_t B, int32_t D, int32_t level) {
+  if (!p || B < 0 || D <= 0 || D > p->N || level < 1 || level > 8) return 0;
+  return (size_t)ggsw_glwes(*p, B, D) * (size_t)(p->k + 1) * level * xq_fstride(p->N);
+}
+int fhe_glwe_docs_queries_pack(fhe_ctx* ctx, const uint64_t* d_glwe, int64_t B, int32_t D, int32_t base_log,
+                               int32_t level, void* d_docs, void* stream) {
+  int rc = ggsws_args(ctx, 1, B, D, base_log, level);  // argument errors first
+  if (rc) return rc;
+  if (!d_glwe || !d_docs) return fail(ctx, FHE_E_ARG, "null ggsw queries document buffers");
+  if ((rc = need_device(ctx))) return rc;
+  const fhe_params& p = ctx->p;
+  hipStream_t st = (hipStream_t)stream;
+  const int n1 = (p.k + 1) * p.N;
+  const int64_t G = ggsw_glwes(p, B, D);
+  if (G > 65535) return fail(ctx, FHE_E_ARG, "ggsw queries document batch too large: split the call");
+  HIPCHK(ctx, hipMemsetAsync(d_docs, 0, fhe_glwe_docs_queries_bytes(&p, B, D, level), st));
+  hipLaunchKernelGGL(k_glwe_digits_rev, dim3((unsigned)((n1 + 1023) / 1024), (unsigned)G), dim3(256), 0, st, d_glwe,
+                     p.N, p.k, (int)base_log, (int)level, (uint8_t*)d_docs);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+// row tiles of the GEMM (16 rows (q, c') each), padded to whole workgroup tiles
+static int64_t ggsws_row_tiles(const fhe_params& p, int64_t Q, int* RT) {
+  const int64_t rtn = (Q * (p.k + 1) + 15) / 16;
+  *RT = rtn > 1 ? 2 : 1;
+  return (rtn + *RT - 1) / *RT * *RT;
+}
+size_t fhe_ggsws_ws_bytes(const fhe_params* p, int64_t Q, int64_t B, int32_t D, int32_t level) {
+  if (!p || Q < 1 || B < 1 || D <= 0 || D > p->N || level < 1 || level > 8) return 0;
+  int RT;
+  const size_t rtp = (size_t)ggsws_row_tiles(*p, Q, &RT);
+  const size_t n1 = (size_t)(p->k + 1) * p->N, G = (size_t)ggsw_glwes(*p, B, D);
+  // byte planes: 8 bytes per padded row and k | the result | the constants
+  return rtp * 16 * n1 * level * 8 + 8 * (size_t)Q * G * n1 + 8 * (size_t)Q;
+}
+
+// planes -> GEMM -> slot extraction, h_cst[q] (or cst - h_T[q]) on query q's
+// bodies, into d_out (Q B x (kN+1), query-major)
+static int linear_ggsws_impl(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t L, const void* d_docs, int64_t Q,
+                             int64_t B, int32_t D, const int64_t* h_cst, int64_t cst, const int64_t* h_T,
+                             uint64_t* d_out, hipStream_t st) {
+  const fhe_params& p = ctx->p;
+  const int n1 = (p.k + 1) * p.N, KB = n1 * L / 64, S = ggsw_slots(p, D);
+  const int64_t G = ggsw_glwes(p, B, D);
+  int RT;
+  const int64_t rtp = ggsws_row_tiles(p, Q, &RT), rgrid = rtp / RT;
+  const int64_t cgrid = G * (p.N / 16) / XQ_CG;  // N % 256 == 0: whole workgroups
+  if (G > 65535 || rgrid > 65535 || cgrid > 0x7fffffffLL)
+    return fail(ctx, FHE_E_ARG, "ggsw queries batch too large: split the call");
+  const size_t need = fhe_ggsws_ws_bytes(&p, Q, B, D, L);
+  if (need > ctx->xp_ws_bytes) {
+    if (ctx->xp_ws) {
+      HIPCHK(ctx, hipDeviceSynchronize());
+      HIPCHK(ctx, hipFree(ctx->xp_ws));
+      ctx->xp_ws = nullptr;
+      ctx->xp_ws_bytes = 0;
+    }
+    HIPCHK(ctx, hipMalloc(&ctx->xp_ws, need));
+    ctx->xp_ws_bytes = need;
+  }
+  const size_t pbytes = (size_t)rtp * 16 * n1 * L * 8, mbytes = 8 * (size_t)Q * G * n1;
+  v4i* P8 = (v4i*)ctx->xp_ws;
+  u64* M = (u64*)((char*)ctx->xp_ws + pbytes);
+  u64* d_cst = M + (size_t)Q * G * n1;
+  int rc = store_scaled_csts(ctx, d_cst, Q, h_cst, cst, h_T, st);
+  if (rc) return rc;
+  // K split over workgroups towards ~XQ_WGS of them, slices of 4 k-blocks at least
+#ifndef FHEICP_XQ_WGS
+#define FHEICP_XQ_WGS 512  // A/B builds (tools/build_variant.sh): other targets
+#endif
+  int Sk = (int)std::max<int64_t>(
+      1, std::min<int64_t>(KB / 4, FHEICP_XQ_WGS / std::max<int64_t>(1, cgrid * rgrid)));
+  const int kslice = (KB + Sk - 1) / Sk;
+  Sk = (KB + kslice - 1) / kslice;
+  hipEvent_t e1;
+  prof_begin(ctx, ctx->prof_xq, st, &e1);
+  ctx->prof_xq.kernel = RT == 2 ? "k_extprod_queries_mfma<2>" : "k_extprod_queries_mfma<1>";
+  if (Sk > 1) HIPCHK(ctx, hipMemsetAsync(M, 0, mbytes, st));
+  hipLaunchKernelGGL(k_ggsws_planes, dim3((unsigned)KB, (unsigned)rtp), dim3(64), 0, st, d_ggsw, p.N, p.k, (int)L,
+                     (int)Q, P8);
+  const dim3 grid((unsigned)cgrid, (unsigned)rgrid, (unsigned)Sk);
+  if (RT == 2)
+    hipLaunchKernelGGL(k_extprod_queries_mfma<2>, grid, dim3(256), 0, st, (const v4i*)P8, (const uint8_t*)d_docs, p.N,
+                       p.k, (int)L, (int)Q, (int)G, KB, kslice, M);
+  else
+    hipLaunchKernelGGL(k_extprod_queries_mfma<1>, grid, dim3(256), 0, st, (const v4i*)P8, (const uint8_t*)d_docs, p.N,
+                       p.k, (int)L, (int)Q, (int)G, KB, kslice, M);
+  hipLaunchKernelGGL(k_extprod_extract_queries, dim3((unsigned)B, (unsigned)((p.k * p.N + 256) / 256), (unsigned)Q),
+                     dim3(256), 0, st, M, S, (int)D, p.N, p.k, G, B, d_cst, d_out);
+  prof_end(ctx, ctx->prof_xq, st, e1, Q * B);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+int fhe_linear_ggsws_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_log, int32_t level, const void* d_docs,
+                           int64_t Q, int64_t B, int32_t D, const int64_t* h_cst, uint64_t* d_out, void* stream) {
+  int rc = ggsws_args(ctx, Q, B, D, base_log, level);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  if (!d_ggsw || !d_docs || !h_cst || !d_out) return fail(ctx, FHE_E_ARG, "null linear ggsw queries arguments");
+  if ((rc = need_device(ctx))) return rc;
+  return linear_ggsws_impl(ctx, d_ggsw, level, d_docs, Q, B, D, h_cst, 0, nullptr, d_out, (hipStream_t)stream);
+}
+
+// the leveled workspace for Q B results with the Q thresholds in the query's place
+static int ggsws_leveled(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t L, const void* d_docs, int64_t Q, int64_t B,
+                         int32_t D, int64_t cst, const int64_t* h_T, bool keep_copy, QueryWs* w, int64_t** d_T,
+                         void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  u64* ex;
+  int rc = leveled_ws(ctx, Q * B, (size_t)Q, keep_copy, w, &ex);
+  if (rc) return rc;
+  *d_T = (int64_t*)ex;
+  if ((rc = store_words(ctx, ex, (const u64*)h_T, Q, st))) return rc;
+  return linear_ggsws_impl(ctx, d_ggsw, L, d_docs, Q, B, D, nullptr, cst, h_T, w->ctv, st);
+}
+
+int fhe_compare_ggsws_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_log, int32_t level, const void* d_docs,
+                            int64_t Q, int64_t B, int32_t D, int64_t cst, const int64_t* h_T, int64_t* d_acc,
+                            int64_t* d_below, void* stream) {
+  int rc = ggsws_args(ctx, Q, B, D, base_log, level);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  if (!d_ggsw || !d_docs || !h_T || !d_acc || !d_below)
+    return fail(ctx, FHE_E_ARG, "null compare ggsw queries arguments");
+  if ((rc = need_secret(ctx))) return rc;
+  QueryWs w;
+  int64_t* d_T;
+  rc = ggsws_leveled(ctx, d_ggsw, level, d_docs, Q, B, D, cst, h_T, false, &w, &d_T, stream);
+  if (rc) return rc;
+  return post_leveled_compare_queries(ctx, w, Q, B, d_T, d_acc, d_below, stream);
+}
+
+int fhe_search_ggsws_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_log, int32_t level, const void* d_docs,
+                           int64_t Q, int64_t B, int32_t D, int64_t cst, const int64_t* h_T, int32_t levels_bit,
+                           uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream) {
+  int rc = ggsws_args(ctx, Q, B, D, base_log, level);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  if (levels_bit < 0 || levels_bit > 8)
+    return fail(ctx, FHE_E_ARG, "bad search ggsw queries arguments (levels_bit outside [0, 8])");
+  if (!d_ggsw || !d_docs || !h_T || !d_glwe_acc || !d_glwe_bit)
+    return fail(ctx, FHE_E_ARG, "null search ggsw queries arguments");
+  if ((rc = need_eval_keys(ctx))) return rc;
+  if ((rc = need_pack_key(ctx))) return rc;
+  if (levels_bit > ctx->pk_level)
+    return fail(ctx, FHE_E_ARG, "search ggsw queries levels_bit exceeds the packing key's levels");
+  QueryWs w;
+  int64_t* d_T;
+  rc = ggsws_leveled(ctx, d_ggsw, level, d_docs, Q, B, D, cst, h_T, true, &w, &d_T, stream);
+  if (rc) return rc;
+  // result q B + b is ciphertext q B + b of the batch: coefficient (q B + b) mod N
+  // of GLWE (q B + b) / N
+  return post_leveled_search(ctx, w, Q * B, levels_bit, d_glwe_acc, d_glwe_bit, stream);
+}
+
 int fhe_threshold_batch(fhe_ctx* ctx, const uint64_t* d_ct_acc, int64_t count, int64_t T, uint64_t* d_bit,
                         void* stream) {
   int rc = need_eval_keys(ctx);
@@ -2978,6 +3154,7 @@ static ProfAcc* prof_bucket(fhe_ctx* ctx, const char* kernel) {
   if (!strcmp(kernel, "linear_seeded")) return &ctx->prof_ls;
   if (!strcmp(kernel, "pack")) return &ctx->prof_pack;
   if (!strcmp(kernel, "linear_ggsw")) return &ctx->prof_xp;
+  if (!strcmp(kernel, "linear_ggsws")) return &ctx->prof_xq;
   return nullptr;
 }
 

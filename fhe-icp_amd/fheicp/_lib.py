@@ -143,6 +143,13 @@ SIGNATURES = [
                                                    _vp]),
     ("fhe_search_seeded_queries_batch", C.c_int, [_CTXP, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _vp,
                                                   _vp, _vp]),
+    ("fhe_glwe_docs_queries_bytes", C.c_size_t, [_P, _i64, _i32, _i32]),
+    ("fhe_glwe_docs_queries_pack", C.c_int, [_CTXP, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    ("fhe_ggsws_ws_bytes", C.c_size_t, [_P, _i64, _i64, _i32, _i32]),
+    ("fhe_linear_ggsws_batch", C.c_int, [_CTXP, _vp, _i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    ("fhe_compare_ggsws_batch", C.c_int, [_CTXP, _vp, _i32, _i32, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
+    ("fhe_search_ggsws_batch", C.c_int, [_CTXP, _vp, _i32, _i32, _vp, _i64, _i64, _i32, _i64, _vp, _i32, _vp, _vp,
+                                         _vp]),
     # include/fhe_bert.h: the embedding stage's encoder (fheicp.bert)
     ("fhe_bert_create", C.c_int, [_vp, C.c_int, C.POINTER(C.c_void_p)]),
     ("fhe_bert_destroy", None, [_vp]),

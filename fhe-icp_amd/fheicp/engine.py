@@ -698,6 +698,71 @@ class Engine:
                                                 _stream(self.device)))
         return ga, gb
 
+    # ------------- both-private search: several GGSW queries in one pass (§8.10) --
+    def ggsws_ws_bytes(self, Q: int, B: int, D: int, level: int) -> int:
+        """Context workspace of a batched call (fhe_ggsws_ws_bytes; host only)."""
+        return self._L.fhe_ggsws_ws_bytes(C.byref(self._P), int(Q), int(B), int(D), int(level))
+
+    def pack_docs_glwe_queries(self, glwe: torch.Tensor, B: int, D: int, base_log: int, level: int) -> torch.Tensor:
+        """Document GLWEs -> the resident operand of linear_ggsws /
+        compare_ggsws / search_ggsws (fhe_glwe_docs_queries_pack)."""
+        n = self._L.fhe_glwe_docs_queries_bytes(C.byref(self._P), int(B), int(D), int(level))
+        docs = torch.empty(n, dtype=torch.uint8, device=self.device)
+        self._chk(self._L.fhe_glwe_docs_queries_pack(self._ctx, _ptr(glwe), int(B), int(D), int(base_log), int(level),
+                                                     _ptr(docs), _stream(self.device)))
+        return docs
+
+    def _ggsws(self, ggsws: torch.Tensor, base_log: int, level: int) -> int:
+        words = self.ggsw_words(base_log, level)
+        if words == 0 or ggsws.numel() == 0 or ggsws.numel() % words:
+            raise ValueError(f"{ggsws.numel()} words are no whole number of GGSWs of gadget ({base_log}, {level})")
+        return ggsws.numel() // words
+
+    def linear_ggsws(self, ggsws: torch.Tensor, base_log: int, level: int, docs: torch.Tensor, B: int, D: int, csts,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+        """fhe_linear_ggsws_batch: ggsws Q x ggsw_words (device), csts Q host
+        constants; Q * B x (kN+1), query-major."""
+        Q = self._ggsws(ggsws, base_log, level)
+        keep, hc = self._i64s(csts)
+        if keep.size != Q:
+            raise ValueError(f"{keep.size} constants for {Q} queries")
+        if out is None:
+            out = self.empty_big(Q * B)
+        self._chk(self._L.fhe_linear_ggsws_batch(self._ctx, _ptr(ggsws), int(base_log), int(level), _ptr(docs), Q,
+                                                 int(B), int(D), hc, _ptr(out), _stream(self.device)))
+        return out
+
+    def compare_ggsws(self, ggsws: torch.Tensor, base_log: int, level: int, docs: torch.Tensor, B: int, D: int,
+                      cst: int, Ts):
+        """fhe_compare_ggsws_batch: Ts Q host thresholds;
+        (acc int64 [Q, B], below int64 [Q, B])."""
+        Q = self._ggsws(ggsws, base_log, level)
+        keep, hT = self._i64s(Ts)
+        if keep.size != Q:
+            raise ValueError(f"{keep.size} thresholds for {Q} queries")
+        acc = torch.empty((Q, B), dtype=torch.int64, device=self.device)
+        below = torch.empty((Q, B), dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_compare_ggsws_batch(self._ctx, _ptr(ggsws), int(base_log), int(level), _ptr(docs), Q,
+                                                  int(B), int(D), int(cst), hT, _ptr(acc), _ptr(below),
+                                                  _stream(self.device)))
+        return acc, below
+
+    def search_ggsws(self, ggsws: torch.Tensor, base_log: int, level: int, docs: torch.Tensor, B: int, D: int,
+                     cst: int, Ts, levels_bit: int = 0):
+        """fhe_search_ggsws_batch: the evaluation-only form;
+        (glwe_acc, glwe_bit), each ceil(Q B / N) x (k+1)N words."""
+        Q = self._ggsws(ggsws, base_log, level)
+        keep, hT = self._i64s(Ts)
+        if keep.size != Q:
+            raise ValueError(f"{keep.size} thresholds for {Q} queries")
+        shape = (self.glwe_count(Q * B), (self.params.k + 1) * self.params.N)
+        ga = torch.empty(shape, dtype=torch.int64, device=self.device)
+        gb = torch.empty(shape, dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_search_ggsws_batch(self._ctx, _ptr(ggsws), int(base_log), int(level), _ptr(docs), Q,
+                                                 int(B), int(D), int(cst), hT, int(levels_bit), _ptr(ga), _ptr(gb),
+                                                 _stream(self.device)))
+        return ga, gb
+
     def topk(self, acc: torch.Tensor, below: torch.Tensor | None, k: int, base_idx: int = 0):
         oa = torch.empty(k, dtype=torch.int64, device=self.device)
         oi = torch.empty(k, dtype=torch.int64, device=self.device)

@@ -16,6 +16,12 @@ sees neither the documents nor the query.
     ``acc - T`` and the packed replies of the two-party private query
     (fhe_search_ggsw_batch); it holds evaluation keys, the CorpusQuant and P0.
 
+Several queries of one key holder go in one pass:
+``PrivateClient.encrypt_queries`` gives each query its own stream-id range,
+``PrivateServer.pack_docs_many`` makes the batched document operand and
+``search_many`` answers with fheicp.query's version-2 replies
+(fhe_search_ggsws_batch: the product transposed, no Toeplitz operand).
+
 The expected values are the bilinear restatement of fheicp.corpus
 (oracle/quant_ref.py, ``corpus_*``); reply format and packing plan are
 fheicp.query's.
@@ -58,6 +64,35 @@ def unpack_ggsw_query(arr) -> dict:
         raise ValueError("GGSW query payload size does not match its gadget and parameters")
     return {"D": int(a[2]), "P0": int(a[3]), "base_log": base_log, "level": level, "N": N, "k": k,
             "ggsw": a[HEADER_WORDS:].copy()}
+
+
+# ------------------------------------------------------ batches of queries --
+# Several GGSW queries of one key holder answered in one pass (DESIGN.md
+# §8.10): a batch is a list of the payloads above, no new format.
+def ggsw_id_span(k: int, level: int) -> int:
+    """Stream ids one GGSW consumes: (k+1) L k mask ids from its id0 on (the
+    (k+1) L noise ids are the first of the same range, under another tag)."""
+    return (int(k) + 1) * int(level) * int(k)
+
+
+def ggsw_query_ids(id0: int, Q: int, k: int, level: int) -> list:
+    """id0 of each of Q queries of one batch: query q takes
+    [id0 + q span, id0 + (q + 1) span) modulo 2^64, span = ggsw_id_span."""
+    span = ggsw_id_span(k, level)
+    return [(int(id0) + q * span) % (1 << 64) for q in range(int(Q))]
+
+
+def check_ggsw_batch(pls) -> None:
+    """The unpacked GGSW payloads of one batch agree in D, P0, gadget, N and
+    k. ValueError names the offending query."""
+    if not pls:
+        raise ValueError("an empty batch of queries")
+    first = pls[0]
+    for i, pl in enumerate(pls[1:], 1):
+        for field, what in (("D", "dimension D"), ("P0", "width P0"), ("base_log", "gadget base_log"),
+                            ("level", "gadget level"), ("N", "polynomial size N"), ("k", "GLWE dimension k")):
+            if pl[field] != first[field]:
+                raise ValueError(f"query {i}: {what} {pl[field]} differs from query 0's {first[field]}")
 
 
 def pack_doc_block(glwe, B: int, D: int, P0: int, N: int, k: int) -> np.ndarray:
@@ -157,6 +192,23 @@ class PrivateClient(QueryClient):
         return pack_ggsw_query(g.cpu().numpy().view(np.uint64), len(W), self.P0, self.base_log, self.level,
                                eng.params.N, eng.params.k)
 
+    def encrypt_queries(self, vectors, id0: int | None = None) -> list:
+        """Q reduced query vectors [Q, D] -> Q GGSW payloads. One random id0;
+        query q takes its (k+1) L k mask ids and (k+1) L noise ids from
+        id0 + q (k+1) L k on (ggsw_query_ids), so no id repeats under the
+        session key."""
+        eng = self.corpus.engine
+        qq = self.cq.quant(np.atleast_2d(np.asarray(vectors)))
+        ids = ggsw_query_ids(self._ids(id0), len(qq), eng.params.k, self.level)
+        eng.set_msg_bits(self.P0)
+        out = []
+        for q, i in zip(qq, ids):
+            W = self.cq.weights(q)
+            g = eng.encrypt_ggsw(W, self.base_log, self.level, self._enc_key, i)
+            out.append(pack_ggsw_query(g.cpu().numpy().view(np.uint64), len(W), self.P0, self.base_log, self.level,
+                                       eng.params.N, eng.params.k))
+        return out
+
 
 class PrivateServer(QueryServer):
     """The untrusted host: evaluation keys, the CorpusQuant and P0 only."""
@@ -189,3 +241,37 @@ class PrivateServer(QueryServer):
         ga, gb = eng.search_ggsw(eng.to_dev(pl["ggsw"]), self.base_log, self.level, docs8, int(B), pl["D"], cst, T,
                                  self.bit_levels)
         return pack_reply(ga.cpu().numpy().view(np.uint64), gb.cpu().numpy().view(np.uint64), B, self.P0, T)
+
+    # -------------------------------------------------- batches of queries --
+    def pack_docs_many(self, block):
+        """A document block -> (the device-resident operand of search_many, B)."""
+        bl = unpack_doc_block(block)
+        self._check(bl, "document block")
+        eng = self.engine
+        return eng.pack_docs_glwe_queries(eng.to_dev(bl["glwe"]), bl["B"], bl["D"], self.base_log,
+                                          self.level), bl["B"]
+
+    def search_many(self, payloads, docs, B: int, min_similarity=None) -> list:
+        """Q GGSW queries of one key holder against B encrypted documents
+        packed by pack_docs_many, in one pass (fhe_search_ggsws_batch) -> a
+        LIST of version-2 replies (query.pack_replies), one per chunk of
+        query_chunks(Q, B). min_similarity: a float, None, or a sequence of Q
+        of them. QueryClient.decrypt_replies takes the list."""
+        from .query import pack_replies, query_chunks, thresholds_for
+        eng = self.engine
+        pls = [unpack_ggsw_query(p) for p in payloads]
+        check_ggsw_batch(pls)
+        self._check(pls[0], "query 0")
+        if (pls[0]["base_log"], pls[0]["level"]) != (self.base_log, self.level):
+            raise ValueError("query 0: gadget differs from the one the documents were packed for")
+        Q, D = len(pls), pls[0]["D"]
+        _, cst, _ = self.plan(None)
+        Ts = [self.plan(t)[2] for t in thresholds_for(min_similarity, Q)]
+        out = []
+        for ch in query_chunks(Q, int(B)):
+            g = eng.to_dev(np.concatenate([pls[q]["ggsw"] for q in ch]))
+            Tc = [Ts[q] for q in ch]
+            ga, gb = eng.search_ggsws(g, self.base_log, self.level, docs, int(B), D, cst, Tc, self.bit_levels)
+            out.append(pack_replies(ga.cpu().numpy().view(np.uint64), gb.cpu().numpy().view(np.uint64), B, self.P0,
+                                    Tc))
+        return out

@@ -565,9 +565,10 @@ int fhe_stream_sync(fhe_ctx* ctx, void* stream);
  * private-query leveled step: query planes + GEMM, one bracket around both)
  * "pack" (the packing key switch: digits + GEMM + rotation, one bracket),
  * "linear_ggsw" (the both-private leveled step: Toeplitz planes + GEMM +
- * slot extraction, one bracket) or "linear_seeded" (the stored-ciphertext
- * leveled step of the batched entries, k_linear_seeded_queries), then resets
- * what it read. */
+ * slot extraction, one bracket), "linear_ggsws" (the same step of the batched
+ * entries: GGSW byte planes + the transposed GEMM + slot extraction) or
+ * "linear_seeded" (the stored-ciphertext leveled step of the batched entries,
+ * k_linear_seeded_queries), then resets what it read. */
 int fhe_profile_enable(fhe_ctx* ctx, int enable);
 int fhe_profile_read(fhe_ctx* ctx, const char* kernel, double* total_ms, int64_t* launches, int64_t* items);
 /* The kernel last launched for that bucket, as rocprofv3 names it (e.g.
@@ -644,6 +645,50 @@ int fhe_search_seeded_queries_batch(fhe_ctx* ctx, const uint64_t* d_body, const 
                                     int32_t D, const uint32_t h_mask_key[8], int64_t Q, const int64_t* d_W,
                                     int64_t cst, const int64_t* h_T, int32_t levels_bit, uint64_t* d_glwe_acc,
                                     uint64_t* d_glwe_bit, void* stream);
+
+/* ---- both-private search: several GGSW queries in one pass -
+ * Q GGSW queries of one key holder (d_ggsw: Q x fhe_ggsw_words, one gadget)
+ * against the same B GLWE-encrypted documents. The product is the one of
+ * fhe_linear_ggsw_batch, transposed: rows (q, component), K = (c, l, coef),
+ * columns (document GLWE, coef); the query operand is the GGSWs' own byte
+ * planes and the document fragments are formed in the kernel, so no buffer
+ * is proportional to ((k+1)N)^2 and the Q queries share every document
+ * fragment. Results are query-major (row / element q * B + b) and equal, word
+ * for word, Q single-query calls. Q >= 1, B >= 1, 0 < D <= N, Q <= 65535,
+ * Q * B < 2^31, the gadget bounds of fhe_encrypt_ggsw, N a multiple of 256,
+ * no null pointers: otherwise FHE_E_ARG ("ggsw queries ..." in
+ * fhe_last_error), reported before the device and key checks; missing keys
+ * return FHE_E_STATE.
+ *
+ * The resident document operand of the batched entries, once per corpus:
+ * 2N + 16 bytes per (document GLWE, component, level), the digits of
+ * fhe_glwe_docs_pack (same rounding, same tie coins) reversed and followed by
+ * their negation. fhe_glwe_docs_queries_bytes is 0 for bad arguments. */
+size_t fhe_glwe_docs_queries_bytes(const fhe_params* params, int64_t B, int32_t D, int32_t level);
+int fhe_glwe_docs_queries_pack(fhe_ctx* ctx, const uint64_t* d_glwe, int64_t B, int32_t D, int32_t base_log,
+                               int32_t level, void* d_docs, void* stream);
+/* Bytes of context-owned workspace a batched call allocates on first use
+ * (byte planes of the padded rows | the Q x G x (k+1)N result | Q constants);
+ * the Q * B results' own workspace is the other batched entries'. Host only;
+ * 0 for bad arguments. */
+size_t fhe_ggsws_ws_bytes(const fhe_params* params, int64_t Q, int64_t B, int32_t D, int32_t level);
+/* The leveled step alone; needs no keys. h_cst: Q host constants; d_out:
+ * Q*B x (kN+1), row q B + b = document b under query q with
+ * trivial(h_cst[q] Delta) added. Timing goes to the "linear_ggsws" profile
+ * bucket (planes + GEMM + slot extraction, one bracket). */
+int fhe_linear_ggsws_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_log, int32_t level, const void* d_docs,
+                           int64_t Q, int64_t B, int32_t D, const int64_t* h_cst, uint64_t* d_out, void* stream);
+/* fhe_compare_ggsw_batch for Q queries: query q runs with cst - h_T[q];
+ * d_acc[q B + b], d_below[q B + b] = [acc < h_T[q]]. Needs the secret key. */
+int fhe_compare_ggsws_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_log, int32_t level, const void* d_docs,
+                            int64_t Q, int64_t B, int32_t D, int64_t cst, const int64_t* h_T, int64_t* d_acc,
+                            int64_t* d_below, void* stream);
+/* evaluation-only: result q B + b in coefficient (q B + b) mod N of GLWE (q B + b) / N, ceil(Q B / N) GLWEs
+ * each for acc - h_T[q] (all levels) and the bits (levels_bit prefix; 0: all). Needs evaluation keys and the
+ * packing key, no secret. */
+int fhe_search_ggsws_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_log, int32_t level, const void* d_docs,
+                           int64_t Q, int64_t B, int32_t D, int64_t cst, const int64_t* h_T, int32_t levels_bit,
+                           uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,14 @@ _PROTOS = {
     "fhe_linear_ggsw_batch": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _i32, _i64, _vp, _vp]),
     "fhe_compare_ggsw_batch": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp]),
     "fhe_search_ggsw_batch": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _i32, _i64, _i64, _i32, _vp, _vp, _vp]),
+    # several GGSW queries in one pass
+    "fhe_glwe_docs_queries_bytes": (C.c_size_t, [C.POINTER(fhe_params), _i64, _i32, _i32]),
+    "fhe_glwe_docs_queries_pack": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "fhe_ggsws_ws_bytes": (C.c_size_t, [C.POINTER(fhe_params), _i64, _i64, _i32, _i32]),
+    "fhe_linear_ggsws_batch": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "fhe_compare_ggsws_batch": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "fhe_search_ggsws_batch": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _i64, _i32, _i64, _vp, _i32, _vp, _vp,
+                                         _vp]),
 }
 
 
@@ -416,6 +424,64 @@ class GpuCompare:
         finally:
             for d in bufs:
                 self.L.fhe_dev_free(self.ctx, d)
+
+    # ---- several GGSW queries in one pass ----------------
+    def pack_docs_glwe_queries(self, glwe: np.ndarray, B: int, D: int, base_log: int, level: int):
+        """Server: document GLWEs -> the device-resident operand of the
+        batched calls (handle, B, D); free it with free_docs."""
+        src = self._to_dev(np.asarray(glwe, np.uint64))
+        try:
+            docs = self._alloc(self.L.fhe_glwe_docs_queries_bytes(C.byref(self.P), B, D, level))
+            self._ok(self.L.fhe_glwe_docs_queries_pack(self.ctx, src, B, D, base_log, level, docs, None))
+            self._to_host(docs, 1)  # fhe_memcpy_d2h synchronises: the pack is done before src is freed
+            return docs, B, D
+        finally:
+            self.L.fhe_dev_free(self.ctx, src)
+
+    def _ggsws(self, ggsws, base_log: int, level: int):
+        g = np.ascontiguousarray(ggsws, np.uint64).reshape(-1)
+        words = self.L.fhe_ggsw_words(C.byref(self.P), base_log, level)
+        if words == 0 or g.size == 0 or g.size % words:
+            raise ValueError(f"{g.size} words are no whole number of GGSWs of gadget ({base_log}, {level})")
+        return g, g.size // words
+
+    def compare_ggsws(self, ggsws, base_log: int, level: int, docs, cst: int, Ts):
+        """Single party: Q GGSW queries (uint64 [Q, fhe_ggsw_words]) against
+        documents packed by pack_docs_glwe_queries: (acc int64 [Q, B], below
+        int64 [Q, B]); query q uses threshold Ts[q] (fhe_compare_ggsws_batch)."""
+        d, B, D = docs
+        g, Q = self._ggsws(ggsws, base_log, level)
+        hT = np.ascontiguousarray([int(t) for t in Ts], np.int64)
+        if hT.size != Q:
+            raise ValueError(f"{hT.size} thresholds for {Q} queries")
+        bufs = [self._to_dev(g), self._alloc(8 * Q * B), self._alloc(8 * Q * B)]
+        try:
+            self._ok(self.L.fhe_compare_ggsws_batch(self.ctx, bufs[0], base_log, level, d, Q, B, D, int(cst),
+                                                    hT.ctypes.data, bufs[1], bufs[2], None))
+            return self._to_host(bufs[1], Q * B).reshape(Q, B), self._to_host(bufs[2], Q * B).reshape(Q, B)
+        finally:
+            for b in bufs:
+                self.L.fhe_dev_free(self.ctx, b)
+
+    def search_ggsws(self, ggsws, base_log: int, level: int, docs, cst: int, Ts, levels_bit: int = 0):
+        """Untrusted host, Q GGSW queries: (glwe_acc, glwe_bit) uint64 host
+        arrays of ceil(Q B / N) * (k+1) * N words each; result (q, b) is
+        coefficient (q B + b) mod N of GLWE (q B + b) / N
+        (fhe_search_ggsws_batch; evaluation keys and the packing key only)."""
+        d, B, D = docs
+        g, Q = self._ggsws(ggsws, base_log, level)
+        hT = np.ascontiguousarray([int(t) for t in Ts], np.int64)
+        if hT.size != Q:
+            raise ValueError(f"{hT.size} thresholds for {Q} queries")
+        words = -(-(Q * B) // self.P.N) * (self.P.k + 1) * self.P.N
+        bufs = [self._to_dev(g), self._alloc(8 * words), self._alloc(8 * words)]
+        try:
+            self._ok(self.L.fhe_search_ggsws_batch(self.ctx, bufs[0], base_log, level, d, Q, B, D, int(cst),
+                                                   hT.ctypes.data, int(levels_bit), bufs[1], bufs[2], None))
+            return self._to_host(bufs[1], words).view(np.uint64), self._to_host(bufs[2], words).view(np.uint64)
+        finally:
+            for b in bufs:
+                self.L.fhe_dev_free(self.ctx, b)
 
     def close(self) -> None:
         if self.ctx:
