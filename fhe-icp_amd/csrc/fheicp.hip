@@ -1672,11 +1672,15 @@ struct SignTrace {
   uint32_t* phase = nullptr;
 };
 
+extern "C++" {
+template <class Step>
+static int sign_walk(const fhe_params& p, int d, Step&& step, uint64_t* d_sign);
+}
+
 static int sign_extract(fhe_ctx* ctx, uint64_t* d_ct_v, int64_t count, uint64_t* d_sign, uint64_t* small,
                         hipStream_t st, int lane = 0, const SignTrace* tr = nullptr) {
   const fhe_params& p = ctx->p;
   const int P = p.msg_bits, logN = log2i(p.N);
-  int rc;
   int d = 0, sched[64];
   if (P < 4) {
     for (int r = 0; r < P; ++r) sched[r] = 0;
@@ -1702,6 +1706,17 @@ static int sign_extract(fhe_ctx* ctx, uint64_t* d_ct_v, int64_t count, uint64_t*
     }
     return launch_br(ctx, small, count, tv, mode, nullptr, d_ct_v, nullptr, sign, st, sched[round++]);
   };
+  return sign_walk(p, d, step, d_sign);
+}
+
+// The rounds of a sign extraction in order (shifts, centring constants and
+// test vectors), each handed to step(shift, add, tv, mode, sign): shared by
+// sign_extract and the group form (fhe_sign_group_batch)
+extern "C++" {
+template <class Step>
+static int sign_walk(const fhe_params& p, int d, Step&& step, uint64_t* d_sign) {
+  const int P = p.msg_bits, logN = log2i(p.N);
+  int rc;
   if (P < 4) {
     for (int i = 0; i < P; ++i)
       if ((rc = step(P - 1 - i, 1ull << 62, BrTv{1ull << (63 - P + i), 0, 0}, 1, (i == P - 1) ? d_sign : nullptr)))
@@ -1729,6 +1744,7 @@ static int sign_extract(fhe_ctx* ctx, uint64_t* d_ct_v, int64_t count, uint64_t*
   // sign = MSB of the top digit [P-d, P)
   return step(0, 1ull << (63 - d), BrTv{1ull << 62, 0, 0}, 1, d_sign);
 }
+}  // extern "C++"
 
 // The sign extraction of a large batch (>= PIPE_MIN ciphertexts) in two
 // halves on two streams: each half runs its key switches and bootstraps in
@@ -3201,6 +3217,338 @@ int fhe_profile_read(fhe_ctx* ctx, const char* kernel, double* total_ms, int64_t
   if (total_ms) *total_ms = ms;
   if (launches) *launches = nl;
   if (items) *items = it;
+  return FHE_OK;
+}
+
+// ---- several key holders in one batched call -------------
+// A group borrows T contexts with equal parameters on one device. Its rows are
+// T segments padded to whole four-ciphertext workgroups (fhe_group_rows); per
+// round every tenant's rows take that tenant's key switch, then ONE rotation
+// launch whose workgroups each pick their tenant's bootstrapping key
+// (k_blind_rotate_*_grp). Timing of the group rotations goes to tenant 0's
+// blind-rotation buckets.
+struct fhe_group {
+  std::vector<fhe_ctx*> ctxs;
+  int device = -1;
+  const c64** d_keys = nullptr;     // [NGAD][T]: tenant t's bsk_fft of gadget g
+  std::vector<const c64*> h_keys;   // what d_keys holds
+  void* ws = nullptr;               // tables | small | (search: ct_v | sign | copy | expanded queries)
+  size_t ws_bytes = 0;
+};
+
+static int gfail(int code, const std::string& msg) { return fail(nullptr, code, "group: " + msg); }
+
+// the group kernel launch_br's choice for gadget `gad` maps to: 1 multi-bit,
+// 2 generic, 0 none (the classic v4 / v4s / two-wave rotations)
+static int grp_kernel_for(const fhe_ctx* ctx, int gad) {
+  const bool fast = gad > 0 && fast_level(ctx->p, gad);
+  const fhe_params p = fast ? fast_params(ctx->p, gad) : ctx->p;
+  if (fast && mb_for(ctx->p, gad)) return p.N == 1024 && p.k == 2 && p.pbs_level <= 8 ? 1 : 0;
+  if (p.N == 1024) return 0;
+  if (((p.N == 256 || p.N == 512) && (p.k == 1 || p.k == 2)) || (p.N == 2048 && p.k == 1)) return 2;
+  return 0;
+}
+static int grp_schedule(const fhe_params& p, int* d, int* sched) {
+  *d = 0;
+  if (p.msg_bits < 4) {
+    for (int r = 0; r < p.msg_bits; ++r) sched[r] = 0;
+    return p.msg_bits;
+  }
+  return sign_schedule(p, d, sched);
+}
+// checks 2 and 3 of fhe_group_create; 2 again at every call (fhe_set_msg_bits)
+static int grp_check_params(const fhe_group* g) {
+  for (size_t t = 1; t < g->ctxs.size(); ++t)
+    if (g->ctxs[t]->device != g->ctxs[0]->device || memcmp(&g->ctxs[t]->p, &g->ctxs[0]->p, sizeof(fhe_params)))
+      return gfail(FHE_E_ARG, "tenant " + std::to_string(t) + " differs from tenant 0 in its device or parameters");
+  int d, sched[64];
+  const int R = grp_schedule(g->ctxs[0]->p, &d, sched);
+  for (int r = 0; r < R; ++r)
+    if (!grp_kernel_for(g->ctxs[0], sched[r]))
+      return gfail(FHE_E_ARG, "round " + std::to_string(r) + " runs the classic rotation (no group kernel)");
+  return FHE_OK;
+}
+static int grp_check_keys(const fhe_group* g) {
+  for (size_t t = 0; t < g->ctxs.size(); ++t)
+    if (!g->ctxs[t]->keys) return gfail(FHE_E_STATE, "tenant " + std::to_string(t) + " has no evaluation keys");
+  if (g->device < 0) return gfail(FHE_E_DEVICE, "host-only contexts");
+  if (hipSetDevice(g->device) != hipSuccess) return gfail(FHE_E_DEVICE, "hipSetDevice failed");
+  return FHE_OK;
+}
+// the key-pointer table follows the contexts (a re-keyed tenant moves its keys)
+static int grp_sync_keys(fhe_group* g) {
+  const size_t T = g->ctxs.size();
+  std::vector<const c64*> k((size_t)NGAD * T);
+  for (int gd = 0; gd < NGAD; ++gd)
+    for (size_t t = 0; t < T; ++t) k[gd * T + t] = gd ? g->ctxs[t]->bskf_fft[gd - 1] : g->ctxs[t]->bsk_fft;
+  if (k == g->h_keys) return FHE_OK;
+  fhe_ctx* c0 = g->ctxs[0];
+  HIPCHK(c0, hipDeviceSynchronize());
+  if (!g->d_keys) HIPCHK(c0, hipMalloc((void**)&g->d_keys, sizeof(c64*) * k.size()));
+  HIPCHK(c0, hipMemcpy(g->d_keys, k.data(), sizeof(c64*) * k.size(), hipMemcpyHostToDevice));
+  g->h_keys = k;
+  return FHE_OK;
+}
+static int grp_ensure_ws(fhe_group* g, size_t bytes) {
+  if (bytes <= g->ws_bytes) return FHE_OK;
+  fhe_ctx* c0 = g->ctxs[0];
+  if (g->ws) {
+    HIPCHK(c0, hipDeviceSynchronize());
+    HIPCHK(c0, hipFree(g->ws));
+    g->ws = nullptr;
+    g->ws_bytes = 0;
+  }
+  if (hipMalloc(&g->ws, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    g->ws = nullptr;
+    return gfail(FHE_E_NOMEM, "workspace: out of device memory (fewer rows per call)");
+  }
+  g->ws_bytes = bytes;
+  return FHE_OK;
+}
+
+int64_t fhe_group_rows(const int64_t* counts, int32_t T, int64_t* starts) {
+  if (!counts || T < 0) return -1;
+  int64_t m = 0;
+  for (int32_t t = 0; t < T; ++t) {
+    if (counts[t] < 0 || counts[t] > ((int64_t)1 << 40)) return -1;
+    if (starts) starts[t] = m;
+    m += (counts[t] + 3) / 4 * 4;
+  }
+  return m;
+}
+
+int fhe_group_create(fhe_ctx* const* ctxs, int32_t T, fhe_group** out) {
+  if (!out) return gfail(FHE_E_ARG, "out is null");
+  *out = nullptr;
+  if (T < 1 || T > 64 || !ctxs) return gfail(FHE_E_ARG, "1 to 64 contexts");
+  for (int32_t t = 0; t < T; ++t) {
+    if (!ctxs[t]) return gfail(FHE_E_ARG, "context " + std::to_string(t) + " is null");
+    for (int32_t u = 0; u < t; ++u)
+      if (ctxs[u] == ctxs[t]) return gfail(FHE_E_ARG, "context " + std::to_string(t) + " repeats context " + std::to_string(u));
+  }
+  fhe_group* g = new fhe_group();
+  g->ctxs.assign(ctxs, ctxs + T);
+  g->device = ctxs[0]->device;
+  int rc = grp_check_params(g);
+  if (!rc) rc = grp_check_keys(g);
+  if (!rc) rc = grp_sync_keys(g);
+  if (rc) {
+    fhe_group_destroy(g);
+    return rc;
+  }
+  *out = g;
+  return FHE_OK;
+}
+
+void fhe_group_destroy(fhe_group* g) {
+  if (!g) return;
+  if (g->device >= 0 && (g->d_keys || g->ws)) {
+    (void)hipSetDevice(g->device);
+    (void)hipFree((void*)g->d_keys);
+    (void)hipFree(g->ws);
+  }
+  delete g;
+}
+
+// one group rotation over the M padded rows on gadget `gad`
+static int launch_br_grp(fhe_group* g, const u64* small, int64_t M, const int32_t* wgt, const BrGrpTenant* ten, BrTv tv,
+                         int mode, u64* ct_v, u64* sign, hipStream_t st, int gad) {
+  fhe_ctx* c0 = g->ctxs[0];
+  const bool fast = gad > 0 && fast_level(c0->p, gad);
+  const fhe_params p = fast ? fast_params(c0->p, gad) : c0->p;
+  const BrGrpTenant* tg = ten + (size_t)(fast ? gad : 0) * g->ctxs.size();
+  ProfAcc& prof = fast ? c0->prof_brf[gad - 1] : c0->prof_br;
+  hipEvent_t e1;
+  prof_begin(c0, prof, st, &e1);
+  const char* name = nullptr;
+  if (grp_kernel_for(c0, gad) == 1) {
+    const dim3 gm((unsigned)(M / 4)), bm(v4::nthreads(4));
+#define MBG(L, B)                                                                                                  \
+  hipLaunchKernelGGL((k_blind_rotate_mb_grp<L, B>), gm, bm, 0, st, small, wgt, tg, p.n, p.pbs_base_log, c0->tw4,   \
+                     c0->psi, tv, mode, ct_v, sign);                                                               \
+  name = "k_blind_rotate_mb_grp<" #L ", " #B ">"
+#define MB64G(L)                                                                                                   \
+  hipLaunchKernelGGL((k_blind_rotate_mb64_grp<L>), gm, bm, 0, st, small, wgt, tg, p.n, p.pbs_base_log, c0->tw4,    \
+                     c0->psi, tv, mode, ct_v, sign);                                                               \
+  name = "k_blind_rotate_mb64_grp<" #L ">"
+    // launch_br's choice among the multi-bit kernels
+    if (!(p.pbs_level <= 2 && p.pbs_level * p.pbs_base_log <= 31)) {
+      switch (p.pbs_level) {
+        case 1: MB64G(1); break;
+        case 2: MB64G(2); break;
+        case 3: MB64G(3); break;
+        case 4: MB64G(4); break;
+        case 5: MB64G(5); break;
+        case 6: MB64G(6); break;
+        case 7: MB64G(7); break;
+        default: MB64G(8); break;
+      }
+    } else if (p.pbs_level == 1 && p.pbs_base_log == 23) {
+      MBG(1, 23);
+    } else if (p.pbs_level == 1) {
+      MBG(1, 0);
+    } else if (p.pbs_base_log == 15) {
+      MBG(2, 15);
+    } else {
+      MBG(2, 0);
+    }
+#undef MBG
+#undef MB64G
+  } else {
+#define BRG(LOGM, K)                                                                                               \
+  hipLaunchKernelGGL((k_blind_rotate_grp<LOGM, K>), dim3((unsigned)M), dim3(64), 0, st, small, wgt, tg, p.n,       \
+                     p.pbs_level, p.pbs_base_log, c0->tw, c0->twist, tv, mode, ct_v, sign);                        \
+  name = "k_blind_rotate_grp<" #LOGM ", " #K ">"
+    if (p.N == 256 && p.k == 1) { BRG(7, 1); }
+    else if (p.N == 256) { BRG(7, 2); }
+    else if (p.N == 512 && p.k == 1) { BRG(8, 1); }
+    else if (p.N == 512) { BRG(8, 2); }
+    else { BRG(10, 1); }
+#undef BRG
+  }
+  prof.kernel = name;
+  prof_end(c0, prof, st, e1, M);
+  HIPCHK(c0, hipGetLastError());
+  return FHE_OK;
+}
+
+// table words before the rows of a group workspace: starts | ends | the
+// per-gadget tenant table | the workgroups' tenants (padded to 16 bytes)
+static size_t grp_table_bytes(size_t T, int64_t M) {
+  return 16 * T + sizeof(BrGrpTenant) * NGAD * T + ((size_t)(M / 4) * 4 + 15) / 16 * 16;
+}
+// The sign extraction over the padded rows: sign_extract's rounds, each T key
+// switches (tenant t's rows, key and workspace) and one group rotation, on
+// the caller's stream. `tables` holds grp_table_bytes.
+static int grp_sign(fhe_group* g, u64* ct_v, const int64_t* counts, const int64_t* starts, int64_t M, u64* sign,
+                    u64* small, void* tables, hipStream_t st) {
+  fhe_ctx* c0 = g->ctxs[0];
+  const fhe_params& p = c0->p;
+  const size_t T = g->ctxs.size(), Wb = fhe_big_lwe_words(&p), Ws = fhe_small_lwe_words(&p);
+  int rc;
+  std::vector<u64> se(2 * T);
+  for (size_t t = 0; t < T; ++t) {
+    se[t] = (u64)starts[t];
+    se[T + t] = (u64)(starts[t] + counts[t]);
+  }
+  u64* d_se = (u64*)tables;
+  BrGrpTenant* ten = (BrGrpTenant*)(d_se + 2 * T);
+  int32_t* wgt = (int32_t*)(ten + (size_t)NGAD * T);
+  if ((rc = store_words(c0, d_se, se.data(), (int64_t)(2 * T), st))) return rc;
+  const int64_t nwg = M / 4, nth = std::max<int64_t>(nwg, (int64_t)(NGAD * T));
+  hipLaunchKernelGGL(k_grp_tables, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, st, g->d_keys,
+                     (const int64_t*)d_se, (int)T, NGAD, nwg, ten, wgt);
+  HIPCHK(c0, hipGetLastError());
+  int d, sched[64], round = 0;
+  grp_schedule(p, &d, sched);
+  auto step = [&](int shift, uint64_t add, BrTv tv, int mode, uint64_t* sg) -> int {
+    for (size_t t = 0; t < T; ++t) {
+      if (!counts[t]) continue;
+      int r = keyswitch_lane(g->ctxs[t], ct_v + (size_t)starts[t] * Wb, counts[t], shift, add,
+                             small + (size_t)starts[t] * Ws, st, 0);
+      if (r) return r;
+    }
+    return launch_br_grp(g, small, M, wgt, ten, tv, mode, ct_v, sg, st, sched[round++]);
+  };
+  return sign_walk(p, d, step, sign);
+}
+
+// what every group call checks first: counts, then parameters, keys, tables
+static int grp_enter(fhe_group* g) {
+  int rc = grp_check_params(g);
+  if (!rc) rc = grp_check_keys(g);
+  if (!rc) rc = grp_sync_keys(g);
+  return rc;
+}
+
+int fhe_sign_group_batch(fhe_group* g, uint64_t* d_ct_v, const int64_t* h_counts, uint64_t* d_sign, void* stream) {
+  if (!g) return gfail(FHE_E_ARG, "null group");
+  const int32_t T = (int32_t)g->ctxs.size();
+  std::vector<int64_t> starts((size_t)T);
+  const int64_t M = fhe_group_rows(h_counts, T, starts.data());  // < 0: null or a count outside [0, 2^40]
+  int64_t total = 0;
+  for (int32_t t = 0; M >= 0 && t < T; ++t) total += h_counts[t];
+  if (M < 0 || total >= ((int64_t)1 << 31))
+    return gfail(FHE_E_ARG, "bad sign arguments (counts null, negative or 2^31 rows and more)");
+  int rc = grp_enter(g);
+  if (rc) return rc;
+  if (M == 0) return FHE_OK;
+  if (!d_ct_v || !d_sign) return gfail(FHE_E_ARG, "null sign buffers");
+  const size_t tb = grp_table_bytes((size_t)T, M);
+  if ((rc = grp_ensure_ws(g, tb + 8 * (size_t)M * fhe_small_lwe_words(&g->ctxs[0]->p)))) return rc;
+  return grp_sign(g, d_ct_v, h_counts, starts.data(), M, d_sign, (u64*)((char*)g->ws + tb), g->ws, (hipStream_t)stream);
+}
+
+int fhe_search_query_group_batch(fhe_group* g, const fhe_group_query* items, int32_t T, void* stream) {
+  if (!g) return gfail(FHE_E_ARG, "null group");
+  if (!items || T != (int32_t)g->ctxs.size()) return gfail(FHE_E_ARG, "one fhe_group_query per tenant");
+  // argument errors first: a group of host-only contexts reports them too
+  std::vector<int64_t> counts((size_t)T), starts((size_t)T);
+  int64_t total = 0;
+  for (int32_t t = 0; t < T; ++t) {
+    const fhe_group_query& q = items[t];
+    if (q.struct_size != (int32_t)sizeof(fhe_group_query))
+      return gfail(FHE_E_ARG, "tenant " + std::to_string(t) + ": fhe_group_query.struct_size is not this library's");
+    if (q.Q < 0) return gfail(FHE_E_ARG, "tenant " + std::to_string(t) + ": Q < 0");
+    counts[t] = 0;
+    if (q.Q == 0) continue;  // sits this call out
+    if (queries_args(g->ctxs[t], q.Q, q.B, q.D)) return FHE_E_ARG;
+    if (q.levels_bit < 0 || q.levels_bit > 8)
+      return gfail(FHE_E_ARG, "tenant " + std::to_string(t) + ": levels_bit outside [0, 8]");
+    counts[t] = q.Q * q.B;
+    total += counts[t];
+    if (total >= ((int64_t)1 << 31)) return gfail(FHE_E_ARG, "2^31 results and more: split the call");
+  }
+  int rc = grp_enter(g);
+  if (rc) return rc;
+  for (int32_t t = 0; t < T; ++t) {
+    const fhe_group_query& q = items[t];
+    if (!q.Q) continue;
+    if ((rc = need_pack_key(g->ctxs[t]))) return rc;
+    if (q.levels_bit > g->ctxs[t]->pk_level)
+      return gfail(FHE_E_ARG, "tenant " + std::to_string(t) + ": levels_bit exceeds the packing key's levels");
+    if (!q.h_mask_key || !q.h_T || !q.d_qbody || !q.d_id0 || !q.d_docs8 || !q.d_w || !q.d_glwe_acc || !q.d_glwe_bit)
+      return gfail(FHE_E_ARG, "tenant " + std::to_string(t) + ": null search arguments");
+  }
+  const int64_t M = fhe_group_rows(counts.data(), T, starts.data());
+  if (M == 0) return FHE_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const fhe_params& p = g->ctxs[0]->p;
+  const size_t Wb = fhe_big_lwe_words(&p), Ws = fhe_small_lwe_words(&p), tb = grp_table_bytes((size_t)T, M);
+  size_t qmax = 0;  // the largest tenant's expanded queries (one at a time, in stream order)
+  for (int32_t t = 0; t < T; ++t) qmax = std::max(qmax, (size_t)items[t].Q * (size_t)items[t].D * Wb);
+  if ((rc = grp_ensure_ws(g, tb + 8 * ((size_t)M * (3 * Wb + Ws) + qmax)))) return rc;
+  u64* small = (u64*)((char*)g->ws + tb);
+  u64* ctv = small + (size_t)M * Ws;
+  u64* sgn = ctv + (size_t)M * Wb;
+  u64* cpy = sgn + (size_t)M * Wb;
+  u64* ctq = cpy + (size_t)M * Wb;
+  // per tenant: expansion and leveled GEMM into its segment, a copy of the
+  // leveled rows (the sign extraction consumes them)
+  for (int32_t t = 0; t < T; ++t) {
+    const fhe_group_query& q = items[t];
+    if (!q.Q) continue;
+    fhe_ctx* ctx = g->ctxs[t];
+    std::vector<int64_t> cs((size_t)q.Q);
+    for (int64_t i = 0; i < q.Q; ++i) cs[(size_t)i] = q.cst - q.h_T[i];
+    if ((rc = fhe_expand_seeded_batch(ctx, q.d_qbody, q.d_id0, q.Q, q.D, q.h_mask_key, ctq, stream))) return rc;
+    u64* seg = ctv + (size_t)starts[t] * Wb;
+    if ((rc = fhe_linear_queries_batch(ctx, ctq, q.Q, q.d_docs8, q.B, q.D, q.d_w, cs.data(), seg, stream))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(cpy + (size_t)starts[t] * Wb, seg, 8 * (size_t)counts[t] * Wb, hipMemcpyDeviceToDevice, st));
+  }
+  if ((rc = grp_sign(g, ctv, counts.data(), starts.data(), M, sgn, small, g->ws, st))) return rc;
+  // tenant t's two packings with its own key: result q B + b in coefficient
+  // (q B + b) mod N of its GLWE (q B + b) / N, as fhe_search_queries_batch
+  for (int32_t t = 0; t < T; ++t) {
+    const fhe_group_query& q = items[t];
+    if (!q.Q) continue;
+    fhe_ctx* ctx = g->ctxs[t];
+    if ((rc = pack_impl(ctx, cpy + (size_t)starts[t] * Wb, counts[t], ctx->pk_level, q.d_glwe_acc, st))) return rc;
+    if ((rc = pack_impl(ctx, sgn + (size_t)starts[t] * Wb, counts[t], q.levels_bit ? q.levels_bit : ctx->pk_level,
+                        q.d_glwe_bit, st)))
+      return rc;
+  }
   return FHE_OK;
 }
 

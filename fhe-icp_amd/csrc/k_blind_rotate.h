@@ -8,19 +8,19 @@
 #include "br_m512.h"
 #include "br_v4.h"
 
-template <int LOGM, int K, class TV = BrTv>
-__global__ void __launch_bounds__(64) k_blind_rotate(const u64* __restrict__ small, int n, int L, int beta,
-                                                     const c64* __restrict__ bsk, const c64* __restrict__ tw,
-                                                     const c64* __restrict__ twist, TV tv, int mode,
-                                                     u64* __restrict__ out, u64* __restrict__ ct_v,
-                                                     u64* __restrict__ refreshed, u64* __restrict__ sign) {
+// one ciphertext (row c) per 64-thread workgroup
+template <int LOGM, int K, class TV>
+__device__ __forceinline__ void br_rotate_row(const u64* __restrict__ small, int n, int L, int beta,
+                                              const c64* __restrict__ bsk, const c64* __restrict__ tw,
+                                              const c64* __restrict__ twist, TV tv, int mode, u64* __restrict__ out,
+                                              u64* __restrict__ ct_v, u64* __restrict__ refreshed,
+                                              u64* __restrict__ sign, const int64_t c) {
   using F = WaveFFT<LOGM>;
   constexpr int M = F::M, S = F::S, N = 2 * M;
   constexpr int LOG2N2 = LOGM + 2;
   __shared__ u64 acc[(K + 1) * N];
   __shared__ c64 lds[F::LDS_ELEMS];
   const int l = threadIdx.x;
-  const int64_t c = blockIdx.x;
   const u64* sm = small + (size_t)c * (n + 1);
   const int R = (K + 1) * L;
 
@@ -95,6 +95,15 @@ __global__ void __launch_bounds__(64) k_blind_rotate(const u64* __restrict__ sma
     }
   }
   if (l == 0) br_emit(mode, acc[K * N], true, tv, (size_t)c * W + K * N, out, ct_v, refreshed, sign);
+}
+
+template <int LOGM, int K, class TV = BrTv>
+__global__ void __launch_bounds__(64) k_blind_rotate(const u64* __restrict__ small, int n, int L, int beta,
+                                                     const c64* __restrict__ bsk, const c64* __restrict__ tw,
+                                                     const c64* __restrict__ twist, TV tv, int mode,
+                                                     u64* __restrict__ out, u64* __restrict__ ct_v,
+                                                     u64* __restrict__ refreshed, u64* __restrict__ sign) {
+  br_rotate_row<LOGM, K, TV>(small, n, L, beta, bsk, tw, twist, tv, mode, out, ct_v, refreshed, sign, blockIdx.x);
 }
 
 // Client-side input path of batch_operations.py:226/:273 + Concrete-ML's
@@ -745,7 +754,8 @@ template <int L, int DBG, int BETA, int AW, class TV = BrTv>
 __device__ __forceinline__ void mb_rotate(const u64* __restrict__ small, int64_t count, int n, int beta,
                                           const c64* __restrict__ bsk, const c64* __restrict__ tw4,
                                           const c64* __restrict__ psi, TV tv, int mode, u64* __restrict__ out,
-                                          u64* __restrict__ ct_v, u64* __restrict__ refreshed, u64* __restrict__ sign) {
+                                          u64* __restrict__ ct_v, u64* __restrict__ refreshed, u64* __restrict__ sign,
+                                          const unsigned wg) {
   using namespace v4;
   constexpr bool A32 = AW == 1, A48 = AW == 2;
   using AT = Acc<A32>;
@@ -768,7 +778,7 @@ __device__ __forceinline__ void mb_rotate(const u64* __restrict__ small, int64_t
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = w / WPC, comp = w - g * WPC;
-  const int64_t c = (int64_t)blockIdx.x * G + g;
+  const int64_t c = (int64_t)wg * G + g;
   c64* slot = xbuf + (g * WPC + comp) * SCR;
   using TS = std::conditional_t<A48, u64, T>;
   TS* sa = reinterpret_cast<TS*>(slot);
@@ -793,7 +803,7 @@ __device__ __forceinline__ void mb_rotate(const u64* __restrict__ small, int64_t
   for (int m = 0; m < NR; ++m) treg[m] = tw4[m * 64 + lane];
   for (int x = tid; x < G * np; x += NT) {
     const int gg = x / np, jj = x - gg * np;
-    const int64_t cc = (int64_t)blockIdx.x * G + gg;
+    const int64_t cc = (int64_t)wg * G + gg;
     uint32_t a1 = 0, a2 = 0, e = 1;
     if (cc < count) {
       const u64* sm = small + (size_t)cc * (n + 1);
@@ -1034,7 +1044,7 @@ __device__ __forceinline__ void mb_rotate(const u64* __restrict__ small, int64_t
     MB_PRIO(br_prio_fine<L>() ? 2 : 0);
     V4_STAMP(11);
     if constexpr ((DBG & 128) != 0)
-      if (blockIdx.x == 0 && w == (DBG >> 8) && j >= 100 && j < 104 && lane < 16) {
+      if (wg == 0 && w == (DBG >> 8) && j >= 100 && j < 104 && lane < 16) {
         unsigned long long t_ = 0;
 #pragma unroll
         for (int k = 0; k < 12; ++k) t_ = lane == k ? stamp_[k] : t_;
@@ -1079,7 +1089,7 @@ __global__ void __launch_bounds__(v4::nthreads(4), 1) k_blind_rotate_mb(const u6
                                                                       const c64* __restrict__ psi, TV tv, int mode,
                                                                       u64* __restrict__ out, u64* __restrict__ ct_v,
                                                                       u64* __restrict__ refreshed, u64* __restrict__ sign) {
-  mb_rotate<L, DBG, BETA, 1, TV>(small, count, n, beta, bsk, tw4, psi, tv, mode, out, ct_v, refreshed, sign);
+  mb_rotate<L, DBG, BETA, 1, TV>(small, count, n, beta, bsk, tw4, psi, tv, mode, out, ct_v, refreshed, sign, blockIdx.x);
 }
 // the deep gadgets (L * beta > 31) on the multi-bit rotation: 48-bit accumulators
 // (FHEICP_MB64_AW = 0: 64-bit ones, A/B builds)
@@ -1094,7 +1104,80 @@ __global__ void __launch_bounds__(v4::nthreads(4), 1) k_blind_rotate_mb64(const 
                                                                         u64* __restrict__ out, u64* __restrict__ ct_v,
                                                                         u64* __restrict__ refreshed,
                                                                         u64* __restrict__ sign) {
-  mb_rotate<L, DBG, 0, FHEICP_MB64_AW, TV>(small, count, n, beta, bsk, tw4, psi, tv, mode, out, ct_v, refreshed, sign);
+  mb_rotate<L, DBG, 0, FHEICP_MB64_AW, TV>(small, count, n, beta, bsk, tw4, psi, tv, mode, out, ct_v, refreshed, sign,
+                                           blockIdx.x);
+}
+
+// ---- group forms: one launch over several key holders ----
+// Rows are T segments, tenant t at start_t = sum_{u<t} 4 ceil(n_u / 4) with
+// n_t real rows, so a four-ciphertext workgroup never straddles two tenants;
+// rows between start_t + n_t and start_{t+1} are padding, neither read nor
+// written. wg_tenant[w] is logical workgroup w's tenant (rows 4w .. 4w+3) and
+// ten[t] that tenant's key for this round's gadget and its end row start_t +
+// n_t, which serves as the rotation's `count`: every row before it in the
+// workgroup is real. Both are read at a workgroup-uniform address (scalar
+// loads), so the state lives in scalar registers only.
+struct BrGrpTenant {
+  const c64* bsk;  // bsk_fft of this round's gadget
+  int64_t end;     // start_t + n_t
+};
+// blockIdx.x -> logical index. Blocks are dealt round-robin over the 8 XCDs;
+// DEAL gives each XCD a contiguous run of logical indices (k_keyswitch_mfma's
+// deal), so a tenant's workgroups, and with them its key, fall on as few
+// XCDs' L2 as possible. The order is for speed only.
+#ifndef FHEICP_GRP_DEAL
+#define FHEICP_GRP_DEAL 1  // 0: identity order (A/B builds)
+#endif
+__device__ __forceinline__ unsigned grp_deal(unsigned bid, unsigned nblk) {
+  if constexpr (FHEICP_GRP_DEAL == 0) return bid;
+  const unsigned xcd = bid & 7, q8 = nblk >> 3, r8 = nblk & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+}
+
+template <int L, int BETA>
+__global__ void __launch_bounds__(v4::nthreads(4), 1) k_blind_rotate_mb_grp(
+    const u64* __restrict__ small, const int32_t* __restrict__ wg_tenant, const BrGrpTenant* __restrict__ ten, int n,
+    int beta, const c64* __restrict__ tw4, const c64* __restrict__ psi, BrTv tv, int mode, u64* __restrict__ ct_v,
+    u64* __restrict__ sign) {
+  const unsigned wg = grp_deal(blockIdx.x, gridDim.x);
+  const BrGrpTenant e = ten[wg_tenant[wg]];
+  mb_rotate<L, 0, BETA, 1, BrTv>(small, e.end, n, beta, e.bsk, tw4, psi, tv, mode, nullptr, ct_v, nullptr, sign, wg);
+}
+template <int L>
+__global__ void __launch_bounds__(v4::nthreads(4), 1) k_blind_rotate_mb64_grp(
+    const u64* __restrict__ small, const int32_t* __restrict__ wg_tenant, const BrGrpTenant* __restrict__ ten, int n,
+    int beta, const c64* __restrict__ tw4, const c64* __restrict__ psi, BrTv tv, int mode, u64* __restrict__ ct_v,
+    u64* __restrict__ sign) {
+  const unsigned wg = grp_deal(blockIdx.x, gridDim.x);
+  const BrGrpTenant e = ten[wg_tenant[wg]];
+  mb_rotate<L, 0, 0, FHEICP_MB64_AW, BrTv>(small, e.end, n, beta, e.bsk, tw4, psi, tv, mode, nullptr, ct_v, nullptr,
+                                           sign, wg);
+}
+// the generic rotation: one row per block, four blocks to a logical workgroup
+template <int LOGM, int K>
+__global__ void __launch_bounds__(64) k_blind_rotate_grp(const u64* __restrict__ small,
+                                                         const int32_t* __restrict__ wg_tenant,
+                                                         const BrGrpTenant* __restrict__ ten, int n, int L, int beta,
+                                                         const c64* __restrict__ tw, const c64* __restrict__ twist,
+                                                         BrTv tv, int mode, u64* __restrict__ ct_v,
+                                                         u64* __restrict__ sign) {
+  const unsigned row = grp_deal(blockIdx.x, gridDim.x);
+  const BrGrpTenant e = ten[wg_tenant[row >> 2]];
+  if ((int64_t)row >= e.end) return;  // padding row
+  br_rotate_row<LOGM, K, BrTv>(small, n, L, beta, e.bsk, tw, twist, tv, mode, nullptr, ct_v, nullptr, sign, row);
+}
+// the two tables of a call: tenant t's key per gadget and end row (ten[g * T +
+// t]), and the tenant of every logical workgroup
+__global__ void k_grp_tables(const c64* const* __restrict__ keys, const int64_t* __restrict__ se, int T, int ngad,
+                             int64_t nwg, BrGrpTenant* __restrict__ ten, int32_t* __restrict__ wg_tenant) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < (int64_t)T * ngad) ten[i] = {keys[i], se[T + i % T]};
+  if (i < nwg) {
+    int t = 0;  // the last tenant whose start is at or before row 4 i and that has rows
+    for (int u = 0; u < T; ++u)
+      if (se[u] <= 4 * i && se[T + u] > se[u]) t = u;
+    wg_tenant[i] = t;
+  }
 }
 
 // ---- classic blind rotation with key-stationary products ---------------------

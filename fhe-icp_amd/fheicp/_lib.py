@@ -34,6 +34,15 @@ class FheParams(C.Structure):
     _fields_ = [("struct_size", C.c_int32)] + [(f, C.c_int32) for f in PARAM_FIELDS]
 
 
+class FheGroupQuery(C.Structure):
+    # one tenant's part of fhe_search_query_group_batch (include/fhe_icp.h):
+    # struct_size first, then the arguments of fhe_search_queries_batch
+    _fields_ = [("struct_size", C.c_int32), ("D", C.c_int32), ("d_qbody", C.c_void_p), ("d_id0", C.c_void_p),
+                ("h_mask_key", C.c_void_p), ("Q", C.c_int64), ("d_docs8", C.c_void_p), ("B", C.c_int64),
+                ("d_w", C.c_void_p), ("cst", C.c_int64), ("h_T", C.c_void_p), ("levels_bit", C.c_int32),
+                ("reserved", C.c_int32), ("d_glwe_acc", C.c_void_p), ("d_glwe_bit", C.c_void_p)]
+
+
 # (name, restype, argtypes) for every symbol declared in include/fhe_icp.h
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -150,6 +159,12 @@ SIGNATURES = [
     ("fhe_compare_ggsws_batch", C.c_int, [_CTXP, _vp, _i32, _i32, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
     ("fhe_search_ggsws_batch", C.c_int, [_CTXP, _vp, _i32, _i32, _vp, _i64, _i64, _i32, _i64, _vp, _i32, _vp, _vp,
                                          _vp]),
+    # several key holders in one batched call
+    ("fhe_group_create", C.c_int, [C.POINTER(C.c_void_p), _i32, C.POINTER(C.c_void_p)]),
+    ("fhe_group_destroy", None, [_vp]),
+    ("fhe_group_rows", _i64, [C.POINTER(_i64), _i32, C.POINTER(_i64)]),
+    ("fhe_sign_group_batch", C.c_int, [_vp, _vp, C.POINTER(_i64), _vp, _vp]),
+    ("fhe_search_query_group_batch", C.c_int, [_vp, _vp, _i32, _vp]),
     # include/fhe_bert.h: the embedding stage's encoder (fheicp.bert)
     ("fhe_bert_create", C.c_int, [_vp, C.c_int, C.POINTER(C.c_void_p)]),
     ("fhe_bert_destroy", None, [_vp]),

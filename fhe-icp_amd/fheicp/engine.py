@@ -788,6 +788,92 @@ class Engine:
         return {"total_ms": ms.value, "launches": nl.value, "items": items.value}
 
 
+def group_rows(counts) -> tuple:
+    """(M, starts) of a group batch (fhe_group_rows): tenant t's counts[t] rows
+    start at sum of the earlier tenants' counts, each rounded up to 4."""
+    n = len(counts)
+    c = (C.c_int64 * max(n, 1))(*[int(x) for x in counts])
+    s = (C.c_int64 * max(n, 1))()
+    M = _lib.lib().fhe_group_rows(c, n, s)
+    if M < 0:
+        raise ValueError("group_rows needs counts >= 0")
+    return int(M), [int(x) for x in s[:n]]
+
+
+class EngineGroup:
+    """Several key holders in one batched call: engines on
+    one device with equal parameters, each with its own evaluation keys. The
+    engines are borrowed and must outlive the group."""
+
+    def __init__(self, engines):
+        self.engines = list(engines)
+        self._L = _lib.lib()
+        arr = (C.c_void_p * max(len(self.engines), 1))(*[e._ctx for e in self.engines])
+        h = C.c_void_p()
+        _lib.check(self._L.fhe_group_create(arr, len(self.engines), C.byref(h)))
+        self._grp = h
+        self.device = self.engines[0].device
+        self.W = self.engines[0].W
+
+    def close(self) -> None:
+        if getattr(self, "_grp", None):
+            self._L.fhe_group_destroy(self._grp)
+            self._grp = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def rows(counts) -> tuple:
+        return group_rows(counts)
+
+    def sign(self, ct_v: torch.Tensor, counts) -> torch.Tensor:
+        """fhe_sign_group_batch: ct_v holds the M padded rows of rows(counts)
+        (consumed); returns M sign rows, the padding rows unwritten."""
+        M, _ = group_rows(counts)
+        if len(counts) != len(self.engines) or ct_v.numel() != M * self.W:
+            raise ValueError(f"{len(counts)} counts and {ct_v.numel() // self.W} rows for {len(self.engines)} tenants "
+                             f"and {M} padded rows")
+        sign = torch.empty((M, self.W), dtype=torch.int64, device=self.device)
+        c = (C.c_int64 * len(counts))(*[int(x) for x in counts])
+        _lib.check(self._L.fhe_sign_group_batch(self._grp, _ptr(ct_v), c, _ptr(sign), _stream(self.device)))
+        return sign
+
+    def search_queries(self, items) -> list:
+        """fhe_search_query_group_batch. items: one per engine, None (the
+        tenant sits this call out) or the arguments of Engine.search_queries
+        as a tuple (qbody, id0, mask_key, docs8, B, D, w, cst, Ts, levels_bit).
+        Returns, per tenant, (glwe_acc, glwe_bit) or None."""
+        if len(items) != len(self.engines):
+            raise ValueError(f"{len(items)} items for {len(self.engines)} tenants")
+        arr = (_lib.FheGroupQuery * len(items))()
+        keep, out = [], []
+        for t, (eng, it) in enumerate(zip(self.engines, items)):
+            arr[t].struct_size = C.sizeof(_lib.FheGroupQuery)
+            if it is None:
+                out.append(None)
+                continue
+            qbody, id0, mask_key, docs8, B, D, w, cst, Ts, levels_bit = it
+            hT, _ = Engine._i64s(Ts)
+            key = Engine._key(mask_key)
+            Q = hT.size
+            shape = (eng.glwe_count(Q * int(B)), (eng.params.k + 1) * eng.params.N)
+            ga = torch.empty(shape, dtype=torch.int64, device=self.device)
+            gb = torch.empty(shape, dtype=torch.int64, device=self.device)
+            keep.append((hT, key, qbody, id0, docs8, w))
+            q = arr[t]
+            q.D, q.Q, q.B, q.cst, q.levels_bit = int(D), Q, int(B), int(cst), int(levels_bit)
+            q.d_qbody, q.d_id0, q.d_docs8, q.d_w = qbody.data_ptr(), id0.data_ptr(), docs8.data_ptr(), w.data_ptr()
+            q.h_mask_key, q.h_T = C.addressof(key), hT.ctypes.data
+            q.d_glwe_acc, q.d_glwe_bit = ga.data_ptr(), gb.data_ptr()
+            out.append((ga, gb))
+        _lib.check(self._L.fhe_search_query_group_batch(self._grp, arr, len(items), _stream(self.device)))
+        return out
+
+
 def u64(t: torch.Tensor) -> np.ndarray:
     """Device int64 tensor -> host uint64 array (bit pattern)."""
     return t.detach().cpu().numpy().view(np.uint64)

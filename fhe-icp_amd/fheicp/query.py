@@ -475,3 +475,156 @@ class QueryServer:
             out.append(pack_replies(ga.cpu().numpy().view(np.uint64), gb.cpu().numpy().view(np.uint64), B, self.P0,
                                     Tc))
         return out
+
+
+# ------------------------------------------------------ several key holders --
+# One evaluation-only host serving tenants that each hold their own keys and
+# their own documents: every tenant keeps a QueryServer; a
+# call that names several of them runs their sign extractions in one group
+# launch sequence (fhe_search_query_group_batch) and answers each tenant in
+# the version-2 reply format above, word for word what its own
+# QueryServer.search_many returns.
+def hub_chunks(sizes: dict, cap: int = MAX_RESULTS) -> list:
+    """sizes: {name: (Q, B)} -> a list of chunks, each a list of (name,
+    range of that tenant's queries), tenants and queries in order. A chunk
+    carries at most max(cap, the largest B) results: a query's B results are
+    never split, and a tenant's piece is as many whole queries as still fit."""
+    if cap < 1:
+        raise ValueError("hub_chunks needs cap >= 1")
+    chunks, cur, used = [], [], 0
+    for name, (Q, B) in sizes.items():
+        Q, B = int(Q), int(B)
+        if Q < 0 or B < 1:
+            raise ValueError(f"tenant {name!r}: hub_chunks needs Q >= 0 and B >= 1")
+        q = 0
+        while q < Q:
+            fit = max(0, cap - used) // B
+            if fit == 0 and cur:          # no room left for one more query: close the chunk
+                chunks.append(cur)
+                cur, used = [], 0
+                continue
+            take = min(Q - q, max(fit, 1))  # an empty chunk takes one query even when B > cap
+            cur.append((name, range(q, q + take)))
+            used += take * B
+            q += take
+    if cur:
+        chunks.append(cur)
+    return chunks
+
+
+class QueryHub:
+    """Tenants with their own keys and documents behind one GPU. The host
+    learns which tenant asked; each tenant's values stay under its own key."""
+
+    def __init__(self, device: int = 0):
+        self.device = device
+        self.tenants = {}       # name -> {"server": QueryServer, "docs8": tensor or None, "B": int}
+        self._group = None
+
+    def add_tenant(self, name, eval_keys, cq, P0: int, scheme=None, server=None):
+        """Builds the tenant's QueryServer from its evaluation keys (or adopts
+        `server`). Every tenant shares the first one's P0 and scheme
+        parameters: ValueError naming the tenant otherwise."""
+        if name in self.tenants:
+            raise ValueError(f"tenant {name!r} is already registered")
+        from .params import params_for_bits
+        want = (scheme if scheme is not None else params_for_bits(int(P0))).with_msg_bits(int(P0)) \
+            if server is None else server.scheme
+        p0 = int(P0) if server is None else int(server.P0)
+        for other, rec in self.tenants.items():
+            s = rec["server"]
+            if int(s.P0) != p0:
+                raise ValueError(f"tenant {name!r}: P0 = {p0} differs from tenant {other!r}'s {int(s.P0)}")
+            if s.scheme != want:
+                raise ValueError(f"tenant {name!r}: scheme parameters differ from tenant {other!r}'s")
+            break
+        if server is None:
+            server = QueryServer(eval_keys, cq, p0, self.device, scheme)
+        self.tenants[name] = {"server": server, "docs8": None, "B": 0}
+        self._group = None
+        return server
+
+    def load(self, name, docs) -> int:
+        """Packs the tenant's documents and keeps them resident; returns B."""
+        rec = self._tenant(name)
+        B = int(docs.shape[0])
+        if B < 1:
+            raise ValueError(f"tenant {name!r}: an empty document store")
+        rec["docs8"], rec["B"] = rec["server"].pack_docs(docs), B
+        return B
+
+    def _tenant(self, name) -> dict:
+        if name not in self.tenants:
+            raise ValueError(f"unknown tenant {name!r}")
+        return self.tenants[name]
+
+    def check_reply(self, name, reply, Q: int) -> dict:
+        """A version-2 reply must be the named tenant's: its P0, its loaded
+        document count, Q queries and the matching size. ValueError otherwise."""
+        rec = self._tenant(name)
+        s = rec["server"]
+        r = unpack_replies(reply, (s.scheme.k + 1) * s.scheme.N, s.scheme.N)
+        if r["P0"] != s.P0 or r["B"] != rec["B"] or r["Q"] != int(Q):
+            raise ValueError(f"tenant {name!r}: reply of {r['Q']} queries x {r['B']} documents at P0 = {r['P0']}, "
+                             f"expected {int(Q)} x {rec['B']} at P0 = {s.P0}")
+        return r
+
+    def group(self):
+        if self._group is None:
+            from .engine import EngineGroup
+            self._group = EngineGroup([rec["server"].engine for rec in self.tenants.values()])
+        return self._group
+
+    def search_many(self, requests: dict) -> dict:
+        """requests: {name: (payloads, min_similarity)} -> {name: [replies]},
+        version-2 replies for the tenant's QueryClient.decrypt_replies, its
+        queries in order. One library call carries at most max(largest B,
+        8192) results (hub_chunks); a tenant alone in a chunk goes through its
+        own QueryServer.search_many."""
+        plan = {}
+        for name, (payloads, min_similarity) in requests.items():
+            rec = self._tenant(name)
+            s = rec["server"]
+            if rec["docs8"] is None:
+                raise ValueError(f"tenant {name!r} has no documents loaded")
+            pls = [unpack_query(p) for p in payloads]
+            try:
+                check_query_batch(pls)
+            except ValueError as e:
+                raise ValueError(f"tenant {name!r}: {e}") from None
+            pl = pls[0]
+            if pl["P0"] != s.P0 or pl["big"] != s.scheme.k * s.scheme.N:
+                raise ValueError(f"tenant {name!r}: query 0 was encrypted under different parameters")
+            if pl["D"] != len(s.cq.model.q_w):
+                raise ValueError(f"tenant {name!r}: query 0 holds {pl['D']} features, the model {len(s.cq.model.q_w)}")
+            ms = thresholds_for(min_similarity, len(pls))
+            w, cst, _ = s.plan(None)
+            plan[name] = {"payloads": list(payloads), "pls": pls, "ms": ms, "Ts": [s.plan(t)[2] for t in ms],
+                          "w": s.engine.to_dev(w), "cst": cst}
+        out = {name: [] for name in requests}
+        names = list(self.tenants)
+        for chunk in hub_chunks({name: (len(plan[name]["pls"]), self.tenants[name]["B"]) for name in plan}):
+            if len(chunk) == 1:
+                name, rng = chunk[0]
+                rec, pn = self.tenants[name], plan[name]
+                out[name] += rec["server"].search_many([pn["payloads"][q] for q in rng], rec["docs8"], rec["B"],
+                                                       [pn["ms"][q] for q in rng])
+                continue
+            items, Tcs = [None] * len(names), {}
+            for name, rng in chunk:
+                rec, pn = self.tenants[name], plan[name]
+                eng, pls = rec["server"].engine, pn["pls"]
+                body = eng.to_dev(np.stack([pls[q]["body"] for q in rng]))
+                ids = eng.to_dev(np.array([pls[q]["id0"] for q in rng], dtype=np.uint64))
+                Tcs[name] = [pn["Ts"][q] for q in rng]
+                items[names.index(name)] = (body, ids, pls[0]["mask_key"], rec["docs8"], rec["B"], pls[0]["D"],
+                                            pn["w"], pn["cst"], Tcs[name], rec["server"].bit_levels)
+            res = self.group().search_queries(items)
+            for name, rng in chunk:
+                ga, gb = res[names.index(name)]
+                rec = self.tenants[name]
+                reply = pack_replies(ga.cpu().numpy().view(np.uint64), gb.cpu().numpy().view(np.uint64), rec["B"],
+                                     rec["server"].P0, Tcs[name])
+                self.check_reply(name, reply, len(rng))
+                out[name].append(reply)
+        return out

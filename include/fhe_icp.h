@@ -689,6 +689,61 @@ int fhe_compare_ggsws_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_l
 int fhe_search_ggsws_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_log, int32_t level, const void* d_docs,
                            int64_t Q, int64_t B, int32_t D, int64_t cst, const int64_t* h_T, int32_t levels_bit,
                            uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream);
+
+/* ---- several key holders in one batched call -------------
+ * A group borrows T contexts (1 <= T <= 64, no null, no repeat), all on one
+ * device and with equal fhe_params (msg_bits included: re-checked at every
+ * call), whose sign schedule runs only rotations that have a group form: the
+ * multi-bit ones at N = 1024, k = 2 and the generic one (every planned set
+ * from P = 4 to 26 and the toy set; a set with a classic round at N = 1024 is
+ * refused, "group: round r runs the classic rotation"). Checks in that order
+ * (FHE_E_ARG, "group" in fhe_last_error(NULL); host-only contexts report them
+ * too), then evaluation keys on every context (FHE_E_STATE). The contexts
+ * must outlive the group; a group is used from one thread at a time, and its
+ * calls use the contexts' key-switch and packing workspaces.
+ *
+ * Row layout of a group batch: T segments, tenant t with counts[t] >= 0 rows
+ * at start_t = sum_{u<t} 4 ceil(counts[u] / 4); fhe_group_rows returns the
+ * padded total M and writes the T starts (host only; -1 for null or negative
+ * counts). Rows start_t + counts[t] .. start_{t+1} - 1 are padding, neither
+ * read nor written. */
+typedef struct fhe_group fhe_group;
+int fhe_group_create(fhe_ctx* const* ctxs, int32_t T, fhe_group** out);
+void fhe_group_destroy(fhe_group* group);
+int64_t fhe_group_rows(const int64_t* counts, int32_t T, int64_t* starts);
+/* fhe_sign_batch over the padded layout (d_ct_v, d_sign: M x (kN+1), d_ct_v
+ * consumed): the same schedule, shifts and test vectors; per round tenant t's
+ * rows take t's key switch, then one rotation launch serves every tenant,
+ * each workgroup with its own tenant's key. On the caller's stream, no
+ * two-half pipelining. sum counts < 2^31; all zero returns FHE_OK. */
+int fhe_sign_group_batch(fhe_group* group, uint64_t* d_ct_v, const int64_t* h_counts, uint64_t* d_sign, void* stream);
+/* One tenant's part of fhe_search_query_group_batch: the arguments of
+ * fhe_search_queries_batch. Q = 0: the tenant sits this call out. */
+typedef struct fhe_group_query {
+  int32_t struct_size;        /* = sizeof(fhe_group_query); else FHE_E_ARG */
+  int32_t D;
+  const uint64_t* d_qbody;    /* Q x D body words */
+  const uint64_t* d_id0;      /* Q stream ids (device) */
+  const uint32_t* h_mask_key; /* 8 words */
+  int64_t Q;
+  const void* d_docs8;        /* fhe_query_docs_pack of the tenant's B documents */
+  int64_t B;
+  const int64_t* d_w;
+  int64_t cst;
+  const int64_t* h_T;         /* Q thresholds (host) */
+  int32_t levels_bit;
+  int32_t reserved;           /* 0 */
+  uint64_t* d_glwe_acc;       /* ceil(Q B / N) x (k+1)N words */
+  uint64_t* d_glwe_bit;
+} fhe_group_query;
+/* The evaluation-only server of fhe_search_queries_batch for the T tenants of
+ * a group (items[t] for context t): per tenant the expansion and leveled GEMM
+ * into its segment, one fhe_sign_group_batch over all segments, then the
+ * tenant's two packings with its own packing key. Tenant t's outputs are word
+ * for word those of fhe_search_queries_batch on its own context (result order
+ * q * B + b). Argument errors (FHE_E_ARG) come before the device and key
+ * checks; a participating tenant without a packing key is FHE_E_STATE. */
+int fhe_search_query_group_batch(fhe_group* group, const fhe_group_query* items, int32_t T, void* stream);
 #ifdef __cplusplus
 }
 #endif

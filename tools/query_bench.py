@@ -57,6 +57,15 @@ calls on the same documents at B = 128 and B = 1024, with the outputs
 compared, and the same at Q = 1; it writes profiles/r13/private_queries.json
 (--no-end-to-end: the leveled step only, gadget (7, 6)).
 
+With --tenants (docs/AB_LOG_r14.md) it measures several key
+holders in one batched call, two-party, at 16 dimensions, n_bits 6 (P0 = 21):
+QueryHub.search_many for 8 tenants x (Q = 1, B = 128), each with its own keys
+and documents, against the eight QueryServer.search calls one after another
+and one tenant's search at B = 1024, 24 steps after 4 warm-up in rotating
+order, with the HIP-event split of each (rotations, key switches, leveled
+step, packings: the profile buckets summed over the tenants' contexts); it
+writes profiles/r14/tenants.json (--tenant-shape T B: another shape).
+
 The floor of the leveled step is its output, B * (kN + 1) * 8 bytes, over the
 6.29 TB/s a float4 copy reaches on the MI355X; `floor_fraction` is that floor
 over the measured time. Prints one JSON line and writes it to --out.
@@ -296,6 +305,105 @@ def multi_query(cq, oq, D: int, n_bits: int, steps: int, warmup: int, Qn: int = 
     out["meets_bar"] = out["meets_bar_a_over_c"] and out["meets_bar_a_over_b"]
     server.engine.close()
     c.engine.close()
+    return out
+
+
+def tenants(cq, oq, D: int, n_bits: int, steps: int, warmup: int, Tn: int = 8, B: int = 128) -> dict:
+    """Several key holders behind one host, two-party, one
+    process, three things interleaved in rotating order: (a) QueryHub.search_many
+    for Tn tenants x (Q = 1, B documents), each with its own keys, (b) the Tn
+    QueryServer.search calls one after another, (c) one tenant's search at
+    Tn * B documents. Host clock around each (reply copies included); per run
+    the HIP-event split into rotations, key switches, leveled step and packings
+    (the profile buckets, summed over the tenants' contexts); parity of (a)'s
+    decrypted replies with (b)'s and the restatement."""
+    import numpy as np
+    import torch
+    from oracle import quant_ref as Q
+    from fheicp.corpus import EncryptedCorpus
+    from fheicp.query import QueryClient, QueryHub
+    from fheicp import _lib
+    B_full = Tn * B
+    hub, clients, corpora = QueryHub(0), [], []
+    names = [f"tenant{t}" for t in range(Tn)]
+    _, docs = Q.make_corpus(D, B_full, seed=21)
+    qs = [Q.make_corpus(D, 1, seed=100 + t)[0] for t in range(Tn)]
+    for t, name in enumerate(names):
+        c = EncryptedCorpus(cq).compile(key_seed=5 + t, device=0, noise_seed=6 + t)
+        client = QueryClient(c, count=B_full, pack_seed=17 + t)
+        hub.add_tenant(name, client.eval_keys(), cq, c.P0)
+        hub.load(name, docs[t * B:(t + 1) * B])                      # every tenant its own documents
+        clients.append(client)
+        corpora.append(c)
+    servers = [hub.tenants[n]["server"] for n in names]
+    docs8 = [hub.tenants[n]["docs8"] for n in names]
+    docs8_full = servers[0].pack_docs(docs)
+    payloads = [clients[t].encrypt_queries(qs[t][None, :]) for t in range(Tn)]
+    engines = [s.engine for s in servers]
+    for e in engines:
+        e.profile(True)
+    buckets = ("blind_rotate", "keyswitch", "linear_query", "pack")
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        sec = time.perf_counter() - t0
+        split = {k: {"ms": 0.0, "launches": 0} for k in buckets}
+        for e in engines:
+            for k in buckets:
+                r = e.profile_read(k)
+                split[k]["ms"] += r["total_ms"]
+                split[k]["launches"] += r["launches"]
+        return sec, out, split
+
+    runs = {"a": lambda: hub.search_many({n: (payloads[t], 0.5) for t, n in enumerate(names)}),
+            "b": lambda: [servers[t].search(payloads[t][0], docs8[t], B, 0.5) for t in range(Tn)],
+            "c": lambda: servers[0].search(payloads[0][0], docs8_full, B_full, 0.5)}
+    orders = ("abc", "cba", "bca", "acb", "cab", "bac")
+    t_ = {k: [] for k in runs}
+    sp = {k: {b: [] for b in buckets} for k in runs}
+    last = {}
+    for i in range(warmup + steps):
+        for k in orders[i % len(orders)]:
+            sec, out, split = timed(runs[k])
+            last[k] = (out, split)
+            if i >= warmup:
+                t_[k].append(sec)
+                for b in buckets:
+                    sp[k][b].append(split[b]["ms"])
+    for e in engines:
+        e.profile(False)
+    parity = exact = True
+    for t, name in enumerate(names):
+        acc_a, below_a = clients[t].decrypt_replies(last["a"][0][name])
+        acc_b, below_b = clients[t].decrypt_reply(last["b"][0][t])
+        parity = parity and bool(torch.equal(acc_a[0], acc_b) and torch.equal(below_a[0], below_b))
+        ref = Q.corpus_accumulate(oq, cq.s_e, n_bits, qs[t], docs[t * B:(t + 1) * B])
+        scores = np.float64(Q.corpus_out_scale(oq, cq.s_e)) * ref.astype(np.float64)
+        exact = exact and bool(np.array_equal(acc_a[0].cpu().numpy(), ref) and
+                               np.array_equal(below_a[0].cpu().numpy(), (scores < 0.5).astype(np.int64)))
+    med = {k: statistics.median(v) * 1e3 for k, v in t_.items()}
+    out = {"tenants": Tn, "Q": 1, "B": B, "B_full": B_full,
+           "a_hub_search_many_ms": med["a"], "a_min_ms": min(t_["a"]) * 1e3,
+           "b_sequential_searches_ms": med["b"], "b_min_ms": min(t_["b"]) * 1e3, "b_per_search_ms": med["b"] / Tn,
+           "c_one_tenant_full_search_ms": med["c"], "c_min_ms": min(t_["c"]) * 1e3,
+           "ratio_a_over_b": med["a"] / med["b"], "meets_bar_a_over_b": med["a"] <= 0.5 * med["b"],
+           "ratio_a_over_c": med["a"] / med["c"],
+           "event_split_ms": {k: {b: statistics.median(v) for b, v in sp[k].items()} for k in runs},
+           "event_split_launches": {k: {b: last[k][1][b]["launches"] for b in buckets} for k in runs},
+           "rotation_kernel_last_group": None,
+           "parity_with_sequential": parity, "bit_exact": exact, "steps": steps, "warmup": warmup,
+           "build": _lib.lib().fhe_build_info().decode()}
+    # the buckets name what ran last, a single-tenant search: one more hub call names the group kernel
+    hub.search_many({n: (payloads[t], 0.5) for t, n in enumerate(names)})
+    out["rotation_kernel_last_group"] = engines[0].kernel_name("blind_rotate_fast")
+    out["meets_bar"] = out["meets_bar_a_over_b"] and parity and exact
+    for e in engines:
+        e.close()
+    for c in corpora:
+        c.engine.close()
     return out
 
 
@@ -675,13 +783,21 @@ def main() -> int:
                          "B = 1024 search, and the batched leveled step against eight single calls at B = 128 "
                          "and 1024; 24 interleaved steps after 4 warm-up; writes profiles/r13/private_queries.json "
                          "(with --no-end-to-end: the leveled step only, no keys)")
+    ap.add_argument("--tenants", action="store_true",
+                    help="several key holders in one batched call (16-dim, n_bits 6, two-party): QueryHub.search_many "
+                         "for 8 tenants x (Q = 1, B = 128) against the eight QueryServer.search calls and one "
+                         "tenant's B = 1024 search, 24 interleaved steps after 4 warm-up, with the HIP-event split "
+                         "per run; writes profiles/r14/tenants.json")
+    ap.add_argument("--tenant-shape", type=int, nargs=2, default=[8, 128], metavar=("T", "B"),
+                    help="--tenants: T tenants of B documents each (default 8 128)")
     ap.add_argument("--out", default=None, help="default profiles/query_bench.json "
                                                 "(--multi-query: profiles/r11/multi_query.json, "
                                                 "--stored-queries: profiles/r12/stored_queries.json, "
                                                 "--private-queries: profiles/r13/private_queries.json)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = str(REPO / "profiles" / ("r11/multi_query.json" if a.multi_query else
+        a.out = str(REPO / "profiles" / ("r14/tenants.json" if a.tenants else
+                                         "r11/multi_query.json" if a.multi_query else
                                          "r12/stored_queries.json" if a.stored_queries else
                                          "r13/private_queries.json" if a.private_queries else "query_bench.json"))
     if a.launches < 20:
@@ -692,6 +808,16 @@ def main() -> int:
         return 2
     from fheicp.engine import Engine
     from fheicp.params import params_for_bits
+    if a.tenants:
+        cq, oq = corpus_quant(16, 6)
+        tn = tenants(cq, oq, 16, 6, steps=24, warmup=4, Tn=a.tenant_shape[0], B=a.tenant_shape[1])
+        res = {"bench": "query_bench --tenants", "device": torch.cuda.get_device_name(0), "D": 16, "n_bits": 6,
+               "P0": cq.worst_msg_bits(), "tenants": tn, "meets_bar": tn["meets_bar"]}
+        line = json.dumps(res)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(line + "\n")
+        print(line)
+        return 0
     if a.multi_query:
         cq, oq = corpus_quant(16, 6)
         mq = multi_query(cq, oq, 16, 6, steps=24, warmup=4)
