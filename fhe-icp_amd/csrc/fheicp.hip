@@ -10,6 +10,8 @@
 //                     the i8 MFMA GEMM of one encrypted query x clear documents
 //   k_pack.h          LWE -> GLWE packing key switch (two-party replies): wide
 //                     digits, key generation, rotation, packed decryption
+//   k_bridge.h        LWE -> LWE bridge key switch (key rotation of stored
+//                     ciphertexts): key generation, mapped digits, scatter
 //   k_extprod.h       both-private search: GGSW query encryption, GLWE document
 //                     digits, Toeplitz byte planes, slot extraction
 //   k_extprod_q.h     both-private search, Q queries in one pass: reversed
@@ -36,6 +38,7 @@
 #include "k_server.h"
 #include "k_query.h"
 #include "k_pack.h"
+#include "k_bridge.h"
 #include "k_extprod.h"
 #include "k_extprod_q.h"
 #include "k_blind_rotate.h"
@@ -110,6 +113,14 @@ struct fhe_ctx {
   void* pack_ws = nullptr;  // digits | zero bodies | the GEMM's count x (k+1)N result
   size_t pack_ws_bytes = 0;
   ProfAcc prof_pack;        // fhe_pack_batch: k_pack_digits + the GEMM + k_pack_rotate
+  // LWE -> LWE bridge key of a key rotation (k_bridge.h): gadget (bk_beta,
+  // bk_level), the key [i][l][kN+1] as exported and its 8 byte planes
+  u64* bk = nullptr;
+  int8_t* bk8 = nullptr;
+  int bk_beta = 0, bk_level = 0;
+  void* bridge_ws = nullptr;  // digits | bodies | the GEMM's count x (kN+1) compact result
+  size_t bridge_ws_bytes = 0;
+  ProfAcc prof_bridge;      // fhe_bridge_batch: k_bridge_digits + the GEMM + k_bridge_scatter
   // both-private search (k_extprod.h): the query's Toeplitz byte planes |
   // zero bodies | the GEMM's G x (k+1)N result, allocated on first use
   void* xp_ws = nullptr;
@@ -565,7 +576,7 @@ void fhe_ctx_destroy(fhe_ctx* ctx) {
                       (void*)ctx->bskf[4], (void*)ctx->bskf_fft[4],
                       (void*)ctx->ksk8, (void*)ctx->ks_ws, (void*)ctx->ks_ws1, (void*)ctx->tw4, (void*)ctx->bsk_fft_v2,
                       (void*)ctx->psi, (void*)ctx->mb_msg, ctx->lq_ws, (void*)ctx->pk, (void*)ctx->pk8,
-                      ctx->pack_ws, ctx->xp_ws, ctx->lsq_cst})
+                      ctx->pack_ws, ctx->xp_ws, ctx->lsq_cst, (void*)ctx->bk, (void*)ctx->bk8, ctx->bridge_ws})
       (void)hipFree(ptr);
     for (hipStream_t s : ctx->lane_st)
       if (s) (void)hipStreamDestroy(s);
@@ -578,6 +589,7 @@ void fhe_ctx_destroy(fhe_ctx* ctx) {
     free_ev(ctx->prof_lq);
     free_ev(ctx->prof_ls);
     free_ev(ctx->prof_pack);
+    free_ev(ctx->prof_bridge);
     free_ev(ctx->prof_xp);
     free_ev(ctx->prof_xq);
   }
@@ -2321,6 +2333,202 @@ int fhe_decrypt_packed_batch(fhe_ctx* ctx, const uint64_t* d_glwe, int64_t count
   return FHE_OK;
 }
 
+// ---- LWE -> LWE bridge key switch of a key rotation (k_bridge.h) --
+// The gadget bounds are the packing key's (int8 digits, tie coins); the noise
+// model is pack_var at count = 1 and the plan pack_plan's at count = 1.
+static int bridge_gadget_args(fhe_ctx* ctx, int32_t beta, int32_t L) {
+  if (!pack_gadget_ok(beta, L))
+    return fail(ctx, FHE_E_ARG, "bridge gadget out of range (1 <= base_log <= 7, 1 <= level <= 8, "
+                                "level * (base_log + 1) <= 62)");
+  return FHE_OK;
+}
+size_t fhe_bridge_key_words(const fhe_params* p, int32_t base_log, int32_t level) {
+  if (!p || !pack_gadget_ok(base_log, level)) return 0;
+  return (size_t)p->k * p->N * level * ((size_t)p->k * p->N + 1);
+}
+int fhe_bridge_plan(const fhe_params* params, double in_var, int32_t* base_log, int32_t* level) {
+  return fhe_pack_plan(params, 1, in_var, base_log, level, nullptr);
+}
+// bytes of the key's 8 byte planes: the column blocks padded to ceil((kN+1) / 16)
+static size_t bridge_plane_bytes(const fhe_params& p, int32_t L) {
+  const size_t big = (size_t)p.k * p.N, NB = (big + 1 + KSM_NB_COLS - 1) / KSM_NB_COLS;
+  return big * L * NB * KSM_NB_COLS * 8;
+}
+// (re)allocate the bridge key's buffers for gadget (beta, L)
+static int bridge_key_alloc(fhe_ctx* ctx, int32_t beta, int32_t L) {
+  const size_t words = fhe_bridge_key_words(&ctx->p, beta, L);
+  if (ctx->bk && fhe_bridge_key_words(&ctx->p, ctx->bk_beta, ctx->bk_level) != words) {
+    HIPCHK(ctx, hipDeviceSynchronize());
+    HIPCHK(ctx, hipFree(ctx->bk));
+    ctx->bk = nullptr;
+    HIPCHK(ctx, hipFree(ctx->bk8));
+    ctx->bk8 = nullptr;
+  }
+  ctx->bk_beta = ctx->bk_level = 0;
+  if (!ctx->bk) {
+    HIPCHK(ctx, hipMalloc(&ctx->bk, 8 * words));
+    if (hipMalloc(&ctx->bk8, bridge_plane_bytes(ctx->p, L)) != hipSuccess) {
+      (void)hipFree(ctx->bk);
+      ctx->bk = nullptr;
+      return fail(ctx, FHE_E_DEVICE, "hipMalloc of the bridge key's byte planes failed");
+    }
+  }
+  return FHE_OK;
+}
+// the key's 8 byte planes in B-fragment order: k_ksk_to_i8 on the layout
+// [i][l][kN+1] with no rounding (the padded columns of the last block are zero)
+static int bridge_key_planes(fhe_ctx* ctx, int32_t beta, int32_t L, hipStream_t st) {
+  const fhe_params& p = ctx->p;
+  const int big = p.k * p.N, K = big * L, n1 = big + 1, NB = (n1 + KSM_NB_COLS - 1) / KSM_NB_COLS;
+  const int64_t tot = (int64_t)K * NB * KSM_NB_COLS;
+  hipLaunchKernelGGL(k_ksk_to_i8, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, ctx->bk, K, big, (int)L, n1,
+                     NB, 0, 8, ctx->bk8);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  ctx->bk_beta = beta;
+  ctx->bk_level = L;
+  return FHE_OK;
+}
+
+int fhe_keygen_bridge_key_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level,
+                              const uint32_t h_key[8], void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  int rc = bridge_gadget_args(ctx, base_log, level);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  ChaKey K;
+  if (!h_s_big_old || !key_arg(h_key, K)) return fail(ctx, FHE_E_ARG, "null bridge keygen arguments");
+  const fhe_params& p = ctx->p;
+  const int big = p.k * p.N;
+  for (int i = 0; i < big; ++i)
+    if (h_s_big_old[i] > 1) return fail(ctx, FHE_E_ARG, "old big key word other than 0 or 1");
+  if ((rc = need_secret(ctx))) return rc;
+  if ((rc = bridge_key_alloc(ctx, base_log, level))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // the old secret lives on the device for this launch only
+  u64* d_old = nullptr;
+  HIPCHK(ctx, hipMalloc(&d_old, 8 * (size_t)big));
+  hipError_t e = hipMemcpyAsync(d_old, h_s_big_old, 8 * (size_t)big, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_keygen_bridge, dim3((unsigned)(big * level)), dim3(256), 0, st, K, big, (int)level,
+                       (int)base_log, p.glwe_noise_bits, ctx->s_big, d_old, ctx->bk);
+    e = hipGetLastError();
+  }
+  const hipError_t e2 = hipStreamSynchronize(st);
+  const hipError_t e3 = hipMemset(d_old, 0, 8 * (size_t)big);
+  const hipError_t e4 = hipFree(d_old);
+  HIPCHK(ctx, e);
+  HIPCHK(ctx, e2);
+  HIPCHK(ctx, e3);
+  HIPCHK(ctx, e4);
+  return bridge_key_planes(ctx, base_log, level, st);
+}
+int fhe_keygen_bridge_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level, uint64_t seed,
+                          void* stream) {
+  const ChaKey K = key_from_seed(seed);
+  return fhe_keygen_bridge_key_key(ctx, h_s_big_old, base_log, level, K.w, stream);
+}
+
+static int need_bridge_key(fhe_ctx* ctx) {
+  int rc = need_device(ctx);
+  if (rc) return rc;
+  if (!ctx->bk_level)
+    return fail(ctx, FHE_E_STATE, "no bridge key: call fhe_keygen_bridge_key or fhe_import_bridge_key");
+  return FHE_OK;
+}
+
+int fhe_export_bridge_key(fhe_ctx* ctx, uint64_t* h_out) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  if (!h_out) return fail(ctx, FHE_E_ARG, "null buffer");
+  int rc = need_bridge_key(ctx);
+  if (rc) return rc;
+  HIPCHK(ctx, hipDeviceSynchronize());
+  HIPCHK(ctx, hipMemcpy(h_out, ctx->bk, 8 * fhe_bridge_key_words(&ctx->p, ctx->bk_beta, ctx->bk_level),
+                        hipMemcpyDeviceToHost));
+  return FHE_OK;
+}
+
+int fhe_import_bridge_key(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint64_t* h_in) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  int rc = bridge_gadget_args(ctx, base_log, level);  // argument errors first
+  if (rc) return rc;
+  if (!h_in) return fail(ctx, FHE_E_ARG, "null buffer");
+  if ((rc = need_device(ctx))) return rc;
+  if ((rc = bridge_key_alloc(ctx, base_log, level))) return rc;
+  HIPCHK(ctx, hipMemcpy(ctx->bk, h_in, 8 * fhe_bridge_key_words(&ctx->p, base_log, level), hipMemcpyHostToDevice));
+  return bridge_key_planes(ctx, base_log, level, nullptr);
+}
+
+// digits -> GEMM on the i8 matrix cores -> copy back, for the Q * B_old rows
+// {q B + b : b < B_old} of d_in (Q x B big LWEs); row r of d_out takes the
+// bridged row r (d_out may be d_in: every digit is formed before the copy).
+// The GEMM is the key switch's kernel on 8 planes with kN + 1 columns, the
+// K split chosen as pack_impl does; it writes a compact count x (kN+1) buffer.
+static int bridge_impl(fhe_ctx* ctx, const uint64_t* d_in, int64_t Q, int64_t B, int64_t B_old, uint64_t* d_out,
+                       hipStream_t st) {
+  const fhe_params& p = ctx->p;
+  const int levels = ctx->bk_level;
+  const int big = p.k * p.N, K = big * levels, KB = K / 64, n1 = big + 1, NB = (n1 + KSM_NB_COLS - 1) / KSM_NB_COLS;
+  const int64_t count = Q * B_old, ncb = (count + 15) / 16;
+  const int64_t ctb = (count + KSM_CTS - 1) / KSM_CTS, ktiles = ctb * NB;
+  if (ncb > 65535 || count > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "bridge batch too large: split the call");
+  const size_t dbytes = (size_t)ncb * 16 * K, bbytes = 8 * (size_t)ncb * 16;
+  const size_t need = dbytes + bbytes + 8 * (size_t)count * n1;
+  if (need > ctx->bridge_ws_bytes) {
+    if (ctx->bridge_ws) {
+      HIPCHK(ctx, hipDeviceSynchronize());
+      HIPCHK(ctx, hipFree(ctx->bridge_ws));
+      ctx->bridge_ws = nullptr;
+      ctx->bridge_ws_bytes = 0;
+    }
+    HIPCHK(ctx, hipMalloc(&ctx->bridge_ws, need));
+    ctx->bridge_ws_bytes = need;
+  }
+  uint32_t* Dg = (uint32_t*)ctx->bridge_ws;
+  u64* body = (u64*)((char*)ctx->bridge_ws + dbytes);
+  u64* M = (u64*)((char*)ctx->bridge_ws + dbytes + bbytes);
+  int S = (int)std::max<int64_t>(1, std::min<int64_t>(KB / KSM_RING, 512 / ktiles));
+  const int kslice = (KB / KSM_RING + S - 1) / S * KSM_RING;
+  S = (KB + kslice - 1) / kslice;
+  if (ktiles * S > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "bridge batch too large: split the call");
+  hipEvent_t e1;
+  prof_begin(ctx, ctx->prof_bridge, st, &e1);
+  ctx->prof_bridge.kernel = "k_keyswitch_mfma<8, 1>";
+  // the digits kernel also zeroes the compact rows the split's atomics add into
+  hipLaunchKernelGGL(k_bridge_digits, dim3((unsigned)(big / 64), (unsigned)ncb), dim3(256), 0, st, d_in, count, B,
+                     B_old, big, ctx->bk_beta, levels, KB, Dg, body, S > 1 ? n1 : 0, M);
+  hipLaunchKernelGGL((k_keyswitch_mfma<8, 1>), dim3((unsigned)(ktiles * S)), dim3(256), 0, st, (const v4i*)Dg,
+                     (const v4i*)ctx->bk8, body, count, n1, NB, KB, 0, S, kslice, M);
+  hipLaunchKernelGGL(k_bridge_scatter, dim3((unsigned)count, (unsigned)((n1 + 255) / 256)), dim3(256), 0, st, M, count,
+                     B, B_old, n1, d_out);
+  prof_end(ctx, ctx->prof_bridge, st, e1, count);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+int fhe_bridge_batch(fhe_ctx* ctx, const uint64_t* d_ct, int64_t count, uint64_t* d_out, void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  // argument errors first: a host-only context reports them too
+  if (count < 0) return fail(ctx, FHE_E_ARG, "bad bridge arguments (count < 0)");
+  if (count > 0 && (!d_ct || !d_out)) return fail(ctx, FHE_E_ARG, "null bridge buffers");
+  int rc = need_bridge_key(ctx);
+  if (rc) return rc;
+  if (count == 0) return FHE_OK;
+  return bridge_impl(ctx, d_ct, 1, count, count, d_out, (hipStream_t)stream);
+}
+
+int fhe_bridge_rows_batch(fhe_ctx* ctx, uint64_t* d_ct, int64_t Q, int64_t B, int64_t B_old, void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  // argument errors first: a host-only context reports them too
+  if (Q < 1 || B < 1 || Q > 0x7fffffffLL || B > 0x7fffffffLL || Q * B > 0x7fffffffLL)
+    return fail(ctx, FHE_E_ARG, "bad bridge rows arguments (Q < 1, B < 1 or Q*B >= 2^31)");
+  if (B_old < 0 || B_old > B) return fail(ctx, FHE_E_ARG, "bad bridge rows arguments (B_old outside [0, B])");
+  if (!d_ct) return fail(ctx, FHE_E_ARG, "null bridge buffers");
+  int rc = need_bridge_key(ctx);
+  if (rc) return rc;
+  if (B_old == 0) return FHE_OK;
+  return bridge_impl(ctx, d_ct, Q, B, B_old, d_ct, (hipStream_t)stream);
+}
+
 // The leveled part of a private-query search, shared by the single-party
 // compare and the two-party server entry: the workspace
 //   ct_v (B big) | sign (B big) | small (B) | v (B) | the query's D expanded
@@ -2600,25 +2808,40 @@ int fhe_compare_seeded_queries_batch(fhe_ctx* ctx, const uint64_t* d_body, const
   return post_leveled_compare_queries(ctx, w, Q, B, d_T, d_acc, d_below, stream);
 }
 
-int fhe_search_seeded_queries_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t B,
-                                    int32_t D, const uint32_t h_mask_key[8], int64_t Q, const int64_t* d_W,
-                                    int64_t cst, const int64_t* h_T, int32_t levels_bit, uint64_t* d_glwe_acc,
-                                    uint64_t* d_glwe_bit, void* stream) {
+// The evaluation-only entry with the first B_old documents under a rotated-out
+// key: their rows {q B + b : b < B_old} of the leveled result
+// are bridged in place before the copy is taken. B_old = 0: no bridge, no
+// bridge key needed.
+int fhe_search_seeded_queries_bridged_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t B,
+                                            int32_t D, const uint32_t h_mask_key[8], int64_t Q, const int64_t* d_W,
+                                            int64_t cst, const int64_t* h_T, int32_t levels_bit, int64_t B_old,
+                                            uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream) {
   int rc = seeded_queries_args(ctx, Q, B, D);  // argument errors first: a host-only context reports them too
   if (rc) return rc;
   if (levels_bit < 0 || levels_bit > 8)
     return fail(ctx, FHE_E_ARG, "bad search seeded queries arguments (levels_bit outside [0, 8])");
   if (!d_body || !d_id0 || !h_mask_key || !d_W || !h_T || !d_glwe_acc || !d_glwe_bit)
     return fail(ctx, FHE_E_ARG, "null search seeded queries arguments");
+  if (B_old < 0 || B_old > B) return fail(ctx, FHE_E_ARG, "bad search seeded queries arguments (B_old outside [0, B])");
   if ((rc = need_eval_keys(ctx))) return rc;
   if ((rc = need_pack_key(ctx))) return rc;
+  if (B_old > 0 && (rc = need_bridge_key(ctx))) return rc;
   if (levels_bit > ctx->pk_level)
     return fail(ctx, FHE_E_ARG, "search seeded queries levels_bit exceeds the packing key's levels");
   QueryWs w;
   int64_t* d_T;
   rc = seeded_queries_leveled(ctx, d_body, d_id0, B, D, h_mask_key, Q, d_W, cst, h_T, true, &w, &d_T, stream);
   if (rc) return rc;
+  if (B_old > 0 && (rc = bridge_impl(ctx, w.ctv, Q, B, B_old, w.ctv, (hipStream_t)stream))) return rc;
   return post_leveled_search(ctx, w, Q * B, levels_bit, d_glwe_acc, d_glwe_bit, stream);
+}
+
+int fhe_search_seeded_queries_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t B,
+                                    int32_t D, const uint32_t h_mask_key[8], int64_t Q, const int64_t* d_W,
+                                    int64_t cst, const int64_t* h_T, int32_t levels_bit, uint64_t* d_glwe_acc,
+                                    uint64_t* d_glwe_bit, void* stream) {
+  return fhe_search_seeded_queries_bridged_batch(ctx, d_body, d_id0, B, D, h_mask_key, Q, d_W, cst, h_T, levels_bit, 0,
+                                                 d_glwe_acc, d_glwe_bit, stream);
 }
 
 // ---- both-private search: GGSW query x GLWE documents (k_extprod.h, §8.7) --
@@ -3169,6 +3392,7 @@ static ProfAcc* prof_bucket(fhe_ctx* ctx, const char* kernel) {
   if (!strcmp(kernel, "linear_query")) return &ctx->prof_lq;
   if (!strcmp(kernel, "linear_seeded")) return &ctx->prof_ls;
   if (!strcmp(kernel, "pack")) return &ctx->prof_pack;
+  if (!strcmp(kernel, "bridge")) return &ctx->prof_bridge;
   if (!strcmp(kernel, "linear_ggsw")) return &ctx->prof_xp;
   if (!strcmp(kernel, "linear_ggsws")) return &ctx->prof_xq;
   return nullptr;

@@ -45,6 +45,8 @@ enum StreamTag : uint32_t {
   TAG_PACK_NOISE = 30,
   TAG_GGSW_MASK = 31,  // a GGSW-encrypted query (fhe_encrypt_ggsw; per-query stream key and id)
   TAG_GGSW_NOISE = 32,
+  TAG_BRIDGE_MASK = 33,  // the LWE -> LWE bridge key of a key rotation (fhe_keygen_bridge_key)
+  TAG_BRIDGE_NOISE = 34,
 };
 
 struct ChaKey {

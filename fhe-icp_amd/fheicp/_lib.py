@@ -152,6 +152,17 @@ SIGNATURES = [
                                                    _vp]),
     ("fhe_search_seeded_queries_batch", C.c_int, [_CTXP, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _vp,
                                                   _vp, _vp]),
+    # stored-ciphertext key rotation: the bridge key switch
+    ("fhe_bridge_key_words", C.c_size_t, [_P, _i32, _i32]),
+    ("fhe_bridge_plan", C.c_int, [_P, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("fhe_keygen_bridge_key_key", C.c_int, [_CTXP, _vp, _i32, _i32, _vp, _vp]),
+    ("fhe_keygen_bridge_key", C.c_int, [_CTXP, _vp, _i32, _i32, _u64, _vp]),
+    ("fhe_export_bridge_key", C.c_int, [_CTXP, _vp]),
+    ("fhe_import_bridge_key", C.c_int, [_CTXP, _i32, _i32, _vp]),
+    ("fhe_bridge_batch", C.c_int, [_CTXP, _vp, _i64, _vp, _vp]),
+    ("fhe_bridge_rows_batch", C.c_int, [_CTXP, _vp, _i64, _i64, _i64, _vp]),
+    ("fhe_search_seeded_queries_bridged_batch", C.c_int, [_CTXP, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32,
+                                                          _i64, _vp, _vp, _vp]),
     ("fhe_glwe_docs_queries_bytes", C.c_size_t, [_P, _i64, _i32, _i32]),
     ("fhe_glwe_docs_queries_pack", C.c_int, [_CTXP, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     ("fhe_ggsws_ws_bytes", C.c_size_t, [_P, _i64, _i64, _i32, _i32]),

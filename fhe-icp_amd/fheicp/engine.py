@@ -46,6 +46,7 @@ class Engine:
         self.Ws = params.n + 1
         self.has_keys = False
         self.pack_gadget = None   # (base_log, level) of the packing key, once one is generated or imported
+        self.bridge_gadget = None  # (base_log, level) of the bridge key (§8.12), once one is generated or imported
 
     def close(self) -> None:
         if getattr(self, "_ctx", None):
@@ -93,6 +94,16 @@ class Engine:
         }
         self._chk(self._L.fhe_export_keys(self._ctx, *(C.c_void_p(out[k].ctypes.data)
                                                        for k in ("s_small", "s_big", "bsk", "ksk"))))
+        return out
+
+    def export_key(self, which: str) -> np.ndarray:
+        """One array of export_keys() alone ("s_small", "s_big", "bsk" or "ksk")."""
+        names = ("s_small", "s_big", "bsk", "ksk")
+        sizes = (self.params.n, self.big, self._L.fhe_bsk_words(C.byref(self._P)),
+                 self._L.fhe_ksk_words(C.byref(self._P)))
+        out = np.zeros(sizes[names.index(which)], np.uint64)
+        self._chk(self._L.fhe_export_keys(self._ctx, *(C.c_void_p(out.ctypes.data) if n == which else None
+                                                       for n in names)))
         return out
 
     def export_fast_bsk(self, which: int = 1) -> np.ndarray:
@@ -443,10 +454,67 @@ class Engine:
         self._chk(self._L.fhe_import_pack_key(self._ctx, int(base_log), int(level), C.c_void_p(a.ctypes.data)))
         self.pack_gadget = (int(base_log), int(level))
 
+    # ------- stored-ciphertext key rotation: the bridge key switch (§8.12) --
+    def bridge_key_words(self, base_log: int, level: int) -> int:
+        return int(self._L.fhe_bridge_key_words(C.byref(self._P), int(base_log), int(level)))
+
+    def keygen_bridge_key(self, s_big_old, base_log: int, level: int, key=None, seed: int | None = None) -> None:
+        """Generate the bridge key from the old big key s_big_old (kN words of
+        0/1, export_keys()["s_big"] of the old context) to this context's
+        secret (fhe_keygen_bridge_key[_key]); `key` is a 256-bit ChaCha20 key
+        (os.urandom when neither is given), `seed` the 64-bit test form."""
+        s = np.ascontiguousarray(s_big_old, dtype=np.uint64).reshape(-1)
+        if s.size != self.big:
+            raise ValueError(f"the old big key holds {s.size} words, these parameters {self.big}")
+        sp = C.c_void_p(s.ctypes.data)
+        if seed is not None:
+            rc = self._L.fhe_keygen_bridge_key(self._ctx, sp, int(base_log), int(level), C.c_uint64(seed),
+                                               _stream(self.device))
+        else:
+            import os
+            rc = self._L.fhe_keygen_bridge_key_key(self._ctx, sp, int(base_log), int(level),
+                                                   self._key(key if key is not None else os.urandom(32)),
+                                                   _stream(self.device))
+        self._chk(rc)
+        self.bridge_gadget = (int(base_log), int(level))
+
+    def export_bridge_key(self) -> np.ndarray:
+        if not self.bridge_gadget:
+            raise _lib.FheError("FHE_E_STATE: no bridge key")
+        out = np.zeros(self.bridge_key_words(*self.bridge_gadget), np.uint64)
+        self._chk(self._L.fhe_export_bridge_key(self._ctx, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def import_bridge_key(self, base_log: int, level: int, key) -> None:
+        a = np.ascontiguousarray(key, dtype=np.uint64)
+        if a.size != self.bridge_key_words(base_log, level):
+            raise ValueError("bridge key size does not match its gadget and these parameters")
+        self._chk(self._L.fhe_import_bridge_key(self._ctx, int(base_log), int(level), C.c_void_p(a.ctypes.data)))
+        self.bridge_gadget = (int(base_log), int(level))
+
+    def bridge(self, ct: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Big LWEs under the old key -> under this context's key
+        (fhe_bridge_batch); out may be ct."""
+        n = ct.numel() // self.W
+        if out is None:
+            out = self.empty_big(n)
+        self._chk(self._L.fhe_bridge_batch(self._ctx, _ptr(ct), n, _ptr(out), _stream(self.device)))
+        return out
+
+    def bridge_rows(self, ct: torch.Tensor, Q: int, B: int, b_old: int) -> torch.Tensor:
+        """fhe_bridge_rows_batch: in place on rows {q B + b : b < b_old} of a
+        query-major Q x B result."""
+        if ct.numel() < int(Q) * int(B) * self.W:
+            raise ValueError(f"{ct.numel() // self.W} ciphertexts for {Q} x {B} rows")
+        self._chk(self._L.fhe_bridge_rows_batch(self._ctx, _ptr(ct), int(Q), int(B), int(b_old),
+                                                _stream(self.device)))
+        return ct
+
     def export_eval_keys(self) -> dict:
         """Everything a server needs and nothing more, as numpy arrays: bsk,
         ksk, every present gadget's key (gadget_bsk1..5) and, when one was
-        generated, the packing key with its gadget (pack_key, pack_gadget)."""
+        generated, the packing key with its gadget (pack_key, pack_gadget) and
+        the bridge key with its (bridge_key, bridge_gadget)."""
         from .params import gadget_level
         p = self.params
         out = {"bsk": np.zeros(self._L.fhe_bsk_words(C.byref(self._P)), np.uint64),
@@ -459,6 +527,9 @@ class Engine:
         if self.pack_gadget:
             out["pack_key"] = self.export_pack_key()
             out["pack_gadget"] = np.array(self.pack_gadget, dtype=np.int64)
+        if self.bridge_gadget:
+            out["bridge_key"] = self.export_bridge_key()
+            out["bridge_gadget"] = np.array(self.bridge_gadget, dtype=np.int64)
         return out
 
     def import_eval_keys(self, d: dict) -> None:
@@ -480,6 +551,9 @@ class Engine:
         if "pack_key" in d:
             b, L = (int(x) for x in np.asarray(d["pack_gadget"]).reshape(2))
             self.import_pack_key(b, L, d["pack_key"])
+        if "bridge_key" in d:
+            b, L = (int(x) for x in np.asarray(d["bridge_gadget"]).reshape(2))
+            self.import_bridge_key(b, L, d["bridge_key"])
 
     def glwe_count(self, count: int) -> int:
         return -(-int(count) // self.params.N)
@@ -594,10 +668,24 @@ class Engine:
         return acc, below
 
     def search_seeded_queries(self, body: torch.Tensor, id0: torch.Tensor, mask_key, W: torch.Tensor, cst: int, Ts,
-                              levels_bit: int = 0):
+                              levels_bit: int = 0, b_old: int = 0):
         """fhe_search_seeded_queries_batch: the evaluation-only form;
-        (glwe_acc, glwe_bit), each ceil(Q B / N) x (k+1)N words."""
+        (glwe_acc, glwe_bit), each ceil(Q B / N) x (k+1)N words. b_old > 0:
+        the first b_old documents are under a rotated-out key and go through
+        the bridge key (fhe_search_seeded_queries_bridged_batch, §8.12)."""
         B, D = body.shape
+        if b_old:
+            keep, hT = self._i64s(Ts)
+            Q = keep.size
+            if tuple(W.shape) != (Q, D):
+                raise ValueError(f"weights {tuple(W.shape)} for {Q} thresholds of {D} features")
+            shape = (self.glwe_count(Q * B), (self.params.k + 1) * self.params.N)
+            ga = torch.empty(shape, dtype=torch.int64, device=self.device)
+            gb = torch.empty(shape, dtype=torch.int64, device=self.device)
+            self._chk(self._L.fhe_search_seeded_queries_bridged_batch(
+                self._ctx, _ptr(body), _ptr(id0), int(B), int(D), self._key(mask_key), Q, _ptr(W), int(cst), hT,
+                int(levels_bit), int(b_old), _ptr(ga), _ptr(gb), _stream(self.device)))
+            return ga, gb
         keep, hT = self._i64s(Ts)
         Q = keep.size
         if tuple(W.shape) != (Q, D):

@@ -493,6 +493,22 @@ def pack_plan(p: SchemeParams, count: int, in_var: float = 0.0):
     return b, L, lb
 
 
+def bridge_var(p: SchemeParams, base_log: int, level: int) -> float:
+    """Variance the LWE -> LWE bridge key switch of a key rotation adds to a
+    phase, in units of the integer words: pack_var at
+    count = 1 (kN L key rows through the digits, plus the rounding of the kN
+    mask words)."""
+    return pack_var(p, 1, base_log, level)
+
+
+def bridge_plan(p: SchemeParams, in_var: float = 0.0):
+    """(base_log, level) of the bridge key (fhe_bridge_plan): pack_plan(p, 1,
+    in_var)'s gadget. The packing key that follows is planned with
+    in_var + bridge_var / 2^128."""
+    b, L, _ = pack_plan(p, 1, in_var)
+    return b, L
+
+
 def extprod_var(p: SchemeParams, w_norm2: float, base_log: int, level: int) -> float:
     """Variance of an extracted phase of the GGSW x GLWE product, in units of
     the integer words (fheicp.hip extprod_var): the rows'

@@ -5,7 +5,9 @@ searched without decryption) with its two roles in two contexts:
 
   * CorpusClient, the key holder: encrypts documents (EncryptedCorpus's
     encrypt_docs / payloads), hands out evaluation keys with a packing key and
-    decrypts replies;
+    decrypts replies; rotate() makes the next generation's client with a
+    bridge key, so the host keeps searching the documents stored under the
+    old key without re-encryption (DESIGN.md §8.12);
   * CorpusServer, the host: holds evaluation keys, the public mask key, the
     CorpusQuant and P0 only. It keeps a client's encrypted documents resident
     and scores Q CLEAR queries against them in one pass per chunk
@@ -40,6 +42,18 @@ def leveled_in_var(cq: CorpusQuant, P0: int, scheme) -> float:
     return bound * bound * _tuniform_var(scheme.glwe_noise_bits) / 2.0 ** 128
 
 
+def key_fingerprint(ksk) -> str:
+    """16 hex digits naming a key generation: sha256 over the KSK words (public
+    evaluation-key material, different for every secret key)."""
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(ksk, dtype=np.uint64).tobytes()).hexdigest()[:16]
+
+
+def _fp(v) -> str:
+    """A fingerprint entry of an evaluation-key dict (str or a numpy string array) -> str."""
+    return str(np.asarray(v).reshape(-1)[0])
+
+
 def parse_replies(replies, P0: int, glwe_words: int | None = None, N: int | None = None) -> list:
     """The list CorpusServer.search_many returns (or one version-2 reply) ->
     unpacked replies, each with a width in [4, P0] (its "P0" field is the
@@ -59,33 +73,104 @@ class CorpusClient:
     """The key holder of the stored-ciphertext mode: owns the secret context of
     a compiled EncryptedCorpus."""
 
-    def __init__(self, corpus: EncryptedCorpus, count: int = 1024, in_var: float | None = None, pack_seed=None):
+    def __init__(self, corpus: EncryptedCorpus, count: int = 1024, in_var: float | None = None, pack_seed=None,
+                 extra_var: float = 0.0, next_id: int | None = None):
         """Generates the packing key planned once at P0 (at P < P0 the margin
         2^(63 - P) / sigma only grows) for replies of up to `count` results per
         GLWE. in_var defaults to leveled_in_var, the l1 bound of this mode's
-        weights (pack_seed: the 64-bit test form)."""
+        weights (pack_seed: the 64-bit test form). extra_var (torus units) is
+        added to the plan's input variance: rotate() passes the bridge's.
+        next_id: where this client's default stream ids start (rotate()
+        continues after the old client's; None: random ids)."""
         from .params import pack_plan, pack_sigmas
         corpus._need()
         self.corpus = corpus
         self.cq, self.P0 = corpus.cq, corpus.P0
         scheme = corpus.scheme.with_msg_bits(self.P0)
+        self.count = int(count)
         self.in_var = leveled_in_var(self.cq, self.P0, scheme) if in_var is None else float(in_var)
-        self.base_log, self.level, self.bit_levels = pack_plan(scheme, count, self.in_var)
+        self.pack_in_var = self.in_var + float(extra_var)
+        self.base_log, self.level, self.bit_levels = pack_plan(scheme, count, self.pack_in_var)
         #: the plan's margin in sigmas (below 9.2 when no gadget reaches the bar)
-        self.margin = pack_sigmas(scheme, count, self.in_var, self.base_log, self.level, 63 - self.P0)
+        self.margin = pack_sigmas(scheme, count, self.pack_in_var, self.base_log, self.level, 63 - self.P0)
         corpus.engine.keygen_pack(self.base_log, self.level, seed=pack_seed)
+        self.next_id = None if next_id is None else int(next_id) % 2 ** 64
+        self._id_end = 0 if next_id is None else self.next_id  # one past the largest stream id handed out
+        self.bridge_gadget = None  # (base_log, level) of the bridge key and the fingerprint of the
+        self.bridge_from = None    # generation it comes from, once rotate() made this client
+        self._key_id = None
+
+    def _note_ids(self, ids, D: int) -> None:
+        if len(ids):
+            self._id_end = max(self._id_end, int(np.max(ids)) + int(D))
 
     def encrypt_docs(self, docs, id0=None):
-        return self.corpus.encrypt_docs(docs, id0)
+        """EncryptedCorpus.encrypt_docs; a rotated client's default ids are
+        consecutive runs of D after every id of the generations before it."""
+        docs = np.ascontiguousarray(docs)
+        B, D = docs.shape
+        if id0 is None and self.next_id is not None:
+            id0 = (np.uint64(self.next_id) + np.arange(B, dtype=np.uint64) * np.uint64(D))
+            self.next_id = (self.next_id + B * D) % 2 ** 64
+        bodies, ids = self.corpus.encrypt_docs(docs, id0)
+        self._note_ids(ids, D)
+        return bodies, ids
+
+    @property
+    def id_end(self) -> int:
+        """One past the largest stream id this client (or, for a rotated
+        client, any generation before it) has handed out, modulo 2^64."""
+        return self._id_end % 2 ** 64
+
+    @property
+    def key_id(self) -> str:
+        """This generation's fingerprint (key_fingerprint of its KSK)."""
+        if self._key_id is None:
+            self._key_id = key_fingerprint(self.corpus.engine.export_key("ksk"))
+        return self._key_id
+
+    def rotate(self, key_seed=None, count: int | None = None, bridge_from: "CorpusClient | None" = None,
+               device: int | None = None, pack_seed=None, bridge_seed=None, noise_seed=None) -> "CorpusClient":
+        """Key rotation without re-encryption -> the next
+        generation's client: a new EncryptedCorpus with the same CorpusQuant,
+        scheme and mask key and fresh keys, a bridge key from bridge_from's
+        big key (default: this client; it must still hold its secret) to the
+        new one, and a packing key planned with the bridge's variance added.
+        Its eval_keys() carry bridge_key, bridge_gadget and bridge_from; its
+        default stream ids continue after this client's. The *_seed arguments
+        are the 64-bit test forms."""
+        from .params import bridge_plan, bridge_var
+        src = self if bridge_from is None else bridge_from
+        src.corpus._need()
+        old = src.corpus.engine
+        scheme = self.corpus.scheme.with_msg_bits(self.P0)
+        new_corpus = EncryptedCorpus(self.cq, self.corpus.scheme)
+        dev = old.device.index if device is None else device
+        new_corpus.compile(key_seed=key_seed, device=dev, mask_key=self.corpus.mask_key, noise_seed=noise_seed)
+        b, L = bridge_plan(scheme, self.in_var)
+        new = CorpusClient(new_corpus, count=self.count if count is None else count, in_var=self.in_var,
+                           pack_seed=pack_seed, extra_var=bridge_var(scheme, b, L) / 2.0 ** 128,
+                           next_id=max(self.id_end, src.id_end))
+        s_old = old.export_key("s_big")
+        new_corpus.engine.keygen_bridge_key(s_old, b, L, seed=bridge_seed)
+        s_old[:] = 0
+        new.bridge_gadget = (b, L)
+        new.bridge_from = src.key_id
+        return new
 
     def payloads(self, bodies, ids):
         return self.corpus.payloads(bodies, ids)
 
     def eval_keys(self) -> dict:
         """What the host gets: bsk, ksk, the gadgets' keys, the packing key
-        with its gadget and the bit prefix. No secret key."""
+        with its gadget and the bit prefix, and this generation's fingerprint
+        (key_id); after rotate() also bridge_key, bridge_gadget and
+        bridge_from, the old generation's fingerprint. No secret key."""
         d = self.corpus.engine.export_eval_keys()
         d["pack_bit_levels"] = np.array([self.bit_levels], dtype=np.int64)
+        d["key_id"] = np.array([key_fingerprint(d["ksk"])])
+        if self.bridge_from is not None:
+            d["bridge_from"] = np.array([self.bridge_from])
         return d
 
     def decrypt_replies(self, replies):
@@ -115,7 +200,6 @@ class CorpusServer:
     only. Honest-but-curious: it runs the search as written."""
 
     def __init__(self, eval_keys: dict, cq: CorpusQuant, P0: int, mask_key, device: int = 0, scheme=None):
-        from .engine import Engine
         if "pack_key" not in eval_keys:
             raise ValueError("the evaluation keys hold no packing key")
         self.cq, self.P0 = cq, int(P0)
@@ -124,10 +208,19 @@ class CorpusServer:
             raise ValueError(f"P0 = {self.P0} does not match the model's worst-case width {self._plan.P0}")
         self.scheme = self._plan.scheme
         self.mask_key = np.ascontiguousarray(mask_key, dtype=np.uint32).reshape(8).copy()
-        self.engine = Engine(self.scheme, device)
+        self.engine = self._make_engine(device)
         self.engine.import_eval_keys(eval_keys)
         self.bit_levels = int(np.asarray(eval_keys.get("pack_bit_levels", [0])).reshape(-1)[0])
         self.body = self.ids = None
+        # key rotation (§8.12): the resident documents b < b_old are under the
+        # generation old_key_id and go through the bridge key
+        self.key_id = _fp(eval_keys["key_id"]) if "key_id" in eval_keys else key_fingerprint(eval_keys["ksk"])
+        self.b_old = 0
+        self.old_key_id = None
+
+    def _make_engine(self, device):
+        from .engine import Engine
+        return Engine(self.scheme, device)
 
     @classmethod
     def from_npz(cls, path: str, cq: CorpusQuant, P0: int, mask_key, device: int = 0, scheme=None) -> "CorpusServer":
@@ -142,7 +235,59 @@ class CorpusServer:
         if bodies.shape[1] != len(self.cq.model.q_w):
             raise ValueError(f"documents hold {bodies.shape[1]} features, the model {len(self.cq.model.q_w)}")
         self.body, self.ids = self.engine.to_dev(bodies), self.engine.to_dev(ids)
+        self.b_old, self.old_key_id = 0, None
         return int(ids.size)
+
+    def _check_docs(self, bodies, ids):
+        bodies = np.ascontiguousarray(bodies, dtype=np.uint64)
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        if bodies.ndim != 2 or bodies.shape[0] != ids.size or bodies.shape[0] < 1:
+            raise ValueError("needs bodies [B, D] and B stream ids, B >= 1")
+        if bodies.shape[1] != len(self.cq.model.q_w):
+            raise ValueError(f"documents hold {bodies.shape[1]} features, the model {len(self.cq.model.q_w)}")
+        return bodies, ids
+
+    def append(self, bodies, ids) -> int:
+        """Add documents encrypted under the CURRENT key after the resident
+        ones (old-generation documents stay first); -> the resident count."""
+        import torch
+        if self.body is None:
+            return self.load(bodies, ids)
+        bodies, ids = self._check_docs(bodies, ids)
+        self.body = torch.cat([self.body, self.engine.to_dev(bodies)]).contiguous()
+        self.ids = torch.cat([self.ids, self.engine.to_dev(ids)]).contiguous()
+        return int(self.ids.shape[0])
+
+    def rekey(self, eval_keys: dict) -> None:
+        """Key rotation (§8.12): install the next generation's evaluation keys
+        and bridge key (CorpusClient.rotate(...).eval_keys()). Every resident
+        document becomes old-generation. One old generation is resident at a
+        time: with old-generation documents already resident, the bridge must
+        come from THEIR generation (rotate(bridge_from=...)) and every
+        resident document must be of it."""
+        if "pack_key" not in eval_keys:
+            raise ValueError("the evaluation keys hold no packing key")
+        B = 0 if self.body is None else int(self.body.shape[0])
+        if B:
+            if "bridge_key" not in eval_keys or "bridge_from" not in eval_keys:
+                raise ValueError("documents are resident and the evaluation keys hold no bridge key")
+            src = _fp(eval_keys["bridge_from"])
+            if self.b_old > 0:
+                if src != self.old_key_id:
+                    raise ValueError(f"old-generation documents of key {self.old_key_id} are resident; the bridge "
+                                     f"key comes from {src} (rotate(bridge_from=...) needs their generation)")
+                if self.b_old != B:
+                    raise ValueError("documents of two generations are resident: no chained bridges, reload the "
+                                     "newer ones under the new key")
+            elif src != self.key_id:
+                raise ValueError(f"the resident documents are under key {self.key_id}; the bridge key comes "
+                                 f"from {src}")
+        self.engine.import_eval_keys(eval_keys)
+        self.bit_levels = int(np.asarray(eval_keys.get("pack_bit_levels", [0])).reshape(-1)[0])
+        if B and self.b_old == 0:
+            self.old_key_id = self.key_id
+        self.b_old = B
+        self.key_id = _fp(eval_keys["key_id"]) if "key_id" in eval_keys else key_fingerprint(eval_keys["ksk"])
 
     def search_many(self, queries, min_similarity=None) -> list:
         """Q clear queries against the resident corpus -> a LIST of version-2
@@ -160,7 +305,7 @@ class CorpusServer:
             Wr, cst, Ts, P = self._plan.plan_many(queries[ch.start:ch.stop], [ts[q] for q in ch])
             eng.set_msg_bits(P)
             ga, gb = eng.search_seeded_queries(self.body, self.ids, self.mask_key, eng.to_dev(Wr), cst, Ts,
-                                               self.bit_levels)
+                                               self.bit_levels, b_old=self.b_old)
             out.append(pack_replies(ga.cpu().numpy().view(np.uint64), gb.cpu().numpy().view(np.uint64), B, P, Ts))
         return out
 

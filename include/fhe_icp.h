@@ -564,6 +564,8 @@ int fhe_stream_sync(fhe_ctx* ctx, void* stream);
  * (the fused client encryption + leveled dot), "linear_query" (the
  * private-query leveled step: query planes + GEMM, one bracket around both)
  * "pack" (the packing key switch: digits + GEMM + rotation, one bracket),
+ * "bridge" (the bridge key switch of rotated documents: digits + GEMM +
+ * scatter, one bracket),
  * "linear_ggsw" (the both-private leveled step: Toeplitz planes + GEMM +
  * slot extraction, one bracket), "linear_ggsws" (the same step of the batched
  * entries: GGSW byte planes + the transposed GEMM + slot extraction) or
@@ -645,6 +647,67 @@ int fhe_search_seeded_queries_batch(fhe_ctx* ctx, const uint64_t* d_body, const 
                                     int32_t D, const uint32_t h_mask_key[8], int64_t Q, const int64_t* d_W,
                                     int64_t cst, const int64_t* h_T, int32_t levels_bit, uint64_t* d_glwe_acc,
                                     uint64_t* d_glwe_bit, void* stream);
+
+/* ---- stored-ciphertext key rotation: bridge key switch ----
+ * After a key rotation the stored seeded LWEs stay under the old big key. The
+ * leveled step of the stored-ciphertext search is a clear-weight combination
+ * of them, so its output is one big LWE per (query, document) under the OLD
+ * key; one LWE -> LWE key switch with a bridge key (the old big key encrypted
+ * under the new one) turns it into a ciphertext under the NEW key, and the
+ * rest of the search runs with the new evaluation keys. No re-encryption, no
+ * larger payloads; the host sees neither secret.
+ *
+ * Bridge key, gadget (base_log beta, level L; the packing gadget's bounds):
+ * row (i, l), i < kN, l = 1..L, is an LWE under the new big key (dimension kN)
+ * of the constant s_old[i] * 2^(64 - beta l), TUniform(glwe_noise_bits) noise,
+ * ChaCha20 stream tags 33/34; layout [i][l][kN+1], fhe_bridge_key_words =
+ * kN * L * (kN + 1) words (0 for a null params or a bad gadget). The bridge
+ * of (a, b) is (0, .., 0, b) - sum_i sum_l d_{i,l} BK[i][l], d the balanced
+ * digits of a_i (fhe_pack_batch's). It adds, in integer-word units,
+ *   var_bridge = kN L ((B^2 + 2) / 12) tuniform_var(glwe_noise_bits)
+ *                + (1 + kN / 2) 2^(2 (64 - beta L)) / 12,
+ * fhe_pack_plan's model at count = 1; fhe_bridge_plan is fhe_pack_plan(params,
+ * 1, in_var)'s gadget (host only; fheicp.params.bridge_plan is the same
+ * function). Plan the packing key that follows with in_var + var_bridge / 2^128.
+ *
+ * Check order in every entry: argument errors (FHE_E_ARG: bad gadget, null
+ * pointers, B_old outside [0, B], a key word other than 0 or 1) are reported
+ * first, on host-only contexts too; then the device; then FHE_E_STATE ("no
+ * bridge key", or a missing secret for the key generation). */
+size_t fhe_bridge_key_words(const fhe_params* params, int32_t base_log, int32_t level);
+int fhe_bridge_plan(const fhe_params* params, double in_var, int32_t* base_log, int32_t* level);
+/* Generate the context's bridge key FROM the old big key h_s_big_old (kN host
+ * words of 0/1, as fhe_export_keys writes s_big) TO the context's own secret
+ * key (needed: FHE_E_STATE on an evaluation-only context). Replaces any
+ * earlier bridge key. The device copy of the old key is zeroed and freed
+ * before the call returns. */
+int fhe_keygen_bridge_key_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level,
+                              const uint32_t h_key[8], void* stream);
+int fhe_keygen_bridge_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level, uint64_t seed,
+                          void* stream);
+/* Host copy of the bridge key / install one (converted once to byte planes
+ * for the i8 matrix cores). Both work on an evaluation-only context. */
+int fhe_export_bridge_key(fhe_ctx* ctx, uint64_t* h_out);
+int fhe_import_bridge_key(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint64_t* h_in);
+/* Bridge `count` contiguous big LWEs (kN+1 words each) from the old key to the
+ * context's key; d_out may be d_ct. Needs only the bridge key. Bit-exact.
+ * Timing goes to the "bridge" profile bucket. */
+int fhe_bridge_batch(fhe_ctx* ctx, const uint64_t* d_ct, int64_t count, uint64_t* d_out, void* stream);
+/* The same in place on the rows {q B + b : b < B_old} of a query-major Q x B
+ * result (fhe_linear_seeded_queries_batch's d_out, the first B_old documents
+ * under the old key): Q runs of B_old rows, not one block. Q >= 1, B >= 1,
+ * 0 <= B_old <= B, Q * B < 2^31; every other row is left as it is, B_old = 0
+ * does nothing. What fhe_search_seeded_queries_bridged_batch runs. */
+int fhe_bridge_rows_batch(fhe_ctx* ctx, uint64_t* d_ct, int64_t Q, int64_t B, int64_t B_old, void* stream);
+/* fhe_search_seeded_queries_batch with documents b < B_old (0 <= B_old <= B)
+ * stored under the old key: the leveled step is unchanged, rows
+ * {q B + b : b < B_old} of its result are bridged in place, then the sign
+ * extraction and the two packings run as there. At B_old = 0 it is that entry
+ * word for word and needs no bridge key. */
+int fhe_search_seeded_queries_bridged_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t B,
+                                            int32_t D, const uint32_t h_mask_key[8], int64_t Q, const int64_t* d_W,
+                                            int64_t cst, const int64_t* h_T, int32_t levels_bit, int64_t B_old,
+                                            uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream);
 
 /* ---- both-private search: several GGSW queries in one pass -
  * Q GGSW queries of one key holder (d_ggsw: Q x fhe_ggsw_words, one gadget)

@@ -81,6 +81,15 @@ _PROTOS = {
                                                    _vp]),
     "fhe_search_seeded_queries_batch": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _vp,
                                                   _vp, _vp]),
+    # stored-ciphertext key rotation: the bridge key switch
+    "fhe_bridge_key_words": (C.c_size_t, [C.POINTER(fhe_params), _i32, _i32]),
+    "fhe_bridge_plan": (C.c_int, [C.POINTER(fhe_params), C.c_double, C.POINTER(_i32), C.POINTER(_i32)]),
+    "fhe_keygen_bridge_key_key": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "fhe_export_bridge_key": (C.c_int, [_vp, _vp]),
+    "fhe_import_bridge_key": (C.c_int, [_vp, _i32, _i32, _vp]),
+    "fhe_bridge_batch": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "fhe_search_seeded_queries_bridged_batch": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32,
+                                                          _i64, _vp, _vp, _vp]),
     # both sides encrypted: GGSW query x GLWE documents
     "fhe_encrypt_packed_batch_key": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _u64, _vp, _vp]),
     "fhe_encrypt_packed_batch": (C.c_int, [_vp, _vp, _i64, _i32, _u64, _u64, _vp, _vp]),

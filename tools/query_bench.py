@@ -66,6 +66,14 @@ order, with the HIP-event split of each (rotations, key switches, leveled
 step, packings: the profile buckets summed over the tenants' contexts); it
 writes profiles/r14/tenants.json (--tenant-shape T B: another shape).
 
+With --rotated (docs/AB_LOG_r15.md) it measures the
+stored-ciphertext search after a key rotation, two-party, at 16 dimensions,
+n_bits 6 (P0 = 21): CorpusServer.search_many on a server holding the new
+generation's keys and bridge key, at 8 queries x 128 documents and 1 x 1024,
+with every, half and none of the documents old-generation, 24 steps after 4
+warm-up in rotating order, then the "bridge" and "pack" buckets of each leg
+and its parity with the restatement; it writes profiles/r15/rotated.json.
+
 The floor of the leveled step is its output, B * (kN + 1) * 8 bytes, over the
 6.29 TB/s a float4 copy reaches on the MI355X; `floor_fraction` is that floor
 over the measured time. Prints one JSON line and writes it to --out.
@@ -532,6 +540,93 @@ def stored_queries(cq, oq, D: int, n_bits: int, steps: int, warmup: int, Qn: int
     return out
 
 
+def rotated(cq, oq, D: int, n_bits: int, steps: int, warmup: int, shapes=((8, 128), (1, 1024))) -> dict:
+    """The stored-ciphertext search after a key rotation, one
+    process, one evaluation-only server holding the NEW generation's keys and
+    its bridge key. Per shape (Q queries x B documents) three legs, interleaved
+    in rotating order as stored_queries does: every document old-generation
+    (B_old = B), half of them (B_old = B / 2), none (B_old = 0, the unbridged
+    entry). Host clock around each search_many with a device synchronise (reply
+    copies included); then a short profiled pass for the "bridge" and "pack"
+    HIP-event buckets; and the parity of every leg's decrypted replies with
+    the restatement."""
+    import numpy as np
+    import torch
+    from oracle import quant_ref as Q
+    from fheicp.corpus import EncryptedCorpus
+    from fheicp.stored import CorpusClient, CorpusServer
+    Bmax = max(B for _, B in shapes)
+    c0 = EncryptedCorpus(cq).compile(key_seed=5, device=0, noise_seed=6)
+    client0 = CorpusClient(c0, count=1024, pack_seed=17)
+    client1 = client0.rotate(key_seed=7, pack_seed=18, bridge_seed=19, noise_seed=20)
+    server = CorpusServer(client1.eval_keys(), cq, c0.P0, c0.mask_key)
+    eng = server.engine
+    _, docs = Q.make_corpus(D, Bmax, seed=21)
+    old_b, old_i = client0.encrypt_docs(docs)
+    new_b, new_i = client1.encrypt_docs(docs)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    out = {"bridge_gadget": list(client1.bridge_gadget), "pack_gadget": [client1.base_log, client1.level],
+           "pack_gadget_unrotated": [client0.base_log, client0.level], "pack_margin_sigmas": client1.margin,
+           "bridge_key_bytes": 8 * eng.bridge_key_words(*client1.bridge_gadget), "steps": steps, "warmup": warmup,
+           "shapes": []}
+    for Qn, B in shapes:
+        qs = np.stack([Q.make_corpus(D, 1, seed=100 + i)[0] for i in range(Qn)])
+        legs = {}
+        for name, n_old in (("all_old", B), ("half_old", B // 2), ("none_old", 0)):
+            body = np.concatenate([old_b[:n_old], new_b[n_old:B]])
+            ids = np.concatenate([old_i[:n_old], new_i[n_old:B]])
+            legs[name] = (eng.to_dev(body), eng.to_dev(ids), n_old)
+
+        def run(name):
+            server.body, server.ids, server.b_old = legs[name]
+            return server.search_many(qs, 0.5)
+
+        orders = ("abc", "cba", "bca", "acb", "cab", "bac")
+        names = {"a": "all_old", "b": "half_old", "c": "none_old"}
+        t = {k: [] for k in legs}
+        last = {}
+        for i in range(warmup + steps):
+            for k in orders[i % len(orders)]:
+                sec, last[names[k]] = timed(lambda: run(names[k]))
+                if i >= warmup:
+                    t[names[k]].append(sec)
+        ref = np.stack([Q.corpus_accumulate(oq, cq.s_e, n_bits, q, docs[:B]) for q in qs])
+        scores = np.float64(Q.corpus_out_scale(oq, cq.s_e)) * ref.astype(np.float64)
+        exact = {}
+        for name in legs:
+            acc, below = client1.decrypt_replies(last[name])
+            exact[name] = bool(np.array_equal(acc.cpu().numpy(), ref) and
+                               np.array_equal(below.cpu().numpy(), (scores < 0.5).astype(np.int64)))
+        # the HIP-event split, in a pass of its own (the brackets are not in the timed runs)
+        eng.profile(True)
+        split = {}
+        for name in legs:
+            for kern in ("bridge", "pack", "linear_seeded"):
+                eng.profile_read(kern)
+            for _ in range(5):
+                run(name)
+            torch.cuda.synchronize()
+            split[name] = {kern: eng.profile_read(kern)["total_ms"] / 5 for kern in ("bridge", "pack", "linear_seeded")}
+        eng.profile(False)
+        med = {k: statistics.median(v) * 1e3 for k, v in t.items()}
+        out["shapes"].append({
+            "Q": Qn, "B": B, "ms_per_search": med, "min_ms": {k: min(v) * 1e3 for k, v in t.items()},
+            "ratio_over_none_old": {k: med[k] / med["none_old"] for k in med},
+            "event_ms_per_search": split, "bridge_kernel": eng.kernel_name("bridge"), "bit_exact": exact})
+    out["bit_exact"] = all(all(s["bit_exact"].values()) for s in out["shapes"])
+    eng.close()
+    c0.engine.close()
+    client1.corpus.engine.close()
+    return out
+
+
 def private_leveled(eng, beta: int, L: int, D: int, steps: int, warmup: int, Qn: int = 8, sizes=(128, 1024)) -> dict:
     """The both-private leveled step for Qn GGSW queries, per document count:
     one fhe_linear_ggsws_batch (the "linear_ggsws" bucket, and HIP events
@@ -788,6 +883,11 @@ def main() -> int:
                          "for 8 tenants x (Q = 1, B = 128) against the eight QueryServer.search calls and one "
                          "tenant's B = 1024 search, 24 interleaved steps after 4 warm-up, with the HIP-event split "
                          "per run; writes profiles/r14/tenants.json")
+    ap.add_argument("--rotated", action="store_true",
+                    help="the stored-ciphertext search after a key rotation (16-dim, n_bits 6, two-party, DESIGN.md "
+                         "§8.12): CorpusServer.search_many at 8 queries x 128 documents and 1 x 1024 with every, half "
+                         "and none of the documents old-generation (bridged), 24 interleaved steps after 4 warm-up, "
+                         "with the bridge bucket's HIP-event time; writes profiles/r15/rotated.json")
     ap.add_argument("--tenant-shape", type=int, nargs=2, default=[8, 128], metavar=("T", "B"),
                     help="--tenants: T tenants of B documents each (default 8 128)")
     ap.add_argument("--out", default=None, help="default profiles/query_bench.json "
@@ -796,7 +896,8 @@ def main() -> int:
                                                 "--private-queries: profiles/r13/private_queries.json)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = str(REPO / "profiles" / ("r14/tenants.json" if a.tenants else
+        a.out = str(REPO / "profiles" / ("r15/rotated.json" if a.rotated else
+                                         "r14/tenants.json" if a.tenants else
                                          "r11/multi_query.json" if a.multi_query else
                                          "r12/stored_queries.json" if a.stored_queries else
                                          "r13/private_queries.json" if a.private_queries else "query_bench.json"))
@@ -808,6 +909,18 @@ def main() -> int:
         return 2
     from fheicp.engine import Engine
     from fheicp.params import params_for_bits
+    if a.rotated:
+        cq, oq = corpus_quant(16, 6)
+        ro = rotated(cq, oq, 16, 6, steps=24, warmup=4)
+        from fheicp import _lib
+        res = {"bench": "query_bench --rotated", "device": torch.cuda.get_device_name(0), "D": 16, "n_bits": 6,
+               "P0": cq.worst_msg_bits(), "build": _lib.lib().fhe_build_info().decode(), "rotated": ro,
+               "bit_exact": ro["bit_exact"]}
+        line = json.dumps(res)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(line + "\n")
+        print(line)
+        return 0
     if a.tenants:
         cq, oq = corpus_quant(16, 6)
         tn = tenants(cq, oq, 16, 6, steps=24, warmup=4, Tn=a.tenant_shape[0], B=a.tenant_shape[1])
