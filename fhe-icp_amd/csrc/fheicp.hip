@@ -6,6 +6,8 @@
 //   k_client.h        keygen, encrypt / decrypt, seeded (stored) corpus kernels
 //   k_server.h        leveled linear layer, key switch (VALU and i8 MFMA),
 //                     quantisation, top-k
+//   k_ks_grp.h        group form of the i8 MFMA key switch: block table, digits
+//                     and GEMM over several key holders' rows
 //   k_query.h         private-query search: document packing, query byte planes,
 //                     the i8 MFMA GEMM of one encrypted query x clear documents
 //   k_pack.h          LWE -> GLWE packing key switch (two-party replies): wide
@@ -36,6 +38,7 @@
 #include "common.h"
 #include "k_client.h"
 #include "k_server.h"
+#include "k_ks_grp.h"
 #include "k_query.h"
 #include "k_pack.h"
 #include "k_bridge.h"
@@ -3447,27 +3450,30 @@ int fhe_profile_read(fhe_ctx* ctx, const char* kernel, double* total_ms, int64_t
 // ---- several key holders in one batched call -------------
 // A group borrows T contexts with equal parameters on one device. Its rows are
 // T segments padded to whole four-ciphertext workgroups (fhe_group_rows); per
-// round every tenant's rows take that tenant's key switch, then ONE rotation
-// launch whose workgroups each pick their tenant's bootstrapping key
-// (k_blind_rotate_*_grp). Timing of the group rotations goes to tenant 0's
+// round ONE key switch whose workgroups each pick their tenant's key planes
+// (k_ks_grp.h, §8.13), then ONE rotation launch whose workgroups each pick
+// their tenant's bootstrapping key (k_blind_rotate_*_grp). Timing of the group rotations goes to tenant 0's
 // blind-rotation buckets.
 struct fhe_group {
   std::vector<fhe_ctx*> ctxs;
   int device = -1;
-  const c64** d_keys = nullptr;     // [NGAD][T]: tenant t's bsk_fft of gadget g
+  const c64** d_keys = nullptr;     // [NGAD + 1][T]: tenant t's bsk_fft of gadget g, then its ksk8 planes
   std::vector<const c64*> h_keys;   // what d_keys holds
-  void* ws = nullptr;               // tables | small | (search: ct_v | sign | copy | expanded queries)
+  void* ws = nullptr;               // tables | small | (search: ct_v | sign | copy | expanded queries / constants)
   size_t ws_bytes = 0;
+  void* ks_ws = nullptr;            // the group key switch's digit groups | bodies (M words)
+  size_t ks_ws_bytes = 0;
+  int ks_tiles = 512;               // the key switch's K-split target: two workgroups per CU of the device
 };
 
 static int gfail(int code, const std::string& msg) { return fail(nullptr, code, "group: " + msg); }
 
 // the group kernel launch_br's choice for gadget `gad` maps to: 1 multi-bit,
 // 2 generic, 0 none (the classic v4 / v4s / two-wave rotations)
-static int grp_kernel_for(const fhe_ctx* ctx, int gad) {
-  const bool fast = gad > 0 && fast_level(ctx->p, gad);
-  const fhe_params p = fast ? fast_params(ctx->p, gad) : ctx->p;
-  if (fast && mb_for(ctx->p, gad)) return p.N == 1024 && p.k == 2 && p.pbs_level <= 8 ? 1 : 0;
+static int grp_kernel_for(const fhe_params& cp, int gad) {
+  const bool fast = gad > 0 && fast_level(cp, gad);
+  const fhe_params p = fast ? fast_params(cp, gad) : cp;
+  if (fast && mb_for(cp, gad)) return p.N == 1024 && p.k == 2 && p.pbs_level <= 8 ? 1 : 0;
   if (p.N == 1024) return 0;
   if (((p.N == 256 || p.N == 512) && (p.k == 1 || p.k == 2)) || (p.N == 2048 && p.k == 1)) return 2;
   return 0;
@@ -3480,16 +3486,21 @@ static int grp_schedule(const fhe_params& p, int* d, int* sched) {
   }
   return sign_schedule(p, d, sched);
 }
+// the first round of the sign schedule without a group kernel, or -1
+static int grp_classic_round(const fhe_params& p) {
+  int d, sched[64];
+  const int R = grp_schedule(p, &d, sched);
+  for (int r = 0; r < R; ++r)
+    if (!grp_kernel_for(p, sched[r])) return r;
+  return -1;
+}
 // checks 2 and 3 of fhe_group_create; 2 again at every call (fhe_set_msg_bits)
 static int grp_check_params(const fhe_group* g) {
   for (size_t t = 1; t < g->ctxs.size(); ++t)
     if (g->ctxs[t]->device != g->ctxs[0]->device || memcmp(&g->ctxs[t]->p, &g->ctxs[0]->p, sizeof(fhe_params)))
       return gfail(FHE_E_ARG, "tenant " + std::to_string(t) + " differs from tenant 0 in its device or parameters");
-  int d, sched[64];
-  const int R = grp_schedule(g->ctxs[0]->p, &d, sched);
-  for (int r = 0; r < R; ++r)
-    if (!grp_kernel_for(g->ctxs[0], sched[r]))
-      return gfail(FHE_E_ARG, "round " + std::to_string(r) + " runs the classic rotation (no group kernel)");
+  const int r = grp_classic_round(g->ctxs[0]->p);
+  if (r >= 0) return gfail(FHE_E_ARG, "round " + std::to_string(r) + " runs the classic rotation (no group kernel)");
   return FHE_OK;
 }
 static int grp_check_keys(const fhe_group* g) {
@@ -3502,9 +3513,10 @@ static int grp_check_keys(const fhe_group* g) {
 // the key-pointer table follows the contexts (a re-keyed tenant moves its keys)
 static int grp_sync_keys(fhe_group* g) {
   const size_t T = g->ctxs.size();
-  std::vector<const c64*> k((size_t)NGAD * T);
+  std::vector<const c64*> k((size_t)(NGAD + 1) * T);
   for (int gd = 0; gd < NGAD; ++gd)
     for (size_t t = 0; t < T; ++t) k[gd * T + t] = gd ? g->ctxs[t]->bskf_fft[gd - 1] : g->ctxs[t]->bsk_fft;
+  for (size_t t = 0; t < T; ++t) k[(size_t)NGAD * T + t] = (const c64*)g->ctxs[t]->ksk8;  // k_keyswitch_mfma_grp's
   if (k == g->h_keys) return FHE_OK;
   fhe_ctx* c0 = g->ctxs[0];
   HIPCHK(c0, hipDeviceSynchronize());
@@ -3542,6 +3554,12 @@ int64_t fhe_group_rows(const int64_t* counts, int32_t T, int64_t* starts) {
   return m;
 }
 
+int fhe_group_form(const fhe_params* params) {
+  std::string why;
+  if (validate(params, why)) return fail(nullptr, FHE_E_ARG, why);
+  return grp_classic_round(*params) < 0 ? 1 : 0;
+}
+
 int fhe_group_create(fhe_ctx* const* ctxs, int32_t T, fhe_group** out) {
   if (!out) return gfail(FHE_E_ARG, "out is null");
   *out = nullptr;
@@ -3561,16 +3579,22 @@ int fhe_group_create(fhe_ctx* const* ctxs, int32_t T, fhe_group** out) {
     fhe_group_destroy(g);
     return rc;
   }
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device) == hipSuccess && cus > 0)
+    g->ks_tiles = 2 * cus;
+  else
+    (void)hipGetLastError();
   *out = g;
   return FHE_OK;
 }
 
 void fhe_group_destroy(fhe_group* g) {
   if (!g) return;
-  if (g->device >= 0 && (g->d_keys || g->ws)) {
+  if (g->device >= 0 && (g->d_keys || g->ws || g->ks_ws)) {
     (void)hipSetDevice(g->device);
     (void)hipFree((void*)g->d_keys);
     (void)hipFree(g->ws);
+    (void)hipFree(g->ks_ws);
   }
   delete g;
 }
@@ -3586,7 +3610,7 @@ static int launch_br_grp(fhe_group* g, const u64* small, int64_t M, const int32_
   hipEvent_t e1;
   prof_begin(c0, prof, st, &e1);
   const char* name = nullptr;
-  if (grp_kernel_for(c0, gad) == 1) {
+  if (grp_kernel_for(c0->p, gad) == 1) {
     const dim3 gm((unsigned)(M / 4)), bm(v4::nthreads(4));
 #define MBG(L, B)                                                                                                  \
   hipLaunchKernelGGL((k_blind_rotate_mb_grp<L, B>), gm, bm, 0, st, small, wgt, tg, p.n, p.pbs_base_log, c0->tw4,   \
@@ -3638,28 +3662,143 @@ static int launch_br_grp(fhe_group* g, const u64* small, int64_t M, const int32_
 }
 
 // table words before the rows of a group workspace: starts | ends | the
-// per-gadget tenant table | the workgroups' tenants (padded to 16 bytes)
+// per-gadget tenant table | the workgroups' tenants (padded to 16 bytes) |
+// the key switch's ciphertext blocks (at most M / 128 + T)
+static size_t grp_wgt_bytes(int64_t M) { return ((size_t)(M / 4) * 4 + 15) / 16 * 16; }
 static size_t grp_table_bytes(size_t T, int64_t M) {
-  return 16 * T + sizeof(BrGrpTenant) * NGAD * T + ((size_t)(M / 4) * 4 + 15) / 16 * 16;
+  const size_t blocks = sizeof(KsGrpBlock) * ((size_t)(M / KSM_CTS) + T);  // 24 bytes each
+  return 16 * T + sizeof(BrGrpTenant) * NGAD * T + grp_wgt_bytes(M) + (blocks + 15) / 16 * 16;  // rows stay 16-aligned
 }
-// The sign extraction over the padded rows: sign_extract's rounds, each T key
-// switches (tenant t's rows, key and workspace) and one group rotation, on
-// the caller's stream. `tables` holds grp_table_bytes.
+#ifndef FHEICP_GRP_KS
+#define FHEICP_GRP_KS 1  // 0: one key switch per tenant, as before the group form (A/B builds)
+#endif
+// The MFMA key switch of every tenant's rows in two launches (k_ks_grp.h):
+// the digits and the GEMM over the ciphertext blocks of `blk`, each with its
+// tenant's key planes; keyswitch_lane's split rule on the launch's total of
+// blocks x column groups. Timing goes to tenant 0's key-switch bucket.
+static int grp_ks_fits(const fhe_group* g, const int64_t* counts);
+static int grp_keyswitch(fhe_group* g, const u64* d_big, const int64_t* counts, const KsGrpBlock* blk, int64_t M,
+                         int32_t shift, uint64_t add_body, u64* d_small, hipStream_t st) {
+  fhe_ctx* c0 = g->ctxs[0];
+  const fhe_params& p = c0->p;
+  const size_t T = g->ctxs.size();
+  int64_t nblk = 0, ndg = 0;
+  for (size_t t = 0; t < T; ++t) {
+    nblk += (counts[t] + KSM_CTS - 1) / KSM_CTS;
+    ndg += (counts[t] + 15) / 16;
+  }
+  if (nblk == 0) return FHE_OK;
+  // the digit launch's grid y is 8 per block
+  if (ndg > 65535 || 8 * nblk > 65535) return grp_ks_fits(g, counts);  // the entries checked it already
+  const int K = p.k * p.N * p.ks_level, KB = K / 64, n1 = p.n + 1, NB = ks_nb(p), CB = ks_cb(p), R = ks_round_bits(p);
+  const size_t dbytes = (size_t)ndg * 16 * K, need = dbytes + 8 * (size_t)M;
+  if (need > g->ks_ws_bytes) {
+    if (g->ks_ws) {
+      HIPCHK(c0, hipDeviceSynchronize());
+      HIPCHK(c0, hipFree(g->ks_ws));
+      g->ks_ws = nullptr;
+      g->ks_ws_bytes = 0;
+    }
+    if (hipMalloc(&g->ks_ws, need) != hipSuccess) {
+      (void)hipGetLastError();
+      g->ks_ws = nullptr;
+      return gfail(FHE_E_NOMEM, "key-switch workspace: out of device memory (fewer rows per call)");
+    }
+    g->ks_ws_bytes = need;
+  }
+  uint32_t* D = (uint32_t*)g->ks_ws;
+  u64* body = (u64*)((char*)g->ks_ws + dbytes);
+  const int64_t ktiles = nblk * (NB / CB);
+  int S = (int)std::max<int64_t>(1, std::min<int64_t>(KB / KSM_RING, g->ks_tiles / ktiles));
+  const int kslice = (KB / KSM_RING + S - 1) / S * KSM_RING;
+  S = (KB + kslice - 1) / kslice;
+  const v4i* const* keys = (const v4i* const*)(g->d_keys + (size_t)NGAD * T);
+  hipEvent_t e1;
+  prof_begin(c0, c0->prof_ks, st, &e1);
+  hipLaunchKernelGGL(k_ks_digits_grp, dim3((unsigned)(p.k * p.N / 64), (unsigned)(8 * nblk)), dim3(256), 0, st, d_big,
+                     blk, p.k * p.N, p.ks_base_log, p.ks_level, shift, add_body, KB, D, body, S > 1 ? n1 : 0, d_small);
+  const dim3 gks((unsigned)(ktiles * S));
+#define KSMG(Q, C)                                                                                                   \
+  c0->prof_ks.kernel = "k_keyswitch_mfma_grp<" #Q ", " #C ">";                                                      \
+  hipLaunchKernelGGL((k_keyswitch_mfma_grp<Q, C>), gks, dim3(256), 0, st, (const v4i*)D, keys, blk, body, n1, NB, KB, \
+                     R, S, kslice, d_small)
+  switch ((8 - R / 8) * 4 + CB) {
+    case 3 * 4 + 3: KSMG(3, 3); break;
+    case 4 * 4 + 3: KSMG(4, 3); break;
+    case 5 * 4 + 1: KSMG(5, 1); break;
+    case 6 * 4 + 1: KSMG(6, 1); break;
+    case 7 * 4 + 1: KSMG(7, 1); break;
+    case 8 * 4 + 1: KSMG(8, 1); break;
+    default: return gfail(FHE_E_ARG, "key-switch byte planes out of range");
+  }
+#undef KSMG
+  int64_t total = 0;
+  for (size_t t = 0; t < T; ++t) total += counts[t];
+  prof_end(c0, c0->prof_ks, st, e1, total);
+  HIPCHK(c0, hipGetLastError());
+  return FHE_OK;
+}
+// the group form serves tenants that all run the MFMA key switch
+static bool grp_ks_grouped(const fhe_group* g) {
+  if (!FHEICP_GRP_KS) return false;
+  for (fhe_ctx* c : g->ctxs)
+    if (c->ks_variant != 2) return false;
+  return true;
+}
+// The group key switch's launch limits over all tenants together (the digit
+// launch's grid y is 8 per ciphertext block): checked by every group entry
+// before any work is queued. The per-tenant loop has keyswitch_lane's own.
+static int grp_ks_fits(const fhe_group* g, const int64_t* counts) {
+  if (!grp_ks_grouped(g)) return FHE_OK;
+  int64_t nblk = 0, ndg = 0;
+  for (size_t t = 0; t < g->ctxs.size(); ++t) {
+    nblk += (counts[t] + KSM_CTS - 1) / KSM_CTS;
+    ndg += (counts[t] + 15) / 16;
+  }
+  if (ndg > 65535 || 8 * nblk > 65535)
+    return gfail(FHE_E_ARG, "keyswitch batch too large (more than 65535 digit groups of 16 rows, or 8191 blocks of "
+                            "128 rows, over all tenants): split the call");
+  return FHE_OK;
+}
+// starts | ends to the front of `tables`, then the key switch's block table
+// behind the rotation's tables (stream-ordered)
+static int grp_ks_tables(fhe_group* g, const int64_t* counts, const int64_t* starts, int64_t M, void* tables,
+                         hipStream_t st, KsGrpBlock** blk) {
+  fhe_ctx* c0 = g->ctxs[0];
+  const size_t T = g->ctxs.size();
+  std::vector<u64> se(2 * T);
+  int64_t nblk = 0;
+  for (size_t t = 0; t < T; ++t) {
+    se[t] = (u64)starts[t];
+    se[T + t] = (u64)(starts[t] + counts[t]);
+    nblk += (counts[t] + KSM_CTS - 1) / KSM_CTS;
+  }
+  u64* d_se = (u64*)tables;
+  *blk = (KsGrpBlock*)((char*)tables + 16 * T + sizeof(BrGrpTenant) * NGAD * T + grp_wgt_bytes(M));
+  int rc = store_words(c0, d_se, se.data(), (int64_t)(2 * T), st);
+  if (rc || !nblk) return rc;
+  hipLaunchKernelGGL(k_ks_grp_tables, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, (const int64_t*)d_se,
+                     (int)T, nblk, *blk);
+  HIPCHK(c0, hipGetLastError());
+  return FHE_OK;
+}
+// The sign extraction over the padded rows: sign_extract's rounds, each one
+// group key switch (grp_keyswitch; with a tenant on the VALU variant, or in a
+// -DFHEICP_GRP_KS=0 build, T key switches on tenant t's rows, key and
+// workspace) and one group rotation, on the caller's stream. `tables` holds
+// grp_table_bytes.
 static int grp_sign(fhe_group* g, u64* ct_v, const int64_t* counts, const int64_t* starts, int64_t M, u64* sign,
                     u64* small, void* tables, hipStream_t st) {
   fhe_ctx* c0 = g->ctxs[0];
   const fhe_params& p = c0->p;
   const size_t T = g->ctxs.size(), Wb = fhe_big_lwe_words(&p), Ws = fhe_small_lwe_words(&p);
   int rc;
-  std::vector<u64> se(2 * T);
-  for (size_t t = 0; t < T; ++t) {
-    se[t] = (u64)starts[t];
-    se[T + t] = (u64)(starts[t] + counts[t]);
-  }
   u64* d_se = (u64*)tables;
   BrGrpTenant* ten = (BrGrpTenant*)(d_se + 2 * T);
   int32_t* wgt = (int32_t*)(ten + (size_t)NGAD * T);
-  if ((rc = store_words(c0, d_se, se.data(), (int64_t)(2 * T), st))) return rc;
+  KsGrpBlock* blk;
+  if ((rc = grp_ks_tables(g, counts, starts, M, tables, st, &blk))) return rc;
+  const bool grouped = grp_ks_grouped(g);
   const int64_t nwg = M / 4, nth = std::max<int64_t>(nwg, (int64_t)(NGAD * T));
   hipLaunchKernelGGL(k_grp_tables, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, st, g->d_keys,
                      (const int64_t*)d_se, (int)T, NGAD, nwg, ten, wgt);
@@ -3667,7 +3806,11 @@ static int grp_sign(fhe_group* g, u64* ct_v, const int64_t* counts, const int64_
   int d, sched[64], round = 0;
   grp_schedule(p, &d, sched);
   auto step = [&](int shift, uint64_t add, BrTv tv, int mode, uint64_t* sg) -> int {
-    for (size_t t = 0; t < T; ++t) {
+    if (grouped) {
+      int r = grp_keyswitch(g, ct_v, counts, blk, M, shift, add, small, st);
+      if (r) return r;
+    }
+    for (size_t t = 0; t < T && !grouped; ++t) {
       if (!counts[t]) continue;
       int r = keyswitch_lane(g->ctxs[t], ct_v + (size_t)starts[t] * Wb, counts[t], shift, add,
                              small + (size_t)starts[t] * Ws, st, 0);
@@ -3699,15 +3842,51 @@ int fhe_sign_group_batch(fhe_group* g, uint64_t* d_ct_v, const int64_t* h_counts
   if (rc) return rc;
   if (M == 0) return FHE_OK;
   if (!d_ct_v || !d_sign) return gfail(FHE_E_ARG, "null sign buffers");
+  if ((rc = grp_ks_fits(g, h_counts))) return rc;
   const size_t tb = grp_table_bytes((size_t)T, M);
   if ((rc = grp_ensure_ws(g, tb + 8 * (size_t)M * fhe_small_lwe_words(&g->ctxs[0]->p)))) return rc;
   return grp_sign(g, d_ct_v, h_counts, starts.data(), M, d_sign, (u64*)((char*)g->ws + tb), g->ws, (hipStream_t)stream);
 }
 
+int fhe_keyswitch_group_batch(fhe_group* g, const uint64_t* d_big, const int64_t* h_counts, int32_t shift,
+                              uint64_t add_body, uint64_t* d_small, void* stream) {
+  if (!g) return gfail(FHE_E_ARG, "null group");
+  const int32_t T = (int32_t)g->ctxs.size();
+  std::vector<int64_t> starts((size_t)T);
+  const int64_t M = fhe_group_rows(h_counts, T, starts.data());  // < 0: null or a count outside [0, 2^40]
+  int64_t total = 0;
+  for (int32_t t = 0; M >= 0 && t < T; ++t) total += h_counts[t];
+  if (M < 0 || total >= ((int64_t)1 << 31))
+    return gfail(FHE_E_ARG, "bad keyswitch arguments (counts null, negative or 2^31 rows and more)");
+  if (shift < 0 || shift > ks_max_shift(g->ctxs[0]->p))
+    return gfail(FHE_E_ARG, "bad keyswitch arguments (shift must be in [0, 63 - ks_level * (ks_base_log + 1)])");
+  int rc = grp_enter(g);
+  if (rc) return rc;
+  if (M == 0) return FHE_OK;
+  if (!d_big || !d_small) return gfail(FHE_E_ARG, "null keyswitch buffers");
+  if ((rc = grp_ks_fits(g, h_counts))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const fhe_params& p = g->ctxs[0]->p;
+  if (!grp_ks_grouped(g)) {
+    const size_t Wb = fhe_big_lwe_words(&p), Ws = fhe_small_lwe_words(&p);
+    for (int32_t t = 0; t < T; ++t) {
+      if (!h_counts[t]) continue;
+      if ((rc = keyswitch_lane(g->ctxs[t], d_big + (size_t)starts[t] * Wb, h_counts[t], shift, add_body,
+                               d_small + (size_t)starts[t] * Ws, st, 0)))
+        return rc;
+    }
+    return FHE_OK;
+  }
+  if ((rc = grp_ensure_ws(g, grp_table_bytes((size_t)T, M)))) return rc;
+  KsGrpBlock* blk;
+  if ((rc = grp_ks_tables(g, h_counts, starts.data(), M, g->ws, st, &blk))) return rc;
+  return grp_keyswitch(g, d_big, h_counts, blk, M, shift, add_body, d_small, st);
+}
+
 int fhe_search_query_group_batch(fhe_group* g, const fhe_group_query* items, int32_t T, void* stream) {
   if (!g) return gfail(FHE_E_ARG, "null group");
   if (!items || T != (int32_t)g->ctxs.size()) return gfail(FHE_E_ARG, "one fhe_group_query per tenant");
-  // argument errors first: a group of host-only contexts reports them too
+  // argument errors first, before any device or key is looked at
   std::vector<int64_t> counts((size_t)T), starts((size_t)T);
   int64_t total = 0;
   for (int32_t t = 0; t < T; ++t) {
@@ -3737,6 +3916,7 @@ int fhe_search_query_group_batch(fhe_group* g, const fhe_group_query* items, int
   }
   const int64_t M = fhe_group_rows(counts.data(), T, starts.data());
   if (M == 0) return FHE_OK;
+  if ((rc = grp_ks_fits(g, counts.data()))) return rc;
   hipStream_t st = (hipStream_t)stream;
   const fhe_params& p = g->ctxs[0]->p;
   const size_t Wb = fhe_big_lwe_words(&p), Ws = fhe_small_lwe_words(&p), tb = grp_table_bytes((size_t)T, M);
@@ -3771,6 +3951,82 @@ int fhe_search_query_group_batch(fhe_group* g, const fhe_group_query* items, int
     if ((rc = pack_impl(ctx, cpy + (size_t)starts[t] * Wb, counts[t], ctx->pk_level, q.d_glwe_acc, st))) return rc;
     if ((rc = pack_impl(ctx, sgn + (size_t)starts[t] * Wb, counts[t], q.levels_bit ? q.levels_bit : ctx->pk_level,
                         q.d_glwe_bit, st)))
+      return rc;
+  }
+  return FHE_OK;
+}
+
+// ---- stored-ciphertext search for a group ----------------
+int fhe_search_seeded_queries_group_batch(fhe_group* g, const fhe_group_corpus* items, int32_t T, void* stream) {
+  if (!g) return gfail(FHE_E_ARG, "null group");
+  if (!items || T != (int32_t)g->ctxs.size()) return gfail(FHE_E_ARG, "one fhe_group_corpus per tenant");
+  // argument errors first, before any device or key is looked at
+  std::vector<int64_t> counts((size_t)T), starts((size_t)T);
+  int64_t total = 0, qmax = 0;
+  for (int32_t t = 0; t < T; ++t) {
+    const fhe_group_corpus& c = items[t];
+    const std::string who = "tenant " + std::to_string(t) + ": ";
+    if (c.struct_size != (int32_t)sizeof(fhe_group_corpus))
+      return gfail(FHE_E_ARG, who + "fhe_group_corpus.struct_size is not this library's");
+    if (c.Q < 0) return gfail(FHE_E_ARG, who + "Q < 0");
+    counts[t] = 0;
+    if (c.Q == 0) continue;  // sits this call out
+    if (seeded_queries_args(g->ctxs[t], c.Q, c.B, c.D))
+      return gfail(FHE_E_ARG, who + fhe_last_error(g->ctxs[t]));
+    if (c.levels_bit < 0 || c.levels_bit > 8) return gfail(FHE_E_ARG, who + "levels_bit outside [0, 8]");
+    if (!c.d_body || !c.d_id0 || !c.h_mask_key || !c.d_W || !c.h_T || !c.d_glwe_acc || !c.d_glwe_bit)
+      return gfail(FHE_E_ARG, who + "null search arguments");
+    if (c.B_old < 0 || c.B_old > c.B) return gfail(FHE_E_ARG, who + "B_old outside [0, B]");
+    counts[t] = c.Q * c.B;
+    total += counts[t];
+    qmax = std::max(qmax, c.Q);
+    if (total >= ((int64_t)1 << 31)) return gfail(FHE_E_ARG, "2^31 results and more: split the call");
+  }
+  int rc = grp_enter(g);
+  if (rc) return rc;
+  for (int32_t t = 0; t < T; ++t) {
+    const fhe_group_corpus& c = items[t];
+    if (!c.Q) continue;
+    const std::string who = "tenant " + std::to_string(t) + ": ";
+    if ((rc = need_pack_key(g->ctxs[t]))) return gfail(rc, who + fhe_last_error(g->ctxs[t]));
+    if (c.B_old > 0 && (rc = need_bridge_key(g->ctxs[t]))) return gfail(rc, who + fhe_last_error(g->ctxs[t]));
+    if (c.levels_bit > g->ctxs[t]->pk_level)
+      return gfail(FHE_E_ARG, who + "levels_bit exceeds the packing key's levels");
+  }
+  const int64_t M = fhe_group_rows(counts.data(), T, starts.data());
+  if (M == 0) return FHE_OK;
+  if ((rc = grp_ks_fits(g, counts.data()))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const fhe_params& p = g->ctxs[0]->p;
+  const size_t Wb = fhe_big_lwe_words(&p), Ws = fhe_small_lwe_words(&p), tb = grp_table_bytes((size_t)T, M);
+  if ((rc = grp_ensure_ws(g, tb + 8 * ((size_t)M * (3 * Wb + Ws) + (size_t)qmax)))) return rc;
+  u64* small = (u64*)((char*)g->ws + tb);
+  u64* ctv = small + (size_t)M * Ws;
+  u64* sgn = ctv + (size_t)M * Wb;
+  u64* cpy = sgn + (size_t)M * Wb;
+  u64* dcs = cpy + (size_t)M * Wb;  // one tenant's scaled constants at a time, in stream order
+  // per tenant: the leveled step into its segment, the bridge on its old
+  // documents' rows, a copy of the leveled rows (the sign extraction consumes them)
+  for (int32_t t = 0; t < T; ++t) {
+    const fhe_group_corpus& c = items[t];
+    if (!c.Q) continue;
+    fhe_ctx* ctx = g->ctxs[t];
+    u64* seg = ctv + (size_t)starts[t] * Wb;
+    if ((rc = store_scaled_csts(ctx, dcs, c.Q, nullptr, c.cst, c.h_T, st))) return rc;
+    if ((rc = linear_seeded_queries_launch(ctx, c.d_body, c.d_id0, c.B, c.D, c.h_mask_key, c.Q, c.d_W, dcs, seg, st)))
+      return rc;
+    if (c.B_old > 0 && (rc = bridge_impl(ctx, seg, c.Q, c.B, c.B_old, seg, st))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(cpy + (size_t)starts[t] * Wb, seg, 8 * (size_t)counts[t] * Wb, hipMemcpyDeviceToDevice, st));
+  }
+  if ((rc = grp_sign(g, ctv, counts.data(), starts.data(), M, sgn, small, g->ws, st))) return rc;
+  // tenant t's two packings with its own key, as fhe_search_seeded_queries_bridged_batch
+  for (int32_t t = 0; t < T; ++t) {
+    const fhe_group_corpus& c = items[t];
+    if (!c.Q) continue;
+    fhe_ctx* ctx = g->ctxs[t];
+    if ((rc = pack_impl(ctx, cpy + (size_t)starts[t] * Wb, counts[t], ctx->pk_level, c.d_glwe_acc, st))) return rc;
+    if ((rc = pack_impl(ctx, sgn + (size_t)starts[t] * Wb, counts[t], c.levels_bit ? c.levels_bit : ctx->pk_level,
+                        c.d_glwe_bit, st)))
       return rc;
   }
   return FHE_OK;

@@ -166,12 +166,15 @@ __global__ void k_ksk_to_i8(const u64* __restrict__ ksk, int K, int big, int lev
 // also zeroes the key switch's output rows of its 16 ciphertexts (zero_n1
 // words each, a slice of columns per block), for the split-K atomics of
 // k_keyswitch_mfma (one launch fewer than a memset).
-__global__ void __launch_bounds__(256) k_ks_digits(const u64* __restrict__ in, int64_t count, int big, int beta,
-                                                   int levels, int shift, u64 add_body, int KB,
-                                                   uint32_t* __restrict__ D, u64* __restrict__ body, int zero_n1,
-                                                   u64* __restrict__ zero_out) {
+// ks_digits_group is one block's work on digit group cb of the `count`
+// ciphertexts behind in / D / body / zero_out (shared with the group form
+// k_ks_digits_grp, k_ks_grp.h).
+__device__ __forceinline__ void ks_digits_group(const u64* __restrict__ in, int64_t count, int big, int beta,
+                                                int levels, int shift, u64 add_body, int KB,
+                                                uint32_t* __restrict__ D, u64* __restrict__ body, int zero_n1,
+                                                u64* __restrict__ zero_out, int64_t cb) {
   const int t = threadIdx.x, cl = t >> 4, iq = t & 15;
-  const int64_t cb = blockIdx.y, c = cb * 16 + cl;
+  const int64_t c = cb * 16 + cl;
   const int i0 = blockIdx.x * 64 + iq * 4;
   if (zero_n1 > 0) {
     const int per = (zero_n1 + (int)gridDim.x - 1) / (int)gridDim.x;
@@ -215,6 +218,12 @@ __global__ void __launch_bounds__(256) k_ks_digits(const u64* __restrict__ in, i
     const int kb = (levels - 1 - s) * kbl + kbi;
     D[(((size_t)cb * KB + kb) * 64 + lane) * 4 + ((i0 & 15) >> 2)] = packed[s];
   }
+}
+__global__ void __launch_bounds__(256) k_ks_digits(const u64* __restrict__ in, int64_t count, int big, int beta,
+                                                   int levels, int shift, u64 add_body, int KB,
+                                                   uint32_t* __restrict__ D, u64* __restrict__ body, int zero_n1,
+                                                   u64* __restrict__ zero_out) {
+  ks_digits_group(in, count, big, beta, levels, shift, add_body, KB, D, body, zero_n1, zero_out, blockIdx.y);
 }
 
 // workgroup = 4 waves = 128 ciphertexts x CB * 16 columns x QP byte planes x

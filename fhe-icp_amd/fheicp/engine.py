@@ -961,6 +961,60 @@ class EngineGroup:
         _lib.check(self._L.fhe_search_query_group_batch(self._grp, arr, len(items), _stream(self.device)))
         return out
 
+    def keyswitch(self, big: torch.Tensor, counts, shift: int = 0, add_body: int = 0,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+        """fhe_keyswitch_group_batch: big holds the M padded rows of
+        rows(counts), kN + 1 words each; returns M small rows (n + 1 words),
+        tenant t's under its own key, the padding rows unwritten (`out`: a
+        buffer of at least M rows to write into)."""
+        M, _ = group_rows(counts)
+        if len(counts) != len(self.engines) or big.numel() != M * self.W:
+            raise ValueError(f"{len(counts)} counts and {big.numel() // self.W} rows for {len(self.engines)} tenants "
+                             f"and {M} padded rows")
+        Ws = self.engines[0].params.n + 1
+        if out is not None and out.numel() < M * Ws:
+            raise ValueError(f"out holds {out.numel() // Ws} rows, the layout {M}")
+        small = torch.empty((M, Ws), dtype=torch.int64, device=self.device) if out is None else out
+        c = (C.c_int64 * len(counts))(*[int(x) for x in counts])
+        _lib.check(self._L.fhe_keyswitch_group_batch(self._grp, _ptr(big), c, int(shift),
+                                                     int(add_body) % (1 << 64), _ptr(small), _stream(self.device)))
+        return small
+
+    def search_seeded_queries(self, items) -> list:
+        """fhe_search_seeded_queries_group_batch. items: one per engine, None
+        (the tenant sits this call out) or the arguments of
+        Engine.search_seeded_queries as a tuple (body, id0, mask_key, W, cst,
+        Ts, levels_bit, b_old). Returns, per tenant, (glwe_acc, glwe_bit) or
+        None."""
+        if len(items) != len(self.engines):
+            raise ValueError(f"{len(items)} items for {len(self.engines)} tenants")
+        arr = (_lib.FheGroupCorpus * len(items))()
+        keep, out = [], []
+        for t, (eng, it) in enumerate(zip(self.engines, items)):
+            arr[t].struct_size = C.sizeof(_lib.FheGroupCorpus)
+            if it is None:
+                out.append(None)
+                continue
+            body, id0, mask_key, W, cst, Ts, levels_bit, b_old = it
+            hT, _ = Engine._i64s(Ts)
+            key = Engine._key(mask_key)
+            Q = hT.size
+            B, D = body.shape
+            if tuple(W.shape) != (Q, D):
+                raise ValueError(f"tenant {t}: weights {tuple(W.shape)} for {Q} thresholds of {D} features")
+            shape = (eng.glwe_count(Q * int(B)), (eng.params.k + 1) * eng.params.N)
+            ga = torch.empty(shape, dtype=torch.int64, device=self.device)
+            gb = torch.empty(shape, dtype=torch.int64, device=self.device)
+            keep.append((hT, key, body, id0, W))
+            c = arr[t]
+            c.D, c.Q, c.B, c.cst, c.levels_bit, c.B_old = int(D), Q, int(B), int(cst), int(levels_bit), int(b_old)
+            c.d_body, c.d_id0, c.d_W = body.data_ptr(), id0.data_ptr(), W.data_ptr()
+            c.h_mask_key, c.h_T = C.addressof(key), hT.ctypes.data
+            c.d_glwe_acc, c.d_glwe_bit = ga.data_ptr(), gb.data_ptr()
+            out.append((ga, gb))
+        _lib.check(self._L.fhe_search_seeded_queries_group_batch(self._grp, arr, len(items), _stream(self.device)))
+        return out
+
 
 def u64(t: torch.Tensor) -> np.ndarray:
     """Device int64 tensor -> host uint64 array (bit pattern)."""

@@ -18,6 +18,10 @@ The host sees the queries, the thresholds, Q, B and D; it never sees a
 document, a score or a threshold bit. Replies are the version-2 format of
 fheicp.query (pack_replies / unpack_replies) unchanged; the width field
 carries the chunk's own width P <= P0 (EncryptedCorpus.plan_many).
+
+CorpusHub puts several key holders, each with its own
+CorpusServer, behind one GPU: a call that names several of them runs their
+sign extractions in one group launch sequence, key rotation included.
 """
 from __future__ import annotations
 
@@ -312,3 +316,184 @@ class CorpusServer:
     def search(self, query, min_similarity=None) -> np.ndarray:
         """One query: the single reply of search_many([query])."""
         return self.search_many(np.asarray(query).reshape(1, -1), min_similarity)[0]
+
+
+# ------------------------------------------------------ several key holders --
+# One evaluation-only host serving tenants that each hold their own keys and
+# their own STORED documents (DESIGN.md §8.13): every tenant keeps a
+# CorpusServer; a call that names several of them runs their sign extractions
+# in one group launch sequence (fhe_search_seeded_queries_group_batch) and
+# answers each tenant in the version-2 reply format.
+def group_form(scheme, P: int) -> bool:
+    """Whether a group of contexts of `scheme` at width P exists
+    (fhe_group_form, host only): False where a round of the sign schedule
+    runs the classic rotation (P = 27)."""
+    from . import _lib
+    import ctypes as C
+    rc = _lib.lib().fhe_group_form(C.byref(_lib.params_struct(scheme.with_msg_bits(int(P)).as_dict())))
+    if rc < 0:
+        _lib.check(rc)
+    return rc == 1
+
+
+def corpus_rounds(requests: dict, plans: dict, sizes: dict, group_ok=None, cap: int | None = None) -> list:
+    """The rounds of one CorpusHub.search_many call, as pure planning (no
+    device). requests: {name: (queries, min_similarity)}; plans: {name: the
+    tenant's EncryptedCorpus planning object}; sizes: {name: B}.
+
+    Round i takes chunk i of each tenant's query_chunks(Q, B), split further
+    by hub_chunks' bound on the results of one library call. Each piece is
+    planned at its own width P_t (plan_many); the round's width is P = max P_t
+    and a piece's weight rows take the exact arithmetic shift >> (P - P_t)
+    (its rows carry 2^(P0 - P_t), the round's 2^(P0 - P)). A piece alone in
+    its round, or a round whose width has no group form (group_ok(P) False),
+    goes through the tenants' own servers.
+
+    -> [{"mode": "group" | "own", "P": P, "parts": [{"name", "queries" (a
+    range into the tenant's queries), "W" int64 [q, D], "cst", "Ts", "P_t"}]}]
+    """
+    from .query import MAX_RESULTS, hub_chunks
+    cap = MAX_RESULTS if cap is None else int(cap)
+    qs, ts, chunks = {}, {}, {}
+    for name, (queries, min_similarity) in requests.items():
+        q = np.atleast_2d(np.asarray(queries))
+        qs[name], ts[name] = q, thresholds_for(min_similarity, q.shape[0])
+        chunks[name] = query_chunks(q.shape[0], int(sizes[name]), cap)
+    rounds = []
+    for i in range(max((len(c) for c in chunks.values()), default=0)):
+        live = {name: c[i] for name, c in chunks.items() if i < len(c)}
+        for piece in hub_chunks({name: (len(r), int(sizes[name])) for name, r in live.items()}, cap):
+            parts = []
+            for name, sub in piece:
+                rng = range(live[name].start + sub.start, live[name].start + sub.stop)
+                Wr, cst, Ts, P_t = plans[name].plan_many(qs[name][rng.start:rng.stop], [ts[name][q] for q in rng])
+                parts.append({"name": name, "queries": rng, "W": Wr, "cst": cst, "Ts": Ts, "P_t": int(P_t)})
+            P = max(p["P_t"] for p in parts)
+            ok = len(parts) > 1 and (group_ok(P) if group_ok is not None
+                                     else group_form(plans[parts[0]["name"]].scheme, P))
+            if ok:
+                for p in parts:
+                    p["W"] = p["W"] >> np.int64(P - p["P_t"])
+            rounds.append({"mode": "group" if ok else "own", "P": P, "parts": parts})
+    return rounds
+
+
+class CorpusHub:
+    """Tenants with their own keys and their own stored (encrypted) documents
+    behind one GPU. The host learns which tenant asked, the queries and the
+    thresholds; each tenant's documents, scores and bits stay under its key."""
+
+    def __init__(self, device: int = 0):
+        self.device = device
+        self.tenants = {}  # name -> CorpusServer
+        self._group = None
+
+    def add_tenant(self, name, eval_keys, cq, P0: int, mask_key, scheme=None, server=None):
+        """Builds the tenant's CorpusServer from its evaluation keys. Every
+        tenant shares the first one's P0 and scheme parameters: ValueError
+        naming the tenant otherwise. `server` is for tests only: it adopts a
+        ready (or stub) server in place of building one, so the checks run
+        without a device."""
+        if name in self.tenants:
+            raise ValueError(f"tenant {name!r} is already registered")
+        if server is None:
+            plan = EncryptedCorpus(cq, scheme)  # planning only: the width and the scheme this model needs
+            p0, want = int(P0), plan.scheme
+            if plan.P0 != p0:
+                raise ValueError(f"tenant {name!r}: P0 = {p0} does not match the model's worst-case width {plan.P0}")
+        else:
+            p0, want = int(server.P0), server.scheme
+        for other, s in self.tenants.items():
+            if int(s.P0) != p0:
+                raise ValueError(f"tenant {name!r}: P0 = {p0} differs from tenant {other!r}'s {int(s.P0)}")
+            if s.scheme != want:
+                raise ValueError(f"tenant {name!r}: scheme parameters differ from tenant {other!r}'s")
+            break
+        if server is None:
+            server = CorpusServer(eval_keys, cq, p0, mask_key, self.device, scheme)
+        self.tenants[name] = server
+        self._drop_group()
+        return server
+
+    def _drop_group(self) -> None:
+        if self._group is not None:
+            self._group.close()  # its device workspace, now: not whenever the object is collected
+            self._group = None
+
+    def close(self) -> None:
+        """Releases the group's device workspace and every tenant's engine."""
+        self._drop_group()
+        for s in self.tenants.values():
+            if getattr(s, "engine", None) is not None:
+                s.engine.close()
+        self.tenants = {}
+
+    def _tenant(self, name) -> CorpusServer:
+        if name not in self.tenants:
+            raise ValueError(f"unknown tenant {name!r}")
+        return self.tenants[name]
+
+    def load(self, name, bodies, ids) -> int:
+        return self._tenant(name).load(bodies, ids)
+
+    def append(self, name, bodies, ids) -> int:
+        return self._tenant(name).append(bodies, ids)
+
+    def rekey(self, name, eval_keys: dict) -> None:
+        """CorpusServer.rekey of the tenant (its one-old-generation rules);
+        the group re-reads the tenant's keys at the next call."""
+        self._tenant(name).rekey(eval_keys)
+
+    def group(self):
+        if self._group is None:
+            from .engine import EngineGroup
+            self._group = EngineGroup([s.engine for s in self.tenants.values()])
+        return self._group
+
+    def rounds(self, requests: dict) -> list:
+        """corpus_rounds of this hub's tenants (planning only)."""
+        for name in requests:
+            if self._tenant(name).body is None:
+                raise ValueError(f"tenant {name!r} has no documents loaded")
+        return corpus_rounds(requests, {n: self.tenants[n]._plan for n in requests},
+                             {n: int(self.tenants[n].body.shape[0]) for n in requests})
+
+    def search_many(self, requests: dict) -> dict:
+        """requests: {name: (queries, min_similarity)} -> {name: [replies]},
+        version-2 replies for the tenant's CorpusClient.decrypt_replies, its
+        queries in order. A round's replies carry the round's width P. A
+        group round sets EVERY tenant's engine to P, those that sit out too
+        (a group needs one msg_bits); after a call that ran one, all engines
+        are set back to P0. A tenant's own CorpusServer sets its width per
+        chunk anyway, so results never depend on what a call left behind."""
+        out = {name: [] for name in requests}
+        names = list(self.tenants)
+        grouped = False
+        for rnd in self.rounds(requests):
+            if rnd["mode"] == "own":
+                for p in rnd["parts"]:
+                    queries, min_similarity = requests[p["name"]]
+                    q = np.atleast_2d(np.asarray(queries))
+                    ts = thresholds_for(min_similarity, q.shape[0])
+                    rng = p["queries"]
+                    out[p["name"]] += self.tenants[p["name"]].search_many(q[rng.start:rng.stop], [ts[i] for i in rng])
+                continue
+            P = rnd["P"]
+            grouped = True
+            for s in self.tenants.values():  # a group needs one msg_bits on every context
+                s.engine.set_msg_bits(P)
+            items = [None] * len(names)
+            for p in rnd["parts"]:
+                s = self.tenants[p["name"]]
+                items[names.index(p["name"])] = (s.body, s.ids, s.mask_key, s.engine.to_dev(p["W"]), p["cst"], p["Ts"],
+                                                 s.bit_levels, s.b_old)
+            res = self.group().search_seeded_queries(items)
+            for p in rnd["parts"]:
+                ga, gb = res[names.index(p["name"])]
+                B = int(self.tenants[p["name"]].body.shape[0])
+                out[p["name"]].append(pack_replies(ga.cpu().numpy().view(np.uint64), gb.cpu().numpy().view(np.uint64),
+                                                   B, P, p["Ts"]))
+        if grouped:
+            for s in self.tenants.values():
+                s.engine.set_msg_bits(s.P0)
+        return out

@@ -807,6 +807,58 @@ typedef struct fhe_group_query {
  * q * B + b). Argument errors (FHE_E_ARG) come before the device and key
  * checks; a participating tenant without a packing key is FHE_E_STATE. */
 int fhe_search_query_group_batch(fhe_group* group, const fhe_group_query* items, int32_t T, void* stream);
+
+/* ---- a group's key switch and stored-ciphertext search ---
+ * Host only: 1 when every round of the parameter set's sign schedule has a
+ * group kernel (fhe_group_create accepts contexts of it), 0 when a round runs
+ * the classic rotation, FHE_E_ARG for an invalid set. */
+int fhe_group_form(const fhe_params* params);
+/*
+ * fhe_keyswitch_batch over the padded layout (d_big: M x (kN+1), d_small:
+ * M x (n+1)): tenant t's rows with tenant t's key, word for word its own
+ * fhe_keyswitch_batch; padding rows are neither read nor written. With every
+ * tenant on the MFMA variant it is one digits launch and one GEMM launch
+ * whose 128-ciphertext workgroups each take their tenant's key planes from a
+ * table (timing: tenant 0's "keyswitch" bucket, k_keyswitch_mfma_grp<...>);
+ * otherwise one key switch per tenant. Checks as fhe_sign_group_batch, in its
+ * order, with fhe_keyswitch_batch's shift bound among the argument checks.
+ * More than 65535 digit groups (16 rows each, rounded up per tenant) or 8191
+ * blocks (128 rows each, rounded up per tenant) over ALL tenants of one call:
+ * FHE_E_ARG, "split the call", before any work is queued; the same bound
+ * holds for fhe_sign_group_batch and the two group search entries when they
+ * run the grouped key switch. */
+int fhe_keyswitch_group_batch(fhe_group* group, const uint64_t* d_big, const int64_t* h_counts, int32_t shift,
+                              uint64_t add_body, uint64_t* d_small, void* stream);
+/* One tenant's part of fhe_search_seeded_queries_group_batch: the arguments
+ * of fhe_search_seeded_queries_bridged_batch. Q = 0: the tenant sits this
+ * call out. */
+typedef struct fhe_group_corpus {
+  int32_t struct_size;        /* = sizeof(fhe_group_corpus); else FHE_E_ARG */
+  int32_t D;
+  const uint64_t* d_body;     /* B x D body words of the stored documents */
+  const uint64_t* d_id0;      /* B stream ids (device) */
+  int64_t B;
+  const uint32_t* h_mask_key; /* 8 words */
+  int64_t Q;
+  const int64_t* d_W;         /* Q x D weight rows */
+  int64_t cst;
+  const int64_t* h_T;         /* Q thresholds (host) */
+  int32_t levels_bit;
+  int32_t reserved;           /* 0 */
+  int64_t B_old;              /* documents b < B_old are under the rotated-out key */
+  uint64_t* d_glwe_acc;       /* ceil(Q B / N) x (k+1)N words */
+  uint64_t* d_glwe_bit;
+} fhe_group_corpus;
+/* The evaluation-only server of fhe_search_seeded_queries_bridged_batch for
+ * the T tenants of a group (items[t] for context t): per tenant the leveled
+ * step into its segment and, where B_old > 0, the bridge on its old
+ * documents' rows with its own bridge key; one fhe_sign_group_batch over all
+ * segments; then the tenant's two packings with its own packing key. Tenant
+ * t's outputs are word for word those of that entry on its own context.
+ * FHE_E_ARG first ("tenant t: ...": struct_size, the entry's bounds, nulls,
+ * B_old outside [0, B], levels_bit, 2^31 results and more), then the device,
+ * then FHE_E_STATE (no packing key, or no bridge key where B_old > 0). */
+int fhe_search_seeded_queries_group_batch(fhe_group* group, const fhe_group_corpus* items, int32_t T, void* stream);
 #ifdef __cplusplus
 }
 #endif

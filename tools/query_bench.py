@@ -74,6 +74,15 @@ with every, half and none of the documents old-generation, 24 steps after 4
 warm-up in rotating order, then the "bridge" and "pack" buckets of each leg
 and its parity with the restatement; it writes profiles/r15/rotated.json.
 
+With --stored-tenants (docs/AB_LOG_r16.md) it measures
+several key holders' STORED documents in one batched call, two-party, at 16
+dimensions, n_bits 6 (P0 = 21): CorpusHub.search_many for 8 tenants x (Q = 1,
+B = 128 stored documents) against the eight CorpusServer.search calls one
+after another and one tenant's 1 x 1024 search, 24 steps after 4 warm-up in
+rotating order, with the HIP-event split of each (rotations, key switches,
+bridge, packings, leveled step), then a second pass with every tenant rotated
+(all documents old-generation); it writes profiles/r16/stored_tenants.json.
+
 The floor of the leveled step is its output, B * (kN + 1) * 8 bytes, over the
 6.29 TB/s a float4 copy reaches on the MI355X; `floor_fraction` is that floor
 over the measured time. Prints one JSON line and writes it to --out.
@@ -412,6 +421,121 @@ def tenants(cq, oq, D: int, n_bits: int, steps: int, warmup: int, Tn: int = 8, B
         e.close()
     for c in corpora:
         c.engine.close()
+    return out
+
+
+def stored_tenants(cq, oq, D: int, n_bits: int, steps: int, warmup: int, Tn: int = 8, B: int = 128) -> dict:
+    """Several key holders' STORED documents behind one host,
+    two-party, one process. Two passes, none and all of every tenant's
+    documents old-generation (rotated tenants, bridged rows); per pass three
+    legs interleaved in rotating order: (a) CorpusHub.search_many for Tn
+    tenants x (Q = 1, B documents), (b) the Tn CorpusServer.search calls one
+    after another, (c) one tenant's search at Tn * B documents. Host clock
+    around each (reply copies included); per run the HIP-event split into
+    rotations, key switches, bridge, packings and leveled step (the profile
+    buckets, summed over the tenants' contexts); parity of (a)'s decrypted
+    replies with (b)'s and the restatement."""
+    import numpy as np
+    import torch
+    from oracle import quant_ref as Q
+    from fheicp.corpus import EncryptedCorpus
+    from fheicp.stored import CorpusClient, CorpusHub, CorpusServer
+    from fheicp import _lib
+    B_full = Tn * B
+    names = [f"tenant{t}" for t in range(Tn)]
+    _, docs = Q.make_corpus(D, B_full, seed=21)
+    qs = [Q.make_corpus(D, 1, seed=100 + t)[0] for t in range(Tn)]
+    buckets = ("blind_rotate", "keyswitch", "bridge", "pack", "linear_seeded")
+    orders = ("abc", "cba", "bca", "acb", "cab", "bac")
+    out = {"tenants": Tn, "Q": 1, "B": B, "B_full": B_full, "steps": steps, "warmup": warmup,
+           "build": _lib.lib().fhe_build_info().decode(), "passes": {}}
+    for pass_name in ("none_old", "all_old"):
+        hub, clients, corpora = CorpusHub(0), [], []
+        for t, name in enumerate(names):
+            c = EncryptedCorpus(cq).compile(key_seed=5 + t, device=0, noise_seed=6 + t)
+            client = CorpusClient(c, count=1024, pack_seed=17 + t)
+            corpora.append(c)
+            mine = docs[t * B:(t + 1) * B]                               # every tenant its own documents
+            hub.add_tenant(name, client.eval_keys(), cq, c.P0, c.mask_key)
+            hub.load(name, *client.encrypt_docs(mine))
+            if pass_name == "all_old":
+                client = client.rotate(key_seed=50 + t, pack_seed=60 + t, bridge_seed=70 + t, noise_seed=80 + t)
+                corpora.append(client.corpus)
+                hub.rekey(name, client.eval_keys())
+            clients.append(client)
+        servers = [hub.tenants[n] for n in names]
+        # leg (c): tenant 0's generation holds all Tn * B documents (old-generation in the rotated pass)
+        full = CorpusServer(clients[0].eval_keys(), cq, corpora[0].P0, corpora[0].mask_key)
+        if pass_name == "all_old":
+            first = CorpusClient.__new__(CorpusClient)
+            first.__dict__.update(clients[0].__dict__)
+            first.corpus = corpora[0]
+            full.load(*first.encrypt_docs(docs))
+            full.b_old, full.old_key_id = B_full, clients[0].bridge_from
+        else:
+            full.load(*clients[0].encrypt_docs(docs))
+        engines = [s.engine for s in servers] + [full.engine]
+        for e in engines:
+            e.profile(True)
+
+        def timed(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = fn()
+            torch.cuda.synchronize()
+            sec = time.perf_counter() - t0
+            split = {k: {"ms": 0.0, "launches": 0} for k in buckets}
+            for e in engines:
+                for k in buckets:
+                    r = e.profile_read(k)
+                    split[k]["ms"] += r["total_ms"]
+                    split[k]["launches"] += r["launches"]
+            return sec, res, split
+
+        runs = {"a": lambda: hub.search_many({n: (qs[t][None, :], 0.5) for t, n in enumerate(names)}),
+                "b": lambda: [servers[t].search(qs[t], 0.5) for t in range(Tn)],
+                "c": lambda: full.search(qs[0], 0.5)}
+        t_ = {k: [] for k in runs}
+        sp = {k: {b: [] for b in buckets} for k in runs}
+        last = {}
+        for i in range(warmup + steps):
+            for k in orders[i % len(orders)]:
+                sec, res, split = timed(runs[k])
+                last[k] = (res, split)
+                if i >= warmup:
+                    t_[k].append(sec)
+                    for b in buckets:
+                        sp[k][b].append(split[b]["ms"])
+        for e in engines:
+            e.profile(False)
+        parity = exact = True
+        for t, name in enumerate(names):
+            acc_a, below_a = clients[t].decrypt_replies(last["a"][0][name])
+            acc_b, below_b = clients[t].decrypt_replies(last["b"][0][t])
+            parity = parity and bool(torch.equal(acc_a, acc_b) and torch.equal(below_a, below_b))
+            ref = Q.corpus_accumulate(oq, cq.s_e, n_bits, qs[t], docs[t * B:(t + 1) * B])
+            scores = np.float64(Q.corpus_out_scale(oq, cq.s_e)) * ref.astype(np.float64)
+            exact = exact and bool(np.array_equal(acc_a[0].cpu().numpy(), ref) and
+                                   np.array_equal(below_a[0].cpu().numpy(), (scores < 0.5).astype(np.int64)))
+        med = {k: statistics.median(v) * 1e3 for k, v in t_.items()}
+        hub.search_many({n: (qs[t][None, :], 0.5) for t, n in enumerate(names)})  # names what the hub launched
+        res = {"a_hub_search_many_ms": med["a"], "a_min_ms": min(t_["a"]) * 1e3,
+               "b_sequential_searches_ms": med["b"], "b_min_ms": min(t_["b"]) * 1e3, "b_per_search_ms": med["b"] / Tn,
+               "c_one_tenant_full_search_ms": med["c"], "c_min_ms": min(t_["c"]) * 1e3,
+               "ratio_a_over_b": med["a"] / med["b"], "meets_bar_a_over_b": med["a"] <= 0.5 * med["b"],
+               "ratio_a_over_c": med["a"] / med["c"],
+               "event_split_ms": {k: {b: statistics.median(v) for b, v in sp[k].items()} for k in runs},
+               "event_split_launches": {k: {b: last[k][1][b]["launches"] for b in buckets} for k in runs},
+               "keyswitch_kernel_last_group": engines[0].kernel_name("keyswitch"),
+               "rounds": [r["mode"] for r in hub.rounds({n: (qs[t][None, :], 0.5) for t, n in enumerate(names)})],
+               "parity_with_sequential": parity, "bit_exact": exact}
+        res["meets_bar"] = res["meets_bar_a_over_b"] and parity and exact
+        out["passes"][pass_name] = res
+        for e in engines:
+            e.close()
+        for c in corpora:
+            c.engine.close()
+    out["meets_bar"] = all(p["meets_bar"] for p in out["passes"].values())
     return out
 
 
@@ -888,15 +1012,22 @@ def main() -> int:
                          "§8.12): CorpusServer.search_many at 8 queries x 128 documents and 1 x 1024 with every, half "
                          "and none of the documents old-generation (bridged), 24 interleaved steps after 4 warm-up, "
                          "with the bridge bucket's HIP-event time; writes profiles/r15/rotated.json")
+    ap.add_argument("--stored-tenants", action="store_true",
+                    help="several key holders' stored documents in one batched call (16-dim, n_bits 6, two-party, "
+                         "DESIGN.md §8.13): CorpusHub.search_many for 8 tenants x (Q = 1, B = 128) against the eight "
+                         "CorpusServer.search calls and one tenant's B = 1024 search, 24 interleaved steps after 4 "
+                         "warm-up, with the HIP-event split per run, then again with every tenant rotated (all "
+                         "documents old); writes profiles/r16/stored_tenants.json")
     ap.add_argument("--tenant-shape", type=int, nargs=2, default=[8, 128], metavar=("T", "B"),
-                    help="--tenants: T tenants of B documents each (default 8 128)")
+                    help="--tenants / --stored-tenants: T tenants of B documents each (default 8 128)")
     ap.add_argument("--out", default=None, help="default profiles/query_bench.json "
                                                 "(--multi-query: profiles/r11/multi_query.json, "
                                                 "--stored-queries: profiles/r12/stored_queries.json, "
                                                 "--private-queries: profiles/r13/private_queries.json)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = str(REPO / "profiles" / ("r15/rotated.json" if a.rotated else
+        a.out = str(REPO / "profiles" / ("r16/stored_tenants.json" if a.stored_tenants else
+                                         "r15/rotated.json" if a.rotated else
                                          "r14/tenants.json" if a.tenants else
                                          "r11/multi_query.json" if a.multi_query else
                                          "r12/stored_queries.json" if a.stored_queries else
@@ -916,6 +1047,16 @@ def main() -> int:
         res = {"bench": "query_bench --rotated", "device": torch.cuda.get_device_name(0), "D": 16, "n_bits": 6,
                "P0": cq.worst_msg_bits(), "build": _lib.lib().fhe_build_info().decode(), "rotated": ro,
                "bit_exact": ro["bit_exact"]}
+        line = json.dumps(res)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(line + "\n")
+        print(line)
+        return 0
+    if a.stored_tenants:
+        cq, oq = corpus_quant(16, 6)
+        tn = stored_tenants(cq, oq, 16, 6, steps=24, warmup=4, Tn=a.tenant_shape[0], B=a.tenant_shape[1])
+        res = {"bench": "query_bench --stored-tenants", "device": torch.cuda.get_device_name(0), "D": 16, "n_bits": 6,
+               "P0": cq.worst_msg_bits(), "stored_tenants": tn, "meets_bar": tn["meets_bar"]}
         line = json.dumps(res)
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(line + "\n")
