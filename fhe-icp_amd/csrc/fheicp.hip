@@ -31,6 +31,7 @@
 #include <mutex>
 #include <random>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/fhe_icp.h"
@@ -52,6 +53,20 @@ struct ProfAcc {
   double ms = 0;
   int64_t launches = 0, items = 0;
   const char* kernel = nullptr;  // the last launched instantiation (rocprofv3's name)
+};
+
+// a device workspace grown on demand (reserve below)
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+};
+// a gadget key switch's key (k_pack.h, k_bridge.h): gadget (beta, level), the
+// key [i][l][n1] as exported and its 8 byte planes in B-fragment order. A
+// level of 0: no key in place.
+struct GadgetKey {
+  u64* key = nullptr;
+  int8_t* planes = nullptr;
+  int beta = 0, level = 0;
 };
 
 struct fhe_ctx;
@@ -79,17 +94,14 @@ struct fhe_ctx {
   int mb_dbg = 0;      // A/B builds: FHEICP_MB_DBG timing variants of the multi-bit kernel
   int v4s = 0;         // A/B builds: FHEICP_V4S=1, key-stationary v4s for the 32-bit kernels too
   // workspace
-  void* ws = nullptr;
-  size_t ws_bytes = 0;
+  DevBuf ws;
   bool prof = false;
   ProfAcc prof_br, prof_brf[5], prof_ks;  // blind rotation on the main / fast / fast2 / mid / mid2 / mid0 gadget
   ProfAcc prof_enc;                       // the fused client encryption + leveled dot (k_encrypt_linear)
   ProfAcc prof_lq;                        // private-query leveled step: k_query_planes + k_linear_query_mfma
-  void* lq_ws = nullptr;                  // its query byte planes (grown on demand)
-  size_t lq_ws_bytes = 0;
+  DevBuf lq_ws;                           // its query byte planes (grown on demand)
   ProfAcc prof_ls;                        // stored-ciphertext leveled step, batched: k_linear_seeded_queries
-  void* lsq_cst = nullptr;                // fhe_linear_seeded_queries_batch's Q scaled constants (grown on demand)
-  size_t lsq_cst_words = 0;
+  DevBuf lsq_cst;                         // fhe_linear_seeded_queries_batch's Q scaled constants (grown on demand)
   int br_variant = 4;  // N=1024 blind rotation: 4 = a wave per GLWE component (k = 2, default), 2
                        // (two waves per ciphertext; forced by FHEICP_BR_VARIANT=2)
   // A/B builds only (FHEICP_AB, tools/build_variant.sh): other v4 shapes
@@ -99,35 +111,23 @@ struct fhe_ctx {
   int v4_dbg = 0;      // timing experiments only (FHEICP_V4_DBG), wrong results
   // i8-MFMA key switch: key byte planes and a digit/body workspace
   int8_t* ksk8 = nullptr;
-  void* ks_ws = nullptr;       // lane 0 (every caller stream)
-  size_t ks_ws_bytes = 0;
-  void* ks_ws1 = nullptr;      // lane 1: the second half of a pipelined compare
-  size_t ks_ws1_bytes = 0;
+  DevBuf ks_ws[2];  // lane 0 (every caller stream) and lane 1: the second half of a pipelined compare
   // two streams and their events for the pipelined sign extraction of
   // fhe_compare_batch (created on first use)
   hipStream_t lane_st[2] = {nullptr, nullptr};
   hipEvent_t lane_ev[3] = {nullptr, nullptr, nullptr};
   int ks_variant = 2;  // 2 = MFMA (i8 planes, any ks_level with kN % 64 == 0), 1 = VALU split-K
-  // LWE -> GLWE packing key (k_pack.h): gadget (pk_beta, pk_level), the key
-  // [i][l][(k+1)N] as exported and its 8 byte planes in B-fragment order
-  u64* pk = nullptr;
-  int8_t* pk8 = nullptr;
-  int pk_beta = 0, pk_level = 0;
-  void* pack_ws = nullptr;  // digits | zero bodies | the GEMM's count x (k+1)N result
-  size_t pack_ws_bytes = 0;
+  // LWE -> GLWE packing key (k_pack.h), (k+1)N columns
+  GadgetKey pack_key;
+  DevBuf pack_ws;           // digits | zero bodies | the GEMM's count x (k+1)N result
   ProfAcc prof_pack;        // fhe_pack_batch: k_pack_digits + the GEMM + k_pack_rotate
-  // LWE -> LWE bridge key of a key rotation (k_bridge.h): gadget (bk_beta,
-  // bk_level), the key [i][l][kN+1] as exported and its 8 byte planes
-  u64* bk = nullptr;
-  int8_t* bk8 = nullptr;
-  int bk_beta = 0, bk_level = 0;
-  void* bridge_ws = nullptr;  // digits | bodies | the GEMM's count x (kN+1) compact result
-  size_t bridge_ws_bytes = 0;
+  // LWE -> LWE bridge key of a key rotation (k_bridge.h), kN + 1 columns
+  GadgetKey bridge_key;
+  DevBuf bridge_ws;         // digits | bodies | the GEMM's count x (kN+1) compact result
   ProfAcc prof_bridge;      // fhe_bridge_batch: k_bridge_digits + the GEMM + k_bridge_scatter
   // both-private search (k_extprod.h): the query's Toeplitz byte planes |
   // zero bodies | the GEMM's G x (k+1)N result, allocated on first use
-  void* xp_ws = nullptr;
-  size_t xp_ws_bytes = 0;
+  DevBuf xp_ws;
   ProfAcc prof_xp;          // fhe_linear_ggsw_batch: k_extprod_planes + the GEMM + k_extprod_extract
   // the batched entries (k_extprod_q.h) use xp_ws as: the Q queries' byte
   // planes | the Q x G x (k+1)N result | the Q scaled constants
@@ -148,6 +148,28 @@ static int fail(fhe_ctx* ctx, int code, const std::string& msg) {
     hipError_t e_ = (x);                                                                        \
     if (e_ != hipSuccess) return fail(ctx, FHE_E_DEVICE, std::string(#x ": ") + hipGetErrorString(e_)); \
   } while (0)
+
+// Grows `b` to at least `bytes`; what it held is lost. A grow synchronises the
+// device before it frees (work queued on any stream may still read the old
+// buffer). The record is empty while the allocation is in flight, so a failed
+// one leaves it empty and the next call allocates again. The allocation's
+// failure returns the caller's code and message (ctx == nullptr: a group's,
+// the message with its "group: " prefix) and clears HIP's error.
+static int reserve(fhe_ctx* ctx, DevBuf& b, size_t bytes, int code, const char* msg) {
+  if (bytes <= b.bytes) return FHE_OK;
+  if (b.p) {
+    HIPCHK(ctx, hipDeviceSynchronize());
+    HIPCHK(ctx, hipFree(b.p));
+  }
+  b = DevBuf{};
+  if (hipMalloc(&b.p, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    b.p = nullptr;
+    return fail(ctx, code, msg);
+  }
+  b.bytes = bytes;
+  return FHE_OK;
+}
 
 static int ilog2i(int x) {
   int r = 0;
@@ -442,6 +464,44 @@ static int sign_digits(const fhe_params& p) {
   return d;
 }
 
+// The K split of the i8 MFMA key-switch GEMM (k_keyswitch_mfma and its group
+// form) over S workgroups when the `ktiles` of its (ciphertext block, column
+// group) grid alone would leave CUs idle: towards `target` workgroups, ~2 per
+// CU (S = 3 at 1024 ciphertexts; 1, 2, 4-12 measured slower there,
+// tools/ks_sweep.py). Slices are whole ring rounds, so every slice holds at
+// least KSM_RING k-blocks for the kernel's prologue; the partial sums meet by
+// 64-bit atomics in a zeroed result. `force` > 0 (A/B builds) sets S instead.
+struct KsmSplit {
+  int S, kslice;
+};
+static KsmSplit ksm_split(int KB, int64_t ktiles, int64_t target, int force = 0) {
+  int S = (int)std::max<int64_t>(1, std::min<int64_t>(KB / KSM_RING, target / std::max<int64_t>(1, ktiles)));
+  if (force > 0) S = std::max(1, std::min(KB / KSM_RING, force));
+  const int kslice = (KB / KSM_RING + S - 1) / S * KSM_RING;
+  return {(KB + kslice - 1) / kslice, kslice};
+}
+// The instantiated (byte planes Q, column blocks CB) pairs of those two
+// kernels: f(Q, CB) with both as compile-time constants; false for any other pair.
+template <class F>
+static bool ksm_dispatch(int planes, int CB, F&& f) {
+#define KSM_PAIR(Q, C) \
+  case Q * 4 + C: f(std::integral_constant<int, Q>{}, std::integral_constant<int, C>{}); return true
+  switch (planes * 4 + CB) {
+    KSM_PAIR(3, 3);
+    KSM_PAIR(4, 3);
+    KSM_PAIR(5, 1);
+    KSM_PAIR(6, 1);
+    KSM_PAIR(7, 1);
+    KSM_PAIR(8, 1);
+    default: return false;
+  }
+#undef KSM_PAIR
+}
+// rocprofv3's name of an instantiation, for a profile bucket: "base<Q, C>"
+static std::string ksm_name(const char* base, int Q, int C) {
+  return std::string(base) + "<" + std::to_string(Q) + ", " + std::to_string(C) + ">";
+}
+
 extern "C" {
 
 size_t fhe_bsk_words(const fhe_params* p) {
@@ -573,13 +633,14 @@ void fhe_ctx_destroy(fhe_ctx* ctx) {
     // teardown: nothing useful can be done about a failed free
     (void)hipSetDevice(ctx->device);
     for (void* ptr : {(void*)ctx->s_small, (void*)ctx->s_big, (void*)ctx->bsk, (void*)ctx->ksk,
-                      (void*)ctx->ksk_colsum, (void*)ctx->bsk_fft, (void*)ctx->tw, (void*)ctx->twist, ctx->ws,
+                      (void*)ctx->ksk_colsum, (void*)ctx->bsk_fft, (void*)ctx->tw, (void*)ctx->twist, ctx->ws.p,
                       (void*)ctx->bskf[0], (void*)ctx->bskf[1], (void*)ctx->bskf_fft[0], (void*)ctx->bskf_fft[1],
                       (void*)ctx->bskf[2], (void*)ctx->bskf[3], (void*)ctx->bskf_fft[2], (void*)ctx->bskf_fft[3],
                       (void*)ctx->bskf[4], (void*)ctx->bskf_fft[4],
-                      (void*)ctx->ksk8, (void*)ctx->ks_ws, (void*)ctx->ks_ws1, (void*)ctx->tw4, (void*)ctx->bsk_fft_v2,
-                      (void*)ctx->psi, (void*)ctx->mb_msg, ctx->lq_ws, (void*)ctx->pk, (void*)ctx->pk8,
-                      ctx->pack_ws, ctx->xp_ws, ctx->lsq_cst, (void*)ctx->bk, (void*)ctx->bk8, ctx->bridge_ws})
+                      (void*)ctx->ksk8, ctx->ks_ws[0].p, ctx->ks_ws[1].p, (void*)ctx->tw4, (void*)ctx->bsk_fft_v2,
+                      (void*)ctx->psi, (void*)ctx->mb_msg, ctx->lq_ws.p, (void*)ctx->pack_key.key,
+                      (void*)ctx->pack_key.planes, ctx->pack_ws.p, ctx->xp_ws.p, ctx->lsq_cst.p,
+                      (void*)ctx->bridge_key.key, (void*)ctx->bridge_key.planes, ctx->bridge_ws.p})
       (void)hipFree(ptr);
     for (hipStream_t s : ctx->lane_st)
       if (s) (void)hipStreamDestroy(s);
@@ -1116,17 +1177,7 @@ static int ks_reserve(fhe_ctx* ctx, int64_t count, int lane) {
   const fhe_params& p = ctx->p;
   const int K = p.k * p.N * p.ks_level;
   const size_t need = (size_t)((count + 15) / 16) * 16 * K + 8 * (size_t)count;
-  void*& ws = lane ? ctx->ks_ws1 : ctx->ks_ws;
-  size_t& have = lane ? ctx->ks_ws1_bytes : ctx->ks_ws_bytes;
-  if (need <= have) return FHE_OK;
-  if (ws) {
-    HIPCHK(ctx, hipDeviceSynchronize());
-    HIPCHK(ctx, hipFree(ws));
-    ws = nullptr;
-  }
-  HIPCHK(ctx, hipMalloc(&ws, need));
-  have = need;
-  return FHE_OK;
+  return reserve(ctx, ctx->ks_ws[lane], need, FHE_E_DEVICE, "hipMalloc of the key-switch workspace failed");
 }
 
 static int keyswitch_lane(fhe_ctx* ctx, const uint64_t* d_big, int64_t count, int32_t shift, uint64_t add_body,
@@ -1141,40 +1192,29 @@ static int keyswitch_lane(fhe_ctx* ctx, const uint64_t* d_big, int64_t count, in
     int rc = ks_reserve(ctx, count, lane);
     if (rc) return rc;
     if (ncb > 65535) return fail(ctx, FHE_E_ARG, "keyswitch batch too large: split the call");
-    void* ws = lane ? ctx->ks_ws1 : ctx->ks_ws;
+    void* ws = ctx->ks_ws[lane].p;
     uint32_t* D = (uint32_t*)ws;
     u64* body = (u64*)((char*)ws + dbytes);
     const int R = ks_round_bits(p);
-    // K split over S workgroups when the (ciphertext block, column group)
-    // grid alone would leave CUs idle: ~2 workgroups per CU (S = 3 at 1024
-    // ciphertexts; 1, 2, 4-12 measured slower there, tools/ks_sweep.py)
     const int64_t ctb = (count + KSM_CTS - 1) / KSM_CTS, ktiles = ctb * (NB / CB);
-    int S = (int)std::max<int64_t>(1, std::min<int64_t>(KB / KSM_RING, 512 / ktiles));
+    int force = 0;
 #ifdef FHEICP_KS_AB  // A/B builds only: the split forced (tools/build_variant.sh)
-    if (const char* e = getenv("FHEICP_KS_S")) S = std::max(1, std::min(KB / KSM_RING, atoi(e)));
+    if (const char* e = getenv("FHEICP_KS_S")) force = std::max(1, atoi(e));
 #endif
-    const int kslice = (KB / KSM_RING + S - 1) / S * KSM_RING;
-    S = (KB + kslice - 1) / kslice;
+    const auto [S, kslice] = ksm_split(KB, ktiles, 512, force);
     hipEvent_t e1;
     prof_begin(ctx, ctx->prof_ks, st, &e1);
     // the digits kernel also zeroes the output the split's atomics add into
     hipLaunchKernelGGL(k_ks_digits, dim3((unsigned)(p.k * p.N / 64), (unsigned)ncb), dim3(256), 0, st, d_big, count,
                        p.k * p.N, p.ks_base_log, p.ks_level, shift, add_body, KB, D, body, S > 1 ? n1 : 0, d_small);
     const dim3 gks((unsigned)(ktiles * S));
-#define KSM(Q, C)                                                                                                    \
-  ctx->prof_ks.kernel = "k_keyswitch_mfma<" #Q ", " #C ">";                                                         \
-  hipLaunchKernelGGL((k_keyswitch_mfma<Q, C>), gks, dim3(256), 0, st, (const v4i*)D, (const v4i*)ctx->ksk8, body,    \
-                     count, n1, NB, KB, R, S, kslice, d_small)
-    switch ((8 - R / 8) * 4 + CB) {
-      case 3 * 4 + 3: KSM(3, 3); break;
-      case 4 * 4 + 3: KSM(4, 3); break;
-      case 5 * 4 + 1: KSM(5, 1); break;
-      case 6 * 4 + 1: KSM(6, 1); break;
-      case 7 * 4 + 1: KSM(7, 1); break;
-      case 8 * 4 + 1: KSM(8, 1); break;
-      default: return fail(ctx, FHE_E_ARG, "key-switch byte planes out of range");
-    }
-#undef KSM
+    const bool known = ksm_dispatch(8 - R / 8, CB, [&, S = S, kslice = kslice](auto q, auto c) {
+      static const std::string name = ksm_name("k_keyswitch_mfma", q, c);  // one per instantiation
+      ctx->prof_ks.kernel = name.c_str();
+      hipLaunchKernelGGL((k_keyswitch_mfma<q, c>), gks, dim3(256), 0, st, (const v4i*)D, (const v4i*)ctx->ksk8, body,
+                         count, n1, NB, KB, R, S, kslice, d_small);
+    });
+    if (!known) return fail(ctx, FHE_E_ARG, "key-switch byte planes out of range");
     prof_end(ctx, ctx->prof_ks, st, e1, count);
     HIPCHK(ctx, hipGetLastError());
     return FHE_OK;
@@ -1188,6 +1228,29 @@ static int keyswitch_lane(fhe_ctx* ctx, const uint64_t* d_big, int64_t count, in
                      ks_round_bits(p), d_small);
   prof_end(ctx, ctx->prof_ks, st, e1, count);
   HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+// The gadget key switches and the both-private product run that GEMM on 8
+// unrounded byte planes, one column block per workgroup: rows x KB*64 digits
+// `D` times the planes `K8` (KB*64 x NB*16), plus `body` on column n1 - 1,
+// into the rows x n1 words of `M`. gemm81_split is its K split, which the
+// caller's digits kernel needs first: with S > 1 that kernel zeroes M for the
+// partial sums. gemm81 names the kernel in the caller's bucket and launches it
+// between the caller's own kernels, inside the caller's prof_begin / prof_end.
+static KsmSplit gemm81_split(int64_t rows, int NB, int KB) {
+  return ksm_split(KB, (rows + KSM_CTS - 1) / KSM_CTS * NB, 512);
+}
+static int gemm81(fhe_ctx* ctx, ProfAcc& acc, const char* what, const void* D, const void* K8, const u64* body,
+                  int64_t rows, int n1, int NB, int KB, u64* M, hipStream_t st) {
+  const auto [S, kslice] = gemm81_split(rows, NB, KB);
+  const int64_t grid = (rows + KSM_CTS - 1) / KSM_CTS * NB * S;
+  // cannot fire below the callers' own limits (65,535 blocks of 16 rows; a
+  // both-private workspace of 2^31 grid tiles is past any device's memory)
+  if (grid > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, std::string(what) + " batch too large: split the call");
+  acc.kernel = "k_keyswitch_mfma<8, 1>";
+  hipLaunchKernelGGL((k_keyswitch_mfma<8, 1>), dim3((unsigned)grid), dim3(256), 0, st, (const v4i*)D, (const v4i*)K8,
+                     body, rows, n1, NB, KB, 0, S, kslice, M);
   return FHE_OK;
 }
 
@@ -1599,16 +1662,7 @@ int fhe_pbs_table_gadget(const fhe_params* params) {
 }
 
 static int ensure_ws(fhe_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->ws_bytes) return FHE_OK;
-  if (ctx->ws) {
-    HIPCHK(ctx, hipDeviceSynchronize());
-    HIPCHK(ctx, hipFree(ctx->ws));
-    ctx->ws = nullptr;
-    ctx->ws_bytes = 0;
-  }
-  HIPCHK(ctx, hipMalloc(&ctx->ws, bytes));
-  ctx->ws_bytes = bytes;
-  return FHE_OK;
+  return reserve(ctx, ctx->ws, bytes, FHE_E_DEVICE, "hipMalloc of the context workspace failed");
 }
 
 // bit extraction driver; `small` is caller-provided scratch (count x (n+1))
@@ -1818,7 +1872,7 @@ int fhe_sign_batch(fhe_ctx* ctx, uint64_t* d_ct_v, int64_t count, uint64_t* d_si
   if (count == 0) return FHE_OK;
   rc = ensure_ws(ctx, 8 * (size_t)count * fhe_small_lwe_words(&ctx->p));
   if (rc) return rc;
-  return sign_extract_batch(ctx, d_ct_v, count, d_sign, (uint64_t*)ctx->ws, (hipStream_t)stream);
+  return sign_extract_batch(ctx, d_ct_v, count, d_sign, (uint64_t*)ctx->ws.p, (hipStream_t)stream);
 }
 
 int fhe_sign_trace_batch(fhe_ctx* ctx, uint64_t* d_ct_v, int64_t count, const int32_t* h_sched, int32_t rounds,
@@ -1848,7 +1902,7 @@ int fhe_sign_trace_batch(fhe_ctx* ctx, uint64_t* d_ct_v, int64_t count, const in
   tr.sched = h_sched ? sched : nullptr;
   tr.rounds = rounds;
   tr.phase = d_phase;
-  return sign_extract(ctx, d_ct_v, count, d_sign, (uint64_t*)ctx->ws, (hipStream_t)stream, 0, &tr);
+  return sign_extract(ctx, d_ct_v, count, d_sign, (uint64_t*)ctx->ws.p, (hipStream_t)stream, 0, &tr);
 }
 
 int fhe_bit_extract_batch(fhe_ctx* ctx, uint64_t* d_ct_v, int64_t count, uint64_t* d_refreshed, uint64_t* d_sign,
@@ -1860,7 +1914,7 @@ int fhe_bit_extract_batch(fhe_ctx* ctx, uint64_t* d_ct_v, int64_t count, uint64_
   if (count == 0) return FHE_OK;
   rc = ensure_ws(ctx, 8 * (size_t)count * fhe_small_lwe_words(&ctx->p));
   if (rc) return rc;
-  return bit_extract(ctx, d_ct_v, count, d_refreshed, d_sign, (uint64_t*)ctx->ws, (hipStream_t)stream);
+  return bit_extract(ctx, d_ct_v, count, d_refreshed, d_sign, (uint64_t*)ctx->ws.p, (hipStream_t)stream);
 }
 
 static int compare_impl(fhe_ctx* ctx, const int64_t* d_qx, int64_t B, int32_t D, const int64_t* d_w, int64_t cst,
@@ -1878,7 +1932,7 @@ static int compare_impl(fhe_ctx* ctx, const int64_t* d_qx, int64_t B, int32_t D,
   const size_t bytes = 8 * (2 * (size_t)B * Wb + (size_t)B * Ws + (size_t)B);
   rc = ensure_ws(ctx, bytes);
   if (rc) return rc;
-  u64* ctv = (u64*)ctx->ws;
+  u64* ctv = (u64*)ctx->ws.p;
   u64* sgn = ctv + (size_t)B * Wb;
   u64* small = sgn + (size_t)B * Wb;
   int64_t* v = (int64_t*)(small + (size_t)B * Ws);
@@ -1924,7 +1978,7 @@ static int score_impl(fhe_ctx* ctx, const int64_t* d_qx, int64_t B, int32_t D, c
   // workspace: ct_v (B big) | v (B)
   rc = ensure_ws(ctx, 8 * ((size_t)B * Wb + (size_t)B));
   if (rc) return rc;
-  u64* ctv = (u64*)ctx->ws;
+  u64* ctv = (u64*)ctx->ws.p;
   int64_t* v = (int64_t*)(ctv + (size_t)B * Wb);
   rc = encrypt_linear_impl(ctx, d_qx, B, D, K, id0, d_w, cst - T, ctv, stream);
   if (rc) return rc;
@@ -1959,7 +2013,7 @@ int fhe_compare_seeded_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_
   // workspace: ct_v (B big) | sign (B big) | small (B) | v (B)
   rc = ensure_ws(ctx, 8 * (2 * (size_t)B * Wb + (size_t)B * Ws + (size_t)B));
   if (rc) return rc;
-  u64* ctv = (u64*)ctx->ws;
+  u64* ctv = (u64*)ctx->ws.p;
   u64* sgn = ctv + (size_t)B * Wb;
   u64* small = sgn + (size_t)B * Wb;
   int64_t* v = (int64_t*)(small + (size_t)B * Ws);
@@ -2019,23 +2073,14 @@ int fhe_linear_query_batch(fhe_ctx* ctx, const uint64_t* d_ct_q, const void* d_d
   if (rblocks > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "query document batch too large: split the call");
   // the query's byte planes: KB * 64 rows x NB * 16 columns x 8 planes
   const size_t need = (size_t)KB * 64 * NB * 16 * 8;
-  if (need > ctx->lq_ws_bytes) {
-    if (ctx->lq_ws) {
-      HIPCHK(ctx, hipDeviceSynchronize());
-      HIPCHK(ctx, hipFree(ctx->lq_ws));
-      ctx->lq_ws = nullptr;
-      ctx->lq_ws_bytes = 0;
-    }
-    HIPCHK(ctx, hipMalloc(&ctx->lq_ws, need));
-    ctx->lq_ws_bytes = need;
-  }
+  if ((rc = reserve(ctx, ctx->lq_ws, need, FHE_E_DEVICE, "hipMalloc of the query plane workspace failed"))) return rc;
   hipEvent_t e1;
   prof_begin(ctx, ctx->prof_lq, st, &e1);
   ctx->prof_lq.kernel = "k_linear_query_mfma";
   hipLaunchKernelGGL(k_query_planes, dim3((unsigned)(KB * NB)), dim3(64), 0, st, d_ct_q, (int)D, W, NB, KB, d_w,
-                     (v4i*)ctx->lq_ws);
+                     (v4i*)ctx->lq_ws.p);
   hipLaunchKernelGGL(k_linear_query_mfma, dim3((unsigned)rblocks, (unsigned)((NB + LQ_CB - 1) / LQ_CB)), dim3(256), 0,
-                     st, (const v4i*)d_docs8, (const v4i*)ctx->lq_ws, B, W, NB, KB, (u64)cst << (64 - p.msg_bits),
+                     st, (const v4i*)d_docs8, (const v4i*)ctx->lq_ws.p, B, W, NB, KB, (u64)cst << (64 - p.msg_bits),
                      d_out);
   prof_end(ctx, ctx->prof_lq, st, e1, B);
   HIPCHK(ctx, hipGetLastError());
@@ -2079,21 +2124,10 @@ int fhe_linear_queries_batch(fhe_ctx* ctx, const uint64_t* d_ct_q, int64_t Q, co
   // Q plane sets (KB * 64 rows x NB * 16 columns x 8 planes each), then the Q
   // pre-scaled constants
   const size_t planes = (size_t)KB * 64 * NB * 16 * 8 * (size_t)Q, need = planes + 8 * (size_t)Q;
-  if (need > ctx->lq_ws_bytes) {
-    if (ctx->lq_ws) {
-      HIPCHK(ctx, hipDeviceSynchronize());
-      HIPCHK(ctx, hipFree(ctx->lq_ws));
-      ctx->lq_ws = nullptr;
-      ctx->lq_ws_bytes = 0;
-    }
-    if (hipMalloc(&ctx->lq_ws, need) != hipSuccess) {
-      (void)hipGetLastError();
-      ctx->lq_ws = nullptr;
-      return fail(ctx, FHE_E_NOMEM, "queries plane workspace: out of device memory (fewer queries per call)");
-    }
-    ctx->lq_ws_bytes = need;
-  }
-  u64* d_cst = (u64*)((char*)ctx->lq_ws + planes);
+  if ((rc = reserve(ctx, ctx->lq_ws, need, FHE_E_NOMEM,
+                    "queries plane workspace: out of device memory (fewer queries per call)")))
+    return rc;
+  u64* d_cst = (u64*)((char*)ctx->lq_ws.p + planes);
   std::vector<u64> cs((size_t)Q);
   for (int64_t q = 0; q < Q; ++q) cs[(size_t)q] = (u64)h_cst[q] << (64 - p.msg_bits);
   if ((rc = store_words(ctx, d_cst, cs.data(), Q, st))) return rc;
@@ -2101,14 +2135,14 @@ int fhe_linear_queries_batch(fhe_ctx* ctx, const uint64_t* d_ct_q, int64_t Q, co
   prof_begin(ctx, ctx->prof_lq, st, &e1);
   ctx->prof_lq.kernel = "k_linear_queries_mfma";
   hipLaunchKernelGGL(k_query_planes, dim3((unsigned)(KB * NB), (unsigned)Q), dim3(64), 0, st, d_ct_q, (int)D, W, NB, KB,
-                     d_w, (v4i*)ctx->lq_ws);
+                     d_w, (v4i*)ctx->lq_ws.p);
 #ifdef FHEICP_LQ_QLOOP
   const unsigned qgrid = 1;  // A/B: the waves loop over the queries
 #else
   const unsigned qgrid = (unsigned)Q;
 #endif
   hipLaunchKernelGGL(k_linear_queries_mfma, dim3((unsigned)rblocks, (unsigned)((NB + LQ_CB - 1) / LQ_CB), qgrid),
-                     dim3(256), 0, st, (const v4i*)d_docs8, (const v4i*)ctx->lq_ws, B, W, NB, KB, (const u64*)d_cst,
+                     dim3(256), 0, st, (const v4i*)d_docs8, (const v4i*)ctx->lq_ws.p, B, W, NB, KB, (const u64*)d_cst,
                      d_out, (int)Q);
   prof_end(ctx, ctx->prof_lq, st, e1, Q * B);
   HIPCHK(ctx, hipGetLastError());
@@ -2121,10 +2155,26 @@ int fhe_linear_queries_batch(fhe_ctx* ctx, const uint64_t* d_ct_q, int64_t Q, co
 static bool pack_gadget_ok(int32_t beta, int32_t L) {
   return beta >= 1 && beta <= 7 && L >= 1 && L <= 8 && beta * L + L <= 62;
 }
-static int pack_gadget_args(fhe_ctx* ctx, int32_t beta, int32_t L) {
+// What tells the two gadget keys apart: where the context holds the key, its
+// columns n1 ((k+1)N for the packing key, kN + 1 for the bridge key; the byte
+// planes pad them to NB whole 16-column blocks) and the words of its messages.
+// Each key's keygen kernel stays at its ABI entry: their arguments differ.
+struct GadgetDesc {
+  GadgetKey fhe_ctx::*key;
+  int (*n1)(const fhe_params&);
+  const char *noun, *abi;
+  int NB(const fhe_params& p) const { return (n1(p) + KSM_NB_COLS - 1) / KSM_NB_COLS; }
+  size_t words(const fhe_params& p, int L) const { return (size_t)p.k * p.N * L * n1(p); }
+};
+static const GadgetDesc PACK_KEY = {&fhe_ctx::pack_key, [](const fhe_params& p) { return (p.k + 1) * p.N; }, "packing",
+                                    "pack"};
+static const GadgetDesc BRIDGE_KEY = {&fhe_ctx::bridge_key, [](const fhe_params& p) { return p.k * p.N + 1; }, "bridge",
+                                      "bridge"};
+
+static int gadget_args(fhe_ctx* ctx, const GadgetDesc& d, int32_t beta, int32_t L) {
   if (!pack_gadget_ok(beta, L))
-    return fail(ctx, FHE_E_ARG, "packing gadget out of range (1 <= base_log <= 7, 1 <= level <= 8, "
-                                "level * (base_log + 1) <= 62)");
+    return fail(ctx, FHE_E_ARG, std::string(d.noun) + " gadget out of range (1 <= base_log <= 7, 1 <= level <= 8, "
+                                                      "level * (base_log + 1) <= 62)");
   return FHE_OK;
 }
 size_t fhe_pack_key_words(const fhe_params* p, int32_t base_log, int32_t level) {
@@ -2180,84 +2230,102 @@ int fhe_pack_plan(const fhe_params* params, int64_t count, double in_var, int32_
   return FHE_OK;
 }
 
-// (re)allocate the packing key's buffers for gadget (beta, L)
-static int pack_key_alloc(fhe_ctx* ctx, int32_t beta, int32_t L) {
-  const size_t words = fhe_pack_key_words(&ctx->p, beta, L);
-  if (ctx->pk && fhe_pack_key_words(&ctx->p, ctx->pk_beta, ctx->pk_level) != words) {
+// (re)allocate a gadget key's buffers for L levels: 8 * words key bytes and
+// kN * L rows x NB * 16 columns x 8 planes (for the packing key 8 * words too)
+static int gadget_key_alloc(fhe_ctx* ctx, const GadgetDesc& d, int32_t L) {
+  GadgetKey& k = ctx->*d.key;
+  const size_t words = d.words(ctx->p, L);
+  if (k.key && d.words(ctx->p, k.level) != words) {
     HIPCHK(ctx, hipDeviceSynchronize());
-    HIPCHK(ctx, hipFree(ctx->pk));
-    ctx->pk = nullptr;
-    HIPCHK(ctx, hipFree(ctx->pk8));
-    ctx->pk8 = nullptr;
+    HIPCHK(ctx, hipFree(k.key));
+    k.key = nullptr;
+    HIPCHK(ctx, hipFree(k.planes));
+    k.planes = nullptr;
   }
-  ctx->pk_beta = ctx->pk_level = 0;
-  if (!ctx->pk) {
-    HIPCHK(ctx, hipMalloc(&ctx->pk, 8 * words));
-    HIPCHK(ctx, hipMalloc(&ctx->pk8, 8 * words));
+  k.beta = k.level = 0;
+  if (!k.key) {
+    HIPCHK(ctx, hipMalloc(&k.key, 8 * words));
+    if (hipMalloc(&k.planes, (size_t)ctx->p.k * ctx->p.N * L * d.NB(ctx->p) * KSM_NB_COLS * 8) != hipSuccess) {
+      (void)hipFree(k.key);
+      k.key = nullptr;
+      return fail(ctx, FHE_E_DEVICE, "hipMalloc of the " + std::string(d.noun) + " key's byte planes failed");
+    }
   }
   return FHE_OK;
 }
 // the key's 8 byte planes in B-fragment order: k_ksk_to_i8 on the layout
-// [i][l][(k+1)N] with no rounding
-static int pack_key_planes(fhe_ctx* ctx, int32_t beta, int32_t L, hipStream_t st) {
+// [i][l][n1] with no rounding (the padded columns of a last block are zero)
+static int gadget_key_planes(fhe_ctx* ctx, const GadgetDesc& d, int32_t beta, int32_t L, hipStream_t st) {
   const fhe_params& p = ctx->p;
-  const int big = p.k * p.N, K = big * L, n1 = (p.k + 1) * p.N;
-  const int64_t tot = (int64_t)K * n1;
-  hipLaunchKernelGGL(k_ksk_to_i8, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, ctx->pk, K, big, (int)L, n1,
-                     n1 / 16, 0, 8, ctx->pk8);
+  GadgetKey& k = ctx->*d.key;
+  const int big = p.k * p.N, K = big * L, n1 = d.n1(p), NB = d.NB(p);
+  const int64_t tot = (int64_t)K * NB * KSM_NB_COLS;
+  hipLaunchKernelGGL(k_ksk_to_i8, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, k.key, K, big, (int)L, n1, NB,
+                     0, 8, k.planes);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(st));
-  ctx->pk_beta = beta;
-  ctx->pk_level = L;
+  k.beta = beta;
+  k.level = L;
   return FHE_OK;
+}
+static int need_gadget_key(fhe_ctx* ctx, const GadgetDesc& d) {
+  int rc = need_device(ctx);
+  if (rc) return rc;
+  if (!(ctx->*d.key).level)
+    return fail(ctx, FHE_E_STATE, "no " + std::string(d.noun) + " key: call fhe_keygen_" + d.abi + "_key or fhe_import_" +
+                                      d.abi + "_key");
+  return FHE_OK;
+}
+// the ABI entries' tails, after their own checks (whose order differs)
+static int gadget_key_export(fhe_ctx* ctx, const GadgetDesc& d, uint64_t* h_out) {
+  const GadgetKey& k = ctx->*d.key;
+  HIPCHK(ctx, hipDeviceSynchronize());
+  HIPCHK(ctx, hipMemcpy(h_out, k.key, 8 * d.words(ctx->p, k.level), hipMemcpyDeviceToHost));
+  return FHE_OK;
+}
+static int gadget_key_import(fhe_ctx* ctx, const GadgetDesc& d, int32_t beta, int32_t L, const uint64_t* h_in) {
+  int rc = gadget_key_alloc(ctx, d, L);
+  if (rc) return rc;
+  HIPCHK(ctx, hipMemcpy((ctx->*d.key).key, h_in, 8 * d.words(ctx->p, L), hipMemcpyHostToDevice));
+  return gadget_key_planes(ctx, d, beta, L, nullptr);
 }
 
 int fhe_keygen_pack_key_key(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint32_t h_key[8], void* stream) {
   if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
-  int rc = pack_gadget_args(ctx, base_log, level);  // argument errors first: a host-only context reports them too
+  int rc = gadget_args(ctx, PACK_KEY, base_log, level);  // argument errors first: a host-only context reports them too
   if (rc) return rc;
   if ((rc = need_secret(ctx))) return rc;
   ChaKey K;
   if (!key_arg(h_key, K)) return fail(ctx, FHE_E_ARG, "null key");
-  if ((rc = pack_key_alloc(ctx, base_log, level))) return rc;
+  if ((rc = gadget_key_alloc(ctx, PACK_KEY, level))) return rc;
   const fhe_params& p = ctx->p;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_keygen_pack, dim3((unsigned)(p.k * p.N * level)), dim3(256), 8 * (size_t)p.N + p.N, st, K, p.N,
-                     p.k, (int)level, (int)base_log, p.glwe_noise_bits, ctx->s_big, ctx->pk);
+                     p.k, (int)level, (int)base_log, p.glwe_noise_bits, ctx->s_big, ctx->pack_key.key);
   HIPCHK(ctx, hipGetLastError());
-  return pack_key_planes(ctx, base_log, level, st);
+  return gadget_key_planes(ctx, PACK_KEY, base_log, level, st);
 }
 int fhe_keygen_pack_key(fhe_ctx* ctx, int32_t base_log, int32_t level, uint64_t seed, void* stream) {
   const ChaKey K = key_from_seed(seed);
   return fhe_keygen_pack_key_key(ctx, base_log, level, K.w, stream);
 }
 
-static int need_pack_key(fhe_ctx* ctx) {
-  int rc = need_device(ctx);
-  if (rc) return rc;
-  if (!ctx->pk_level) return fail(ctx, FHE_E_STATE, "no packing key: call fhe_keygen_pack_key or fhe_import_pack_key");
-  return FHE_OK;
-}
+static int need_pack_key(fhe_ctx* ctx) { return need_gadget_key(ctx, PACK_KEY); }
 
 int fhe_export_pack_key(fhe_ctx* ctx, uint64_t* h_out) {
   int rc = need_pack_key(ctx);
   if (rc) return rc;
   if (!h_out) return fail(ctx, FHE_E_ARG, "null buffer");
-  HIPCHK(ctx, hipDeviceSynchronize());
-  HIPCHK(ctx, hipMemcpy(h_out, ctx->pk, 8 * fhe_pack_key_words(&ctx->p, ctx->pk_beta, ctx->pk_level),
-                        hipMemcpyDeviceToHost));
-  return FHE_OK;
+  return gadget_key_export(ctx, PACK_KEY, h_out);
 }
 
 int fhe_import_pack_key(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint64_t* h_in) {
   if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
-  int rc = pack_gadget_args(ctx, base_log, level);  // argument errors first
+  int rc = gadget_args(ctx, PACK_KEY, base_log, level);  // argument errors first
   if (rc) return rc;
   if ((rc = need_device(ctx))) return rc;
   if (!h_in) return fail(ctx, FHE_E_ARG, "null buffer");
-  if ((rc = pack_key_alloc(ctx, base_log, level))) return rc;
-  HIPCHK(ctx, hipMemcpy(ctx->pk, h_in, 8 * fhe_pack_key_words(&ctx->p, base_log, level), hipMemcpyHostToDevice));
-  return pack_key_planes(ctx, base_log, level, nullptr);
+  return gadget_key_import(ctx, PACK_KEY, base_log, level, h_in);
 }
 
 // digits -> GEMM on the i8 matrix cores -> rotation, on the first `levels`
@@ -2272,34 +2340,18 @@ static int pack_impl(fhe_ctx* ctx, const uint64_t* d_ct, int64_t count, int32_t 
   if (ncb > 65535 || G * (p.N / PK_JC) > 65535) return fail(ctx, FHE_E_ARG, "pack batch too large: split the call");
   const size_t dbytes = (size_t)ncb * 16 * K, bbytes = 8 * (size_t)ncb * 16;
   const size_t need = dbytes + bbytes + 8 * (size_t)count * n1;
-  if (need > ctx->pack_ws_bytes) {
-    if (ctx->pack_ws) {
-      HIPCHK(ctx, hipDeviceSynchronize());
-      HIPCHK(ctx, hipFree(ctx->pack_ws));
-      ctx->pack_ws = nullptr;
-      ctx->pack_ws_bytes = 0;
-    }
-    HIPCHK(ctx, hipMalloc(&ctx->pack_ws, need));
-    ctx->pack_ws_bytes = need;
-  }
-  uint32_t* Dg = (uint32_t*)ctx->pack_ws;
-  u64* body = (u64*)((char*)ctx->pack_ws + dbytes);
-  u64* M = (u64*)((char*)ctx->pack_ws + dbytes + bbytes);
-  // K split as the key switch's: ~2 workgroups per CU when the (ciphertext
-  // block, column block) grid alone would leave CUs idle
-  const int64_t ctb = (count + KSM_CTS - 1) / KSM_CTS, ktiles = ctb * NB;
-  int S = (int)std::max<int64_t>(1, std::min<int64_t>(KB / KSM_RING, 512 / ktiles));
-  const int kslice = (KB / KSM_RING + S - 1) / S * KSM_RING;
-  S = (KB + kslice - 1) / kslice;
+  int rc = reserve(ctx, ctx->pack_ws, need, FHE_E_DEVICE, "hipMalloc of the pack workspace failed");
+  if (rc) return rc;
+  uint32_t* Dg = (uint32_t*)ctx->pack_ws.p;
+  u64* body = (u64*)((char*)ctx->pack_ws.p + dbytes);
+  u64* M = (u64*)((char*)ctx->pack_ws.p + dbytes + bbytes);
   hipEvent_t e1;
   prof_begin(ctx, ctx->prof_pack, st, &e1);
-  ctx->prof_pack.kernel = "k_keyswitch_mfma<8, 1>";
   HIPCHK(ctx, hipMemsetAsync(d_glwe, 0, 8 * (size_t)G * n1, st));
   // the digits kernel also zeroes the rows the split's atomics add into
   hipLaunchKernelGGL(k_pack_digits, dim3((unsigned)(big / 64), (unsigned)ncb), dim3(256), 0, st, d_ct, count, big,
-                     ctx->pk_beta, (int)levels, KB, Dg, body, S > 1 ? n1 : 0, M);
-  hipLaunchKernelGGL((k_keyswitch_mfma<8, 1>), dim3((unsigned)(ktiles * S)), dim3(256), 0, st, (const v4i*)Dg,
-                     (const v4i*)ctx->pk8, body, count, n1, NB, KB, 0, S, kslice, M);
+                     ctx->pack_key.beta, (int)levels, KB, Dg, body, gemm81_split(count, NB, KB).S > 1 ? n1 : 0, M);
+  if ((rc = gemm81(ctx, ctx->prof_pack, "pack", Dg, ctx->pack_key.planes, body, count, n1, NB, KB, M, st))) return rc;
   hipLaunchKernelGGL(k_pack_rotate, dim3((unsigned)(p.N / 256), (unsigned)(p.k + 1), (unsigned)(G * (p.N / PK_JC))),
                      dim3(256), 0, st, M, d_ct, count, p.N, p.k, d_glwe);
   prof_end(ctx, ctx->prof_pack, st, e1, count);
@@ -2313,10 +2365,10 @@ int fhe_pack_batch(fhe_ctx* ctx, const uint64_t* d_ct, int64_t count, int32_t le
   if (count < 0 || levels < 0 || levels > 8) return fail(ctx, FHE_E_ARG, "bad pack arguments (count < 0 or levels outside [0, 8])");
   int rc = need_pack_key(ctx);
   if (rc) return rc;
-  if (levels > ctx->pk_level) return fail(ctx, FHE_E_ARG, "pack levels exceed the packing key's");
+  if (levels > ctx->pack_key.level) return fail(ctx, FHE_E_ARG, "pack levels exceed the packing key's");
   if (count > 0 && (!d_ct || !d_glwe)) return fail(ctx, FHE_E_ARG, "null pack buffers");
   if (count == 0) return FHE_OK;
-  return pack_impl(ctx, d_ct, count, levels ? levels : ctx->pk_level, d_glwe, (hipStream_t)stream);
+  return pack_impl(ctx, d_ct, count, levels ? levels : ctx->pack_key.level, d_glwe, (hipStream_t)stream);
 }
 
 int fhe_decrypt_packed_batch(fhe_ctx* ctx, const uint64_t* d_glwe, int64_t count, int32_t mode, int64_t* d_out,
@@ -2339,12 +2391,6 @@ int fhe_decrypt_packed_batch(fhe_ctx* ctx, const uint64_t* d_glwe, int64_t count
 // ---- LWE -> LWE bridge key switch of a key rotation (k_bridge.h) --
 // The gadget bounds are the packing key's (int8 digits, tie coins); the noise
 // model is pack_var at count = 1 and the plan pack_plan's at count = 1.
-static int bridge_gadget_args(fhe_ctx* ctx, int32_t beta, int32_t L) {
-  if (!pack_gadget_ok(beta, L))
-    return fail(ctx, FHE_E_ARG, "bridge gadget out of range (1 <= base_log <= 7, 1 <= level <= 8, "
-                                "level * (base_log + 1) <= 62)");
-  return FHE_OK;
-}
 size_t fhe_bridge_key_words(const fhe_params* p, int32_t base_log, int32_t level) {
   if (!p || !pack_gadget_ok(base_log, level)) return 0;
   return (size_t)p->k * p->N * level * ((size_t)p->k * p->N + 1);
@@ -2352,51 +2398,11 @@ size_t fhe_bridge_key_words(const fhe_params* p, int32_t base_log, int32_t level
 int fhe_bridge_plan(const fhe_params* params, double in_var, int32_t* base_log, int32_t* level) {
   return fhe_pack_plan(params, 1, in_var, base_log, level, nullptr);
 }
-// bytes of the key's 8 byte planes: the column blocks padded to ceil((kN+1) / 16)
-static size_t bridge_plane_bytes(const fhe_params& p, int32_t L) {
-  const size_t big = (size_t)p.k * p.N, NB = (big + 1 + KSM_NB_COLS - 1) / KSM_NB_COLS;
-  return big * L * NB * KSM_NB_COLS * 8;
-}
-// (re)allocate the bridge key's buffers for gadget (beta, L)
-static int bridge_key_alloc(fhe_ctx* ctx, int32_t beta, int32_t L) {
-  const size_t words = fhe_bridge_key_words(&ctx->p, beta, L);
-  if (ctx->bk && fhe_bridge_key_words(&ctx->p, ctx->bk_beta, ctx->bk_level) != words) {
-    HIPCHK(ctx, hipDeviceSynchronize());
-    HIPCHK(ctx, hipFree(ctx->bk));
-    ctx->bk = nullptr;
-    HIPCHK(ctx, hipFree(ctx->bk8));
-    ctx->bk8 = nullptr;
-  }
-  ctx->bk_beta = ctx->bk_level = 0;
-  if (!ctx->bk) {
-    HIPCHK(ctx, hipMalloc(&ctx->bk, 8 * words));
-    if (hipMalloc(&ctx->bk8, bridge_plane_bytes(ctx->p, L)) != hipSuccess) {
-      (void)hipFree(ctx->bk);
-      ctx->bk = nullptr;
-      return fail(ctx, FHE_E_DEVICE, "hipMalloc of the bridge key's byte planes failed");
-    }
-  }
-  return FHE_OK;
-}
-// the key's 8 byte planes in B-fragment order: k_ksk_to_i8 on the layout
-// [i][l][kN+1] with no rounding (the padded columns of the last block are zero)
-static int bridge_key_planes(fhe_ctx* ctx, int32_t beta, int32_t L, hipStream_t st) {
-  const fhe_params& p = ctx->p;
-  const int big = p.k * p.N, K = big * L, n1 = big + 1, NB = (n1 + KSM_NB_COLS - 1) / KSM_NB_COLS;
-  const int64_t tot = (int64_t)K * NB * KSM_NB_COLS;
-  hipLaunchKernelGGL(k_ksk_to_i8, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, ctx->bk, K, big, (int)L, n1,
-                     NB, 0, 8, ctx->bk8);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  ctx->bk_beta = beta;
-  ctx->bk_level = L;
-  return FHE_OK;
-}
 
 int fhe_keygen_bridge_key_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level,
                               const uint32_t h_key[8], void* stream) {
   if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
-  int rc = bridge_gadget_args(ctx, base_log, level);  // argument errors first: a host-only context reports them too
+  int rc = gadget_args(ctx, BRIDGE_KEY, base_log, level);  // argument errors first: a host-only context reports them too
   if (rc) return rc;
   ChaKey K;
   if (!h_s_big_old || !key_arg(h_key, K)) return fail(ctx, FHE_E_ARG, "null bridge keygen arguments");
@@ -2405,7 +2411,7 @@ int fhe_keygen_bridge_key_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t
   for (int i = 0; i < big; ++i)
     if (h_s_big_old[i] > 1) return fail(ctx, FHE_E_ARG, "old big key word other than 0 or 1");
   if ((rc = need_secret(ctx))) return rc;
-  if ((rc = bridge_key_alloc(ctx, base_log, level))) return rc;
+  if ((rc = gadget_key_alloc(ctx, BRIDGE_KEY, level))) return rc;
   hipStream_t st = (hipStream_t)stream;
   // the old secret lives on the device for this launch only
   u64* d_old = nullptr;
@@ -2413,7 +2419,7 @@ int fhe_keygen_bridge_key_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t
   hipError_t e = hipMemcpyAsync(d_old, h_s_big_old, 8 * (size_t)big, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_keygen_bridge, dim3((unsigned)(big * level)), dim3(256), 0, st, K, big, (int)level,
-                       (int)base_log, p.glwe_noise_bits, ctx->s_big, d_old, ctx->bk);
+                       (int)base_log, p.glwe_noise_bits, ctx->s_big, d_old, ctx->bridge_key.key);
     e = hipGetLastError();
   }
   const hipError_t e2 = hipStreamSynchronize(st);
@@ -2423,7 +2429,7 @@ int fhe_keygen_bridge_key_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t
   HIPCHK(ctx, e2);
   HIPCHK(ctx, e3);
   HIPCHK(ctx, e4);
-  return bridge_key_planes(ctx, base_log, level, st);
+  return gadget_key_planes(ctx, BRIDGE_KEY, base_log, level, st);
 }
 int fhe_keygen_bridge_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level, uint64_t seed,
                           void* stream) {
@@ -2431,76 +2437,52 @@ int fhe_keygen_bridge_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t bas
   return fhe_keygen_bridge_key_key(ctx, h_s_big_old, base_log, level, K.w, stream);
 }
 
-static int need_bridge_key(fhe_ctx* ctx) {
-  int rc = need_device(ctx);
-  if (rc) return rc;
-  if (!ctx->bk_level)
-    return fail(ctx, FHE_E_STATE, "no bridge key: call fhe_keygen_bridge_key or fhe_import_bridge_key");
-  return FHE_OK;
-}
+static int need_bridge_key(fhe_ctx* ctx) { return need_gadget_key(ctx, BRIDGE_KEY); }
 
 int fhe_export_bridge_key(fhe_ctx* ctx, uint64_t* h_out) {
   if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
   if (!h_out) return fail(ctx, FHE_E_ARG, "null buffer");
   int rc = need_bridge_key(ctx);
   if (rc) return rc;
-  HIPCHK(ctx, hipDeviceSynchronize());
-  HIPCHK(ctx, hipMemcpy(h_out, ctx->bk, 8 * fhe_bridge_key_words(&ctx->p, ctx->bk_beta, ctx->bk_level),
-                        hipMemcpyDeviceToHost));
-  return FHE_OK;
+  return gadget_key_export(ctx, BRIDGE_KEY, h_out);
 }
 
 int fhe_import_bridge_key(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint64_t* h_in) {
   if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
-  int rc = bridge_gadget_args(ctx, base_log, level);  // argument errors first
+  int rc = gadget_args(ctx, BRIDGE_KEY, base_log, level);  // argument errors first
   if (rc) return rc;
   if (!h_in) return fail(ctx, FHE_E_ARG, "null buffer");
   if ((rc = need_device(ctx))) return rc;
-  if ((rc = bridge_key_alloc(ctx, base_log, level))) return rc;
-  HIPCHK(ctx, hipMemcpy(ctx->bk, h_in, 8 * fhe_bridge_key_words(&ctx->p, base_log, level), hipMemcpyHostToDevice));
-  return bridge_key_planes(ctx, base_log, level, nullptr);
+  return gadget_key_import(ctx, BRIDGE_KEY, base_log, level, h_in);
 }
 
 // digits -> GEMM on the i8 matrix cores -> copy back, for the Q * B_old rows
 // {q B + b : b < B_old} of d_in (Q x B big LWEs); row r of d_out takes the
 // bridged row r (d_out may be d_in: every digit is formed before the copy).
 // The GEMM is the key switch's kernel on 8 planes with kN + 1 columns, the
-// K split chosen as pack_impl does; it writes a compact count x (kN+1) buffer.
+// same K split as pack_impl's (gemm81); it writes a compact count x (kN+1) buffer.
 static int bridge_impl(fhe_ctx* ctx, const uint64_t* d_in, int64_t Q, int64_t B, int64_t B_old, uint64_t* d_out,
                        hipStream_t st) {
   const fhe_params& p = ctx->p;
-  const int levels = ctx->bk_level;
+  const int levels = ctx->bridge_key.level;
   const int big = p.k * p.N, K = big * levels, KB = K / 64, n1 = big + 1, NB = (n1 + KSM_NB_COLS - 1) / KSM_NB_COLS;
   const int64_t count = Q * B_old, ncb = (count + 15) / 16;
-  const int64_t ctb = (count + KSM_CTS - 1) / KSM_CTS, ktiles = ctb * NB;
   if (ncb > 65535 || count > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "bridge batch too large: split the call");
   const size_t dbytes = (size_t)ncb * 16 * K, bbytes = 8 * (size_t)ncb * 16;
   const size_t need = dbytes + bbytes + 8 * (size_t)count * n1;
-  if (need > ctx->bridge_ws_bytes) {
-    if (ctx->bridge_ws) {
-      HIPCHK(ctx, hipDeviceSynchronize());
-      HIPCHK(ctx, hipFree(ctx->bridge_ws));
-      ctx->bridge_ws = nullptr;
-      ctx->bridge_ws_bytes = 0;
-    }
-    HIPCHK(ctx, hipMalloc(&ctx->bridge_ws, need));
-    ctx->bridge_ws_bytes = need;
-  }
-  uint32_t* Dg = (uint32_t*)ctx->bridge_ws;
-  u64* body = (u64*)((char*)ctx->bridge_ws + dbytes);
-  u64* M = (u64*)((char*)ctx->bridge_ws + dbytes + bbytes);
-  int S = (int)std::max<int64_t>(1, std::min<int64_t>(KB / KSM_RING, 512 / ktiles));
-  const int kslice = (KB / KSM_RING + S - 1) / S * KSM_RING;
-  S = (KB + kslice - 1) / kslice;
-  if (ktiles * S > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "bridge batch too large: split the call");
+  int rc = reserve(ctx, ctx->bridge_ws, need, FHE_E_DEVICE, "hipMalloc of the bridge workspace failed");
+  if (rc) return rc;
+  uint32_t* Dg = (uint32_t*)ctx->bridge_ws.p;
+  u64* body = (u64*)((char*)ctx->bridge_ws.p + dbytes);
+  u64* M = (u64*)((char*)ctx->bridge_ws.p + dbytes + bbytes);
   hipEvent_t e1;
   prof_begin(ctx, ctx->prof_bridge, st, &e1);
-  ctx->prof_bridge.kernel = "k_keyswitch_mfma<8, 1>";
   // the digits kernel also zeroes the compact rows the split's atomics add into
   hipLaunchKernelGGL(k_bridge_digits, dim3((unsigned)(big / 64), (unsigned)ncb), dim3(256), 0, st, d_in, count, B,
-                     B_old, big, ctx->bk_beta, levels, KB, Dg, body, S > 1 ? n1 : 0, M);
-  hipLaunchKernelGGL((k_keyswitch_mfma<8, 1>), dim3((unsigned)(ktiles * S)), dim3(256), 0, st, (const v4i*)Dg,
-                     (const v4i*)ctx->bk8, body, count, n1, NB, KB, 0, S, kslice, M);
+                     B_old, big, ctx->bridge_key.beta, levels, KB, Dg, body,
+                     gemm81_split(count, NB, KB).S > 1 ? n1 : 0, M);
+  if ((rc = gemm81(ctx, ctx->prof_bridge, "bridge", Dg, ctx->bridge_key.planes, body, count, n1, NB, KB, M, st)))
+    return rc;
   hipLaunchKernelGGL(k_bridge_scatter, dim3((unsigned)count, (unsigned)((n1 + 255) / 256)), dim3(256), 0, st, M, count,
                      B, B_old, n1, d_out);
   prof_end(ctx, ctx->prof_bridge, st, e1, count);
@@ -2549,7 +2531,7 @@ static int leveled_ws(fhe_ctx* ctx, int64_t B, size_t extra, bool keep_copy, Que
   int rc = ensure_ws(ctx, 8 * (2 * (size_t)B * Wb + (size_t)B * Ws + (size_t)B + extra +
                                (keep_copy ? (size_t)B * Wb : 0)));
   if (rc) return rc;
-  w->ctv = (u64*)ctx->ws;
+  w->ctv = (u64*)ctx->ws.p;
   w->sgn = w->ctv + (size_t)B * Wb;
   w->small = w->sgn + (size_t)B * Wb;
   w->v = (int64_t*)(w->small + (size_t)B * Ws);
@@ -2600,9 +2582,9 @@ static int post_leveled_search(fhe_ctx* ctx, const QueryWs& w, int64_t B, int32_
   HIPCHK(ctx, hipMemcpyAsync(w.cpy, w.ctv, 8 * (size_t)B * Wb, hipMemcpyDeviceToDevice, st));
   int rc = sign_extract_batch(ctx, w.ctv, B, w.sgn, w.small, st);
   if (rc) return rc;
-  rc = pack_impl(ctx, w.cpy, B, ctx->pk_level, d_glwe_acc, st);
+  rc = pack_impl(ctx, w.cpy, B, ctx->pack_key.level, d_glwe_acc, st);
   if (rc) return rc;
-  return pack_impl(ctx, w.sgn, B, levels_bit ? levels_bit : ctx->pk_level, d_glwe_bit, st);
+  return pack_impl(ctx, w.sgn, B, levels_bit ? levels_bit : ctx->pack_key.level, d_glwe_bit, st);
 }
 
 int fhe_compare_query_batch(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0, const uint32_t h_mask_key[8],
@@ -2633,7 +2615,7 @@ int fhe_search_query_batch(fhe_ctx* ctx, const uint64_t* d_qbody, uint64_t id0, 
   if (levels_bit < 0 || levels_bit > 8) return fail(ctx, FHE_E_ARG, "bad search query arguments (levels_bit outside [0, 8])");
   if ((rc = need_eval_keys(ctx))) return rc;
   if ((rc = need_pack_key(ctx))) return rc;
-  if (levels_bit > ctx->pk_level) return fail(ctx, FHE_E_ARG, "search query levels_bit exceeds the packing key's levels");
+  if (levels_bit > ctx->pack_key.level) return fail(ctx, FHE_E_ARG, "search query levels_bit exceeds the packing key's levels");
   if (!h_mask_key || (B > 0 && (!d_qbody || !d_docs8 || !d_w || !d_glwe_acc || !d_glwe_bit)))
     return fail(ctx, FHE_E_ARG, "null search query arguments");
   if (B == 0) return FHE_OK;
@@ -2705,7 +2687,7 @@ int fhe_search_queries_batch(fhe_ctx* ctx, const uint64_t* d_qbody, const uint64
     return fail(ctx, FHE_E_ARG, "bad search queries arguments (levels_bit outside [0, 8])");
   if ((rc = need_eval_keys(ctx))) return rc;
   if ((rc = need_pack_key(ctx))) return rc;
-  if (levels_bit > ctx->pk_level)
+  if (levels_bit > ctx->pack_key.level)
     return fail(ctx, FHE_E_ARG, "search queries levels_bit exceeds the packing key's levels");
   if (!h_mask_key || !h_T || !d_qbody || !d_id0 || !d_docs8 || !d_w || !d_glwe_acc || !d_glwe_bit)
     return fail(ctx, FHE_E_ARG, "null search queries arguments");
@@ -2764,18 +2746,10 @@ int fhe_linear_seeded_queries_batch(fhe_ctx* ctx, const uint64_t* d_body, const 
     return fail(ctx, FHE_E_ARG, "null linear seeded queries arguments");
   if ((rc = need_device(ctx))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if ((size_t)Q > ctx->lsq_cst_words) {
-    if (ctx->lsq_cst) {
-      HIPCHK(ctx, hipDeviceSynchronize());
-      HIPCHK(ctx, hipFree(ctx->lsq_cst));
-      ctx->lsq_cst = nullptr;
-      ctx->lsq_cst_words = 0;
-    }
-    HIPCHK(ctx, hipMalloc(&ctx->lsq_cst, 8 * (size_t)Q));
-    ctx->lsq_cst_words = (size_t)Q;
-  }
-  if ((rc = store_scaled_csts(ctx, (u64*)ctx->lsq_cst, Q, h_cst, 0, nullptr, st))) return rc;
-  return linear_seeded_queries_launch(ctx, d_body, d_id0, B, D, h_mask_key, Q, d_W, (const u64*)ctx->lsq_cst, d_out,
+  if ((rc = reserve(ctx, ctx->lsq_cst, 8 * (size_t)Q, FHE_E_DEVICE, "hipMalloc of the scaled constants failed")))
+    return rc;
+  if ((rc = store_scaled_csts(ctx, (u64*)ctx->lsq_cst.p, Q, h_cst, 0, nullptr, st))) return rc;
+  return linear_seeded_queries_launch(ctx, d_body, d_id0, B, D, h_mask_key, Q, d_W, (const u64*)ctx->lsq_cst.p, d_out,
                                       st);
 }
 
@@ -2829,7 +2803,7 @@ int fhe_search_seeded_queries_bridged_batch(fhe_ctx* ctx, const uint64_t* d_body
   if ((rc = need_eval_keys(ctx))) return rc;
   if ((rc = need_pack_key(ctx))) return rc;
   if (B_old > 0 && (rc = need_bridge_key(ctx))) return rc;
-  if (levels_bit > ctx->pk_level)
+  if (levels_bit > ctx->pack_key.level)
     return fail(ctx, FHE_E_ARG, "search seeded queries levels_bit exceeds the packing key's levels");
   QueryWs w;
   int64_t* d_T;
@@ -2956,34 +2930,17 @@ static int linear_ggsw_impl(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t L, con
   if (n1 % 64 || KB % KSM_RING) return fail(ctx, FHE_E_ARG, "ggsw product needs (k+1)N a multiple of 256");
   const size_t pbytes = (size_t)K * n1 * 8, bbytes = 8 * (size_t)G;
   const size_t need = pbytes + bbytes + 8 * (size_t)G * n1;
-  if (need > ctx->xp_ws_bytes) {
-    if (ctx->xp_ws) {
-      HIPCHK(ctx, hipDeviceSynchronize());
-      HIPCHK(ctx, hipFree(ctx->xp_ws));
-      ctx->xp_ws = nullptr;
-      ctx->xp_ws_bytes = 0;
-    }
-    HIPCHK(ctx, hipMalloc(&ctx->xp_ws, need));
-    ctx->xp_ws_bytes = need;
-  }
-  v4i* P8 = (v4i*)ctx->xp_ws;
-  u64* body = (u64*)((char*)ctx->xp_ws + pbytes);
+  int rc = reserve(ctx, ctx->xp_ws, need, FHE_E_DEVICE, "hipMalloc of the ggsw product workspace failed");
+  if (rc) return rc;
+  v4i* P8 = (v4i*)ctx->xp_ws.p;
+  u64* body = (u64*)((char*)ctx->xp_ws.p + pbytes);
   u64* M = body + G;
-  // K split as the packing key switch's (partial sums by 64-bit atomics into
-  // the zeroed result; slices are whole ring rounds, so every slice holds at
-  // least KSM_RING k-blocks for the kernel's prologue)
-  const int64_t ctb = (G + KSM_CTS - 1) / KSM_CTS, ktiles = ctb * NB;
-  int Sk = (int)std::max<int64_t>(1, std::min<int64_t>(KB / KSM_RING, 512 / std::max<int64_t>(1, ktiles)));
-  const int kslice = (KB / KSM_RING + Sk - 1) / Sk * KSM_RING;
-  Sk = (KB + kslice - 1) / kslice;
-  if (ktiles * Sk > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "ggsw document batch too large: split the call");
   hipEvent_t e1;
   prof_begin(ctx, ctx->prof_xp, st, &e1);
-  ctx->prof_xp.kernel = "k_keyswitch_mfma<8, 1>";
+  // the GEMM's K split (gemm81) adds its partial sums into the zeroed result
   HIPCHK(ctx, hipMemsetAsync(body, 0, bbytes + 8 * (size_t)G * n1, st));
   hipLaunchKernelGGL(k_extprod_planes, dim3((unsigned)(KB * NB)), dim3(64), 0, st, d_ggsw, p.N, p.k, (int)L, NB, P8);
-  hipLaunchKernelGGL((k_keyswitch_mfma<8, 1>), dim3((unsigned)(ktiles * Sk)), dim3(256), 0, st, (const v4i*)d_docs8,
-                     (const v4i*)P8, body, G, n1, NB, KB, 0, Sk, kslice, M);
+  if ((rc = gemm81(ctx, ctx->prof_xp, "ggsw document", d_docs8, P8, body, G, n1, NB, KB, M, st))) return rc;
   hipLaunchKernelGGL(k_extprod_extract, dim3((unsigned)B, (unsigned)((p.k * p.N + 256) / 256)), dim3(256), 0, st, M,
                      S, (int)D, p.N, p.k, (u64)cst << (64 - p.msg_bits), d_out);
   prof_end(ctx, ctx->prof_xp, st, e1, B);
@@ -3024,7 +2981,7 @@ int fhe_search_ggsw_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_log
   if (levels_bit < 0 || levels_bit > 8) return fail(ctx, FHE_E_ARG, "bad search ggsw arguments (levels_bit outside [0, 8])");
   if ((rc = need_eval_keys(ctx))) return rc;
   if ((rc = need_pack_key(ctx))) return rc;
-  if (levels_bit > ctx->pk_level) return fail(ctx, FHE_E_ARG, "search ggsw levels_bit exceeds the packing key's levels");
+  if (levels_bit > ctx->pack_key.level) return fail(ctx, FHE_E_ARG, "search ggsw levels_bit exceeds the packing key's levels");
   if (B > 0 && (!d_ggsw || !d_docs8 || !d_glwe_acc || !d_glwe_bit))
     return fail(ctx, FHE_E_ARG, "null search ggsw arguments");
   if (B == 0) return FHE_OK;
@@ -3101,22 +3058,13 @@ static int linear_ggsws_impl(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t L, co
   if (G > 65535 || rgrid > 65535 || cgrid > 0x7fffffffLL)
     return fail(ctx, FHE_E_ARG, "ggsw queries batch too large: split the call");
   const size_t need = fhe_ggsws_ws_bytes(&p, Q, B, D, L);
-  if (need > ctx->xp_ws_bytes) {
-    if (ctx->xp_ws) {
-      HIPCHK(ctx, hipDeviceSynchronize());
-      HIPCHK(ctx, hipFree(ctx->xp_ws));
-      ctx->xp_ws = nullptr;
-      ctx->xp_ws_bytes = 0;
-    }
-    HIPCHK(ctx, hipMalloc(&ctx->xp_ws, need));
-    ctx->xp_ws_bytes = need;
-  }
-  const size_t pbytes = (size_t)rtp * 16 * n1 * L * 8, mbytes = 8 * (size_t)Q * G * n1;
-  v4i* P8 = (v4i*)ctx->xp_ws;
-  u64* M = (u64*)((char*)ctx->xp_ws + pbytes);
-  u64* d_cst = M + (size_t)Q * G * n1;
-  int rc = store_scaled_csts(ctx, d_cst, Q, h_cst, cst, h_T, st);
+  int rc = reserve(ctx, ctx->xp_ws, need, FHE_E_DEVICE, "hipMalloc of the ggsw product workspace failed");
   if (rc) return rc;
+  const size_t pbytes = (size_t)rtp * 16 * n1 * L * 8, mbytes = 8 * (size_t)Q * G * n1;
+  v4i* P8 = (v4i*)ctx->xp_ws.p;
+  u64* M = (u64*)((char*)ctx->xp_ws.p + pbytes);
+  u64* d_cst = M + (size_t)Q * G * n1;
+  if ((rc = store_scaled_csts(ctx, d_cst, Q, h_cst, cst, h_T, st))) return rc;
   // K split over workgroups towards ~XQ_WGS of them, slices of 4 k-blocks at least
 #ifndef FHEICP_XQ_WGS
 #define FHEICP_XQ_WGS 512  // A/B builds (tools/build_variant.sh): other targets
@@ -3193,7 +3141,7 @@ int fhe_search_ggsws_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_lo
     return fail(ctx, FHE_E_ARG, "null search ggsw queries arguments");
   if ((rc = need_eval_keys(ctx))) return rc;
   if ((rc = need_pack_key(ctx))) return rc;
-  if (levels_bit > ctx->pk_level)
+  if (levels_bit > ctx->pack_key.level)
     return fail(ctx, FHE_E_ARG, "search ggsw queries levels_bit exceeds the packing key's levels");
   QueryWs w;
   int64_t* d_T;
@@ -3216,7 +3164,7 @@ int fhe_threshold_batch(fhe_ctx* ctx, const uint64_t* d_ct_acc, int64_t count, i
   // workspace: v = acc - T (B big, consumed by the extraction) | small (B)
   rc = ensure_ws(ctx, 8 * ((size_t)count * Wb + (size_t)count * Ws));
   if (rc) return rc;
-  u64* ctv = (u64*)ctx->ws;
+  u64* ctv = (u64*)ctx->ws.p;
   u64* small = ctv + (size_t)count * Wb;
   const int64_t words = count * (int64_t)Wb;
   hipLaunchKernelGGL(k_lwe_affine, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, d_ct_acc, count, (int)Wb,
@@ -3459,10 +3407,8 @@ struct fhe_group {
   int device = -1;
   const c64** d_keys = nullptr;     // [NGAD + 1][T]: tenant t's bsk_fft of gadget g, then its ksk8 planes
   std::vector<const c64*> h_keys;   // what d_keys holds
-  void* ws = nullptr;               // tables | small | (search: ct_v | sign | copy | expanded queries / constants)
-  size_t ws_bytes = 0;
-  void* ks_ws = nullptr;            // the group key switch's digit groups | bodies (M words)
-  size_t ks_ws_bytes = 0;
+  DevBuf ws;                        // tables | small | (search: ct_v | sign | copy | expanded queries / constants)
+  DevBuf ks_ws;                     // the group key switch's digit groups | bodies (M words)
   int ks_tiles = 512;               // the key switch's K-split target: two workgroups per CU of the device
 };
 
@@ -3526,21 +3472,7 @@ static int grp_sync_keys(fhe_group* g) {
   return FHE_OK;
 }
 static int grp_ensure_ws(fhe_group* g, size_t bytes) {
-  if (bytes <= g->ws_bytes) return FHE_OK;
-  fhe_ctx* c0 = g->ctxs[0];
-  if (g->ws) {
-    HIPCHK(c0, hipDeviceSynchronize());
-    HIPCHK(c0, hipFree(g->ws));
-    g->ws = nullptr;
-    g->ws_bytes = 0;
-  }
-  if (hipMalloc(&g->ws, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    g->ws = nullptr;
-    return gfail(FHE_E_NOMEM, "workspace: out of device memory (fewer rows per call)");
-  }
-  g->ws_bytes = bytes;
-  return FHE_OK;
+  return reserve(nullptr, g->ws, bytes, FHE_E_NOMEM, "group: workspace: out of device memory (fewer rows per call)");
 }
 
 int64_t fhe_group_rows(const int64_t* counts, int32_t T, int64_t* starts) {
@@ -3590,11 +3522,11 @@ int fhe_group_create(fhe_ctx* const* ctxs, int32_t T, fhe_group** out) {
 
 void fhe_group_destroy(fhe_group* g) {
   if (!g) return;
-  if (g->device >= 0 && (g->d_keys || g->ws || g->ks_ws)) {
+  if (g->device >= 0 && (g->d_keys || g->ws.p || g->ks_ws.p)) {
     (void)hipSetDevice(g->device);
     (void)hipFree((void*)g->d_keys);
-    (void)hipFree(g->ws);
-    (void)hipFree(g->ks_ws);
+    (void)hipFree(g->ws.p);
+    (void)hipFree(g->ks_ws.p);
   }
   delete g;
 }
@@ -3677,61 +3609,49 @@ static size_t grp_table_bytes(size_t T, int64_t M) {
 // tenant's key planes; keyswitch_lane's split rule on the launch's total of
 // blocks x column groups. Timing goes to tenant 0's key-switch bucket.
 static int grp_ks_fits(const fhe_group* g, const int64_t* counts);
+// the tenants' ciphertext blocks (128 rows) and digit groups (16 rows) together
+struct GrpKsCount {
+  int64_t nblk = 0, ndg = 0;
+};
+static GrpKsCount grp_ks_count(const fhe_group* g, const int64_t* counts) {
+  GrpKsCount c;
+  for (size_t t = 0; t < g->ctxs.size(); ++t) {
+    c.nblk += (counts[t] + KSM_CTS - 1) / KSM_CTS;
+    c.ndg += (counts[t] + 15) / 16;
+  }
+  return c;
+}
 static int grp_keyswitch(fhe_group* g, const u64* d_big, const int64_t* counts, const KsGrpBlock* blk, int64_t M,
                          int32_t shift, uint64_t add_body, u64* d_small, hipStream_t st) {
   fhe_ctx* c0 = g->ctxs[0];
   const fhe_params& p = c0->p;
   const size_t T = g->ctxs.size();
-  int64_t nblk = 0, ndg = 0;
-  for (size_t t = 0; t < T; ++t) {
-    nblk += (counts[t] + KSM_CTS - 1) / KSM_CTS;
-    ndg += (counts[t] + 15) / 16;
-  }
+  const auto [nblk, ndg] = grp_ks_count(g, counts);
   if (nblk == 0) return FHE_OK;
   // the digit launch's grid y is 8 per block
   if (ndg > 65535 || 8 * nblk > 65535) return grp_ks_fits(g, counts);  // the entries checked it already
   const int K = p.k * p.N * p.ks_level, KB = K / 64, n1 = p.n + 1, NB = ks_nb(p), CB = ks_cb(p), R = ks_round_bits(p);
   const size_t dbytes = (size_t)ndg * 16 * K, need = dbytes + 8 * (size_t)M;
-  if (need > g->ks_ws_bytes) {
-    if (g->ks_ws) {
-      HIPCHK(c0, hipDeviceSynchronize());
-      HIPCHK(c0, hipFree(g->ks_ws));
-      g->ks_ws = nullptr;
-      g->ks_ws_bytes = 0;
-    }
-    if (hipMalloc(&g->ks_ws, need) != hipSuccess) {
-      (void)hipGetLastError();
-      g->ks_ws = nullptr;
-      return gfail(FHE_E_NOMEM, "key-switch workspace: out of device memory (fewer rows per call)");
-    }
-    g->ks_ws_bytes = need;
-  }
-  uint32_t* D = (uint32_t*)g->ks_ws;
-  u64* body = (u64*)((char*)g->ks_ws + dbytes);
+  int rc = reserve(nullptr, g->ks_ws, need, FHE_E_NOMEM,
+                   "group: key-switch workspace: out of device memory (fewer rows per call)");
+  if (rc) return rc;
+  uint32_t* D = (uint32_t*)g->ks_ws.p;
+  u64* body = (u64*)((char*)g->ks_ws.p + dbytes);
   const int64_t ktiles = nblk * (NB / CB);
-  int S = (int)std::max<int64_t>(1, std::min<int64_t>(KB / KSM_RING, g->ks_tiles / ktiles));
-  const int kslice = (KB / KSM_RING + S - 1) / S * KSM_RING;
-  S = (KB + kslice - 1) / kslice;
+  const auto [S, kslice] = ksm_split(KB, ktiles, g->ks_tiles);
   const v4i* const* keys = (const v4i* const*)(g->d_keys + (size_t)NGAD * T);
   hipEvent_t e1;
   prof_begin(c0, c0->prof_ks, st, &e1);
   hipLaunchKernelGGL(k_ks_digits_grp, dim3((unsigned)(p.k * p.N / 64), (unsigned)(8 * nblk)), dim3(256), 0, st, d_big,
                      blk, p.k * p.N, p.ks_base_log, p.ks_level, shift, add_body, KB, D, body, S > 1 ? n1 : 0, d_small);
   const dim3 gks((unsigned)(ktiles * S));
-#define KSMG(Q, C)                                                                                                   \
-  c0->prof_ks.kernel = "k_keyswitch_mfma_grp<" #Q ", " #C ">";                                                      \
-  hipLaunchKernelGGL((k_keyswitch_mfma_grp<Q, C>), gks, dim3(256), 0, st, (const v4i*)D, keys, blk, body, n1, NB, KB, \
-                     R, S, kslice, d_small)
-  switch ((8 - R / 8) * 4 + CB) {
-    case 3 * 4 + 3: KSMG(3, 3); break;
-    case 4 * 4 + 3: KSMG(4, 3); break;
-    case 5 * 4 + 1: KSMG(5, 1); break;
-    case 6 * 4 + 1: KSMG(6, 1); break;
-    case 7 * 4 + 1: KSMG(7, 1); break;
-    case 8 * 4 + 1: KSMG(8, 1); break;
-    default: return gfail(FHE_E_ARG, "key-switch byte planes out of range");
-  }
-#undef KSMG
+  const bool known = ksm_dispatch(8 - R / 8, CB, [&, S = S, kslice = kslice](auto q, auto c) {
+    static const std::string name = ksm_name("k_keyswitch_mfma_grp", q, c);  // one per instantiation
+    c0->prof_ks.kernel = name.c_str();
+    hipLaunchKernelGGL((k_keyswitch_mfma_grp<q, c>), gks, dim3(256), 0, st, (const v4i*)D, keys, blk, body, n1, NB,
+                       KB, R, S, kslice, d_small);
+  });
+  if (!known) return gfail(FHE_E_ARG, "key-switch byte planes out of range");
   int64_t total = 0;
   for (size_t t = 0; t < T; ++t) total += counts[t];
   prof_end(c0, c0->prof_ks, st, e1, total);
@@ -3750,11 +3670,7 @@ static bool grp_ks_grouped(const fhe_group* g) {
 // before any work is queued. The per-tenant loop has keyswitch_lane's own.
 static int grp_ks_fits(const fhe_group* g, const int64_t* counts) {
   if (!grp_ks_grouped(g)) return FHE_OK;
-  int64_t nblk = 0, ndg = 0;
-  for (size_t t = 0; t < g->ctxs.size(); ++t) {
-    nblk += (counts[t] + KSM_CTS - 1) / KSM_CTS;
-    ndg += (counts[t] + 15) / 16;
-  }
+  const auto [nblk, ndg] = grp_ks_count(g, counts);
   if (ndg > 65535 || 8 * nblk > 65535)
     return gfail(FHE_E_ARG, "keyswitch batch too large (more than 65535 digit groups of 16 rows, or 8191 blocks of "
                             "128 rows, over all tenants): split the call");
@@ -3767,11 +3683,10 @@ static int grp_ks_tables(fhe_group* g, const int64_t* counts, const int64_t* sta
   fhe_ctx* c0 = g->ctxs[0];
   const size_t T = g->ctxs.size();
   std::vector<u64> se(2 * T);
-  int64_t nblk = 0;
+  const int64_t nblk = grp_ks_count(g, counts).nblk;
   for (size_t t = 0; t < T; ++t) {
     se[t] = (u64)starts[t];
     se[T + t] = (u64)(starts[t] + counts[t]);
-    nblk += (counts[t] + KSM_CTS - 1) / KSM_CTS;
   }
   u64* d_se = (u64*)tables;
   *blk = (KsGrpBlock*)((char*)tables + 16 * T + sizeof(BrGrpTenant) * NGAD * T + grp_wgt_bytes(M));
@@ -3845,7 +3760,7 @@ int fhe_sign_group_batch(fhe_group* g, uint64_t* d_ct_v, const int64_t* h_counts
   if ((rc = grp_ks_fits(g, h_counts))) return rc;
   const size_t tb = grp_table_bytes((size_t)T, M);
   if ((rc = grp_ensure_ws(g, tb + 8 * (size_t)M * fhe_small_lwe_words(&g->ctxs[0]->p)))) return rc;
-  return grp_sign(g, d_ct_v, h_counts, starts.data(), M, d_sign, (u64*)((char*)g->ws + tb), g->ws, (hipStream_t)stream);
+  return grp_sign(g, d_ct_v, h_counts, starts.data(), M, d_sign, (u64*)((char*)g->ws.p + tb), g->ws.p, (hipStream_t)stream);
 }
 
 int fhe_keyswitch_group_batch(fhe_group* g, const uint64_t* d_big, const int64_t* h_counts, int32_t shift,
@@ -3879,7 +3794,7 @@ int fhe_keyswitch_group_batch(fhe_group* g, const uint64_t* d_big, const int64_t
   }
   if ((rc = grp_ensure_ws(g, grp_table_bytes((size_t)T, M)))) return rc;
   KsGrpBlock* blk;
-  if ((rc = grp_ks_tables(g, h_counts, starts.data(), M, g->ws, st, &blk))) return rc;
+  if ((rc = grp_ks_tables(g, h_counts, starts.data(), M, g->ws.p, st, &blk))) return rc;
   return grp_keyswitch(g, d_big, h_counts, blk, M, shift, add_body, d_small, st);
 }
 
@@ -3909,7 +3824,7 @@ int fhe_search_query_group_batch(fhe_group* g, const fhe_group_query* items, int
     const fhe_group_query& q = items[t];
     if (!q.Q) continue;
     if ((rc = need_pack_key(g->ctxs[t]))) return rc;
-    if (q.levels_bit > g->ctxs[t]->pk_level)
+    if (q.levels_bit > g->ctxs[t]->pack_key.level)
       return gfail(FHE_E_ARG, "tenant " + std::to_string(t) + ": levels_bit exceeds the packing key's levels");
     if (!q.h_mask_key || !q.h_T || !q.d_qbody || !q.d_id0 || !q.d_docs8 || !q.d_w || !q.d_glwe_acc || !q.d_glwe_bit)
       return gfail(FHE_E_ARG, "tenant " + std::to_string(t) + ": null search arguments");
@@ -3923,7 +3838,7 @@ int fhe_search_query_group_batch(fhe_group* g, const fhe_group_query* items, int
   size_t qmax = 0;  // the largest tenant's expanded queries (one at a time, in stream order)
   for (int32_t t = 0; t < T; ++t) qmax = std::max(qmax, (size_t)items[t].Q * (size_t)items[t].D * Wb);
   if ((rc = grp_ensure_ws(g, tb + 8 * ((size_t)M * (3 * Wb + Ws) + qmax)))) return rc;
-  u64* small = (u64*)((char*)g->ws + tb);
+  u64* small = (u64*)((char*)g->ws.p + tb);
   u64* ctv = small + (size_t)M * Ws;
   u64* sgn = ctv + (size_t)M * Wb;
   u64* cpy = sgn + (size_t)M * Wb;
@@ -3941,15 +3856,15 @@ int fhe_search_query_group_batch(fhe_group* g, const fhe_group_query* items, int
     if ((rc = fhe_linear_queries_batch(ctx, ctq, q.Q, q.d_docs8, q.B, q.D, q.d_w, cs.data(), seg, stream))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(cpy + (size_t)starts[t] * Wb, seg, 8 * (size_t)counts[t] * Wb, hipMemcpyDeviceToDevice, st));
   }
-  if ((rc = grp_sign(g, ctv, counts.data(), starts.data(), M, sgn, small, g->ws, st))) return rc;
+  if ((rc = grp_sign(g, ctv, counts.data(), starts.data(), M, sgn, small, g->ws.p, st))) return rc;
   // tenant t's two packings with its own key: result q B + b in coefficient
   // (q B + b) mod N of its GLWE (q B + b) / N, as fhe_search_queries_batch
   for (int32_t t = 0; t < T; ++t) {
     const fhe_group_query& q = items[t];
     if (!q.Q) continue;
     fhe_ctx* ctx = g->ctxs[t];
-    if ((rc = pack_impl(ctx, cpy + (size_t)starts[t] * Wb, counts[t], ctx->pk_level, q.d_glwe_acc, st))) return rc;
-    if ((rc = pack_impl(ctx, sgn + (size_t)starts[t] * Wb, counts[t], q.levels_bit ? q.levels_bit : ctx->pk_level,
+    if ((rc = pack_impl(ctx, cpy + (size_t)starts[t] * Wb, counts[t], ctx->pack_key.level, q.d_glwe_acc, st))) return rc;
+    if ((rc = pack_impl(ctx, sgn + (size_t)starts[t] * Wb, counts[t], q.levels_bit ? q.levels_bit : ctx->pack_key.level,
                         q.d_glwe_bit, st)))
       return rc;
   }
@@ -3990,7 +3905,7 @@ int fhe_search_seeded_queries_group_batch(fhe_group* g, const fhe_group_corpus* 
     const std::string who = "tenant " + std::to_string(t) + ": ";
     if ((rc = need_pack_key(g->ctxs[t]))) return gfail(rc, who + fhe_last_error(g->ctxs[t]));
     if (c.B_old > 0 && (rc = need_bridge_key(g->ctxs[t]))) return gfail(rc, who + fhe_last_error(g->ctxs[t]));
-    if (c.levels_bit > g->ctxs[t]->pk_level)
+    if (c.levels_bit > g->ctxs[t]->pack_key.level)
       return gfail(FHE_E_ARG, who + "levels_bit exceeds the packing key's levels");
   }
   const int64_t M = fhe_group_rows(counts.data(), T, starts.data());
@@ -4000,7 +3915,7 @@ int fhe_search_seeded_queries_group_batch(fhe_group* g, const fhe_group_corpus* 
   const fhe_params& p = g->ctxs[0]->p;
   const size_t Wb = fhe_big_lwe_words(&p), Ws = fhe_small_lwe_words(&p), tb = grp_table_bytes((size_t)T, M);
   if ((rc = grp_ensure_ws(g, tb + 8 * ((size_t)M * (3 * Wb + Ws) + (size_t)qmax)))) return rc;
-  u64* small = (u64*)((char*)g->ws + tb);
+  u64* small = (u64*)((char*)g->ws.p + tb);
   u64* ctv = small + (size_t)M * Ws;
   u64* sgn = ctv + (size_t)M * Wb;
   u64* cpy = sgn + (size_t)M * Wb;
@@ -4018,14 +3933,14 @@ int fhe_search_seeded_queries_group_batch(fhe_group* g, const fhe_group_corpus* 
     if (c.B_old > 0 && (rc = bridge_impl(ctx, seg, c.Q, c.B, c.B_old, seg, st))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(cpy + (size_t)starts[t] * Wb, seg, 8 * (size_t)counts[t] * Wb, hipMemcpyDeviceToDevice, st));
   }
-  if ((rc = grp_sign(g, ctv, counts.data(), starts.data(), M, sgn, small, g->ws, st))) return rc;
+  if ((rc = grp_sign(g, ctv, counts.data(), starts.data(), M, sgn, small, g->ws.p, st))) return rc;
   // tenant t's two packings with its own key, as fhe_search_seeded_queries_bridged_batch
   for (int32_t t = 0; t < T; ++t) {
     const fhe_group_corpus& c = items[t];
     if (!c.Q) continue;
     fhe_ctx* ctx = g->ctxs[t];
-    if ((rc = pack_impl(ctx, cpy + (size_t)starts[t] * Wb, counts[t], ctx->pk_level, c.d_glwe_acc, st))) return rc;
-    if ((rc = pack_impl(ctx, sgn + (size_t)starts[t] * Wb, counts[t], c.levels_bit ? c.levels_bit : ctx->pk_level,
+    if ((rc = pack_impl(ctx, cpy + (size_t)starts[t] * Wb, counts[t], ctx->pack_key.level, c.d_glwe_acc, st))) return rc;
+    if ((rc = pack_impl(ctx, sgn + (size_t)starts[t] * Wb, counts[t], c.levels_bit ? c.levels_bit : ctx->pack_key.level,
                         c.d_glwe_bit, st)))
       return rc;
   }
