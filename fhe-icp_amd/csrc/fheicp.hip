@@ -46,6 +46,7 @@
 #include "k_extprod.h"
 #include "k_extprod_q.h"
 #include "k_blind_rotate.h"
+#include "k_extprod_grp.h"
 
 // ============================================================ host =========
 struct ProfAcc {
@@ -3942,6 +3943,201 @@ int fhe_search_seeded_queries_group_batch(fhe_group* g, const fhe_group_corpus* 
     if ((rc = pack_impl(ctx, cpy + (size_t)starts[t] * Wb, counts[t], ctx->pack_key.level, c.d_glwe_acc, st))) return rc;
     if ((rc = pack_impl(ctx, sgn + (size_t)starts[t] * Wb, counts[t], c.levels_bit ? c.levels_bit : ctx->pack_key.level,
                         c.d_glwe_bit, st)))
+      return rc;
+  }
+  return FHE_OK;
+}
+
+// ---- both-private search for a group ---------------------
+// What one call's leveled step launches, from the participating tenants'
+// shapes: the records, the launch's RT, tile, row-tile and row counts, the K
+// split and the layout of its part of the group workspace (tables | constants
+// | planes | results, each 16-aligned).
+struct XqGrpPlan {
+  int nt = 0, RT = 1, L = 0, KB = 0, Sk = 1, kslice = 0;
+  int64_t ntiles = 0, nrt = 0, M = 0, nq = 0, mwords = 0, total = 0;
+  XqGrpTenants rec;
+  int32_t tenant[XQ_GRP_MAX];  // record -> tenant of the group
+  std::vector<int64_t> counts, starts;
+  size_t off_tiles = 0, off_rt = 0, off_quad = 0, off_cst = 0, off_planes = 0, off_M = 0, bytes = 0;
+};
+static size_t up16(size_t x) { return (x + 15) / 16 * 16; }
+// The argument checks of both entries (FHE_E_ARG, "tenant t: ...", host-only
+// contexts report them too) and the plan. `search`: the thresholds, levels_bit
+// and the two outputs are arguments too.
+static int xq_grp_plan(fhe_group* g, const fhe_group_ggsw* items, int32_t T, const int64_t* const* h_cst, bool search,
+                       XqGrpPlan* pl) {
+  pl->counts.assign((size_t)T, 0);
+  pl->starts.assign((size_t)T, 0);
+  for (int32_t t = 0; t < T; ++t) {
+    const fhe_group_ggsw& it = items[t];
+    fhe_ctx* ctx = g->ctxs[t];
+    const std::string who = "tenant " + std::to_string(t) + ": ";
+    if (it.struct_size != (int32_t)sizeof(fhe_group_ggsw))
+      return gfail(FHE_E_ARG, who + "fhe_group_ggsw.struct_size is not this library's");
+    if (it.Q < 0) return gfail(FHE_E_ARG, who + "Q < 0");
+    if (it.Q == 0) continue;  // sits this call out
+    if (it.reserved != 0) return gfail(FHE_E_ARG, who + "fhe_group_ggsw.reserved is not 0");
+    if (ggsws_args(ctx, it.Q, it.B, it.D, it.base_log, it.level)) return gfail(FHE_E_ARG, who + fhe_last_error(ctx));
+    if (!it.d_ggsw || !it.d_docs) return gfail(FHE_E_ARG, who + "null ggsw queries or documents");
+    if (search) {
+      if (!it.h_T || !it.d_glwe_acc || !it.d_glwe_bit) return gfail(FHE_E_ARG, who + "null search arguments");
+      if (it.levels_bit < 0 || it.levels_bit > 8) return gfail(FHE_E_ARG, who + "levels_bit outside [0, 8]");
+    } else if (!h_cst[t]) {
+      return gfail(FHE_E_ARG, who + "null constants");
+    }
+    if (pl->nt && it.level != pl->L)
+      return gfail(FHE_E_ARG, who + "gadget level " + std::to_string(it.level) + " differs from the first participating "
+                                  "tenant's " + std::to_string(pl->L) + ": one level per call");
+    pl->L = it.level;
+    pl->counts[t] = it.Q * it.B;
+    pl->total += pl->counts[t];
+    if (pl->total >= ((int64_t)1 << 31)) return gfail(FHE_E_ARG, "2^31 results and more: split the call");
+    pl->tenant[pl->nt++] = t;
+  }
+  pl->M = fhe_group_rows(pl->counts.data(), T, pl->starts.data());
+  if (!pl->nt) return FHE_OK;
+  const fhe_params& p = g->ctxs[0]->p;  // the contexts' parameters are equal (grp_check_params, before any launch)
+  const int n1 = (p.k + 1) * p.N;
+  pl->KB = n1 * pl->L / 64;
+  for (int i = 0; i < pl->nt; ++i)
+    if (items[pl->tenant[i]].Q * (p.k + 1) > 16) pl->RT = 2;
+  for (int i = 0; i < pl->nt; ++i) {
+    const int32_t t = pl->tenant[i];
+    const fhe_group_ggsw& it = items[t];
+    XqGrpTenant& r = pl->rec.v[i];
+    const int64_t G = ggsw_glwes(p, it.B, it.D), rtp = xq_grp_rtiles(p.k, (int)it.Q, pl->RT);
+    r = {it.d_ggsw, (const uint8_t*)it.d_docs, pl->starts[t], pl->mwords, (int32_t)it.Q, (int32_t)G, (int32_t)it.B,
+         it.D, (int32_t)pl->nrt, (int32_t)pl->nq};
+    pl->ntiles += xq_grp_cgrid(p.N, (int)G) * (rtp / pl->RT);
+    pl->nrt += rtp;
+    pl->nq += it.Q;
+    pl->mwords += it.Q * G * n1;
+  }
+  // the tiles are the GEMM's grid x, (row tile, k-block) the planes'
+  if (pl->ntiles > 0x7fffffffLL || pl->nrt * pl->KB > 0x7fffffffLL)
+    return gfail(FHE_E_ARG, "ggsw queries batch too large (2^31 tiles over all tenants): split the call");
+  // linear_ggsws_impl's K split on the launch's total of tiles
+  pl->Sk = (int)std::max<int64_t>(1, std::min<int64_t>(pl->KB / 4, FHEICP_XQ_WGS / std::max<int64_t>(1, pl->ntiles)));
+  pl->kslice = (pl->KB + pl->Sk - 1) / pl->Sk;
+  pl->Sk = (pl->KB + pl->kslice - 1) / pl->kslice;
+  pl->off_tiles = up16(sizeof(XqGrpTenant) * (size_t)pl->nt);
+  pl->off_rt = pl->off_tiles + sizeof(XqGrpTile) * (size_t)pl->ntiles;
+  pl->off_quad = pl->off_rt + up16(4 * (size_t)pl->nrt);
+  pl->off_cst = pl->off_quad + up16((size_t)pl->M);  // 4 bytes per row quad
+  pl->off_planes = pl->off_cst + up16(8 * (size_t)pl->nq);
+  pl->off_M = pl->off_planes + (size_t)pl->nrt * 16 * n1 * pl->L * 8;
+  pl->bytes = pl->off_M + 8 * (size_t)pl->mwords;
+  return FHE_OK;
+}
+// The leveled step of every participating tenant at `ws` (pl->bytes of the
+// group workspace): the constants, then in one bracket the tables, the memset
+// of a split K, the planes, the GEMM and the extraction into the padded rows of
+// d_out (and d_cpy, when given). The launch count does not depend on T.
+// Timing goes to tenant 0's "linear_ggsws" bucket.
+static int xq_grp_launch(fhe_group* g, const XqGrpPlan& pl, const std::vector<u64>& cs, void* ws, u64* d_out,
+                         u64* d_cpy, hipStream_t st) {
+  fhe_ctx* c0 = g->ctxs[0];
+  const fhe_params& p = c0->p;
+  XqGrpTenant* ten = (XqGrpTenant*)ws;
+  XqGrpTile* tiles = (XqGrpTile*)((char*)ws + pl.off_tiles);
+  int32_t* rtt = (int32_t*)((char*)ws + pl.off_rt);
+  int32_t* qdt = (int32_t*)((char*)ws + pl.off_quad);
+  u64* d_cst = (u64*)((char*)ws + pl.off_cst);
+  v4i* P8 = (v4i*)((char*)ws + pl.off_planes);
+  u64* Mall = (u64*)((char*)ws + pl.off_M);
+  int rc = store_words(c0, d_cst, cs.data(), pl.nq, st);
+  if (rc) return rc;
+  hipEvent_t e1;
+  prof_begin(c0, c0->prof_xq, st, &e1);
+  c0->prof_xq.kernel = pl.RT == 2 ? "k_extprod_queries_mfma_grp<2>" : "k_extprod_queries_mfma_grp<1>";
+  const int64_t nquads = pl.M / 4, nth = std::max(std::max(pl.ntiles, pl.nrt), std::max<int64_t>(nquads, pl.nt));
+  hipLaunchKernelGGL(k_xq_grp_tables, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, st, pl.rec, pl.nt, p.N, p.k,
+                     pl.RT, pl.ntiles, pl.nrt, nquads, ten, tiles, rtt, qdt);
+  if (pl.Sk > 1) HIPCHK(c0, hipMemsetAsync(Mall, 0, 8 * (size_t)pl.mwords, st));
+  hipLaunchKernelGGL(k_ggsws_planes_grp, dim3((unsigned)(pl.nrt * pl.KB)), dim3(64), 0, st,
+                     (const XqGrpTenant*)ten, (const int32_t*)rtt, p.N, p.k, pl.L, pl.KB, P8);
+  const dim3 grid((unsigned)pl.ntiles, 1, (unsigned)pl.Sk);
+  if (pl.RT == 2)
+    hipLaunchKernelGGL(k_extprod_queries_mfma_grp<2>, grid, dim3(256), 0, st, (const XqGrpTile*)tiles,
+                       (const XqGrpTenant*)ten, (const v4i*)P8, p.N, p.k, pl.L, pl.KB, pl.kslice, Mall);
+  else
+    hipLaunchKernelGGL(k_extprod_queries_mfma_grp<1>, grid, dim3(256), 0, st, (const XqGrpTile*)tiles,
+                       (const XqGrpTenant*)ten, (const v4i*)P8, p.N, p.k, pl.L, pl.KB, pl.kslice, Mall);
+  hipLaunchKernelGGL(k_extprod_extract_grp, dim3((unsigned)pl.M, (unsigned)((p.k * p.N + 256) / 256)), dim3(256), 0, st,
+                     (const u64*)Mall, (const XqGrpTenant*)ten, (const int32_t*)qdt, p.N, p.k, (const u64*)d_cst, d_out,
+                     d_cpy);
+  prof_end(c0, c0->prof_xq, st, e1, pl.total);
+  HIPCHK(c0, hipGetLastError());
+  return FHE_OK;
+}
+
+int fhe_linear_ggsws_group_batch(fhe_group* g, const fhe_group_ggsw* items, int32_t T, const int64_t* const* h_cst,
+                                 uint64_t* d_out, void* stream) {
+  if (!g) return gfail(FHE_E_ARG, "null group");
+  if (!items || T != (int32_t)g->ctxs.size()) return gfail(FHE_E_ARG, "one fhe_group_ggsw per tenant");
+  if (!h_cst) return gfail(FHE_E_ARG, "null constants");
+  XqGrpPlan pl;
+  int rc = xq_grp_plan(g, items, T, h_cst, false, &pl);  // argument errors first
+  if (rc) return rc;
+  if ((rc = grp_check_params(g))) return rc;
+  if (g->device < 0) return gfail(FHE_E_DEVICE, "host-only contexts");
+  if (hipSetDevice(g->device) != hipSuccess) return gfail(FHE_E_DEVICE, "hipSetDevice failed");
+  if (!pl.nt) return FHE_OK;
+  if (!d_out) return gfail(FHE_E_ARG, "null output rows");
+  if ((rc = grp_ensure_ws(g, pl.bytes))) return rc;
+  const int sh = 64 - g->ctxs[0]->p.msg_bits;
+  std::vector<u64> cs;
+  for (int i = 0; i < pl.nt; ++i)
+    for (int64_t q = 0; q < items[pl.tenant[i]].Q; ++q) cs.push_back((u64)h_cst[pl.tenant[i]][q] << sh);
+  return xq_grp_launch(g, pl, cs, g->ws.p, d_out, nullptr, (hipStream_t)stream);
+}
+
+int fhe_search_ggsws_group_batch(fhe_group* g, const fhe_group_ggsw* items, int32_t T, void* stream) {
+  if (!g) return gfail(FHE_E_ARG, "null group");
+  if (!items || T != (int32_t)g->ctxs.size()) return gfail(FHE_E_ARG, "one fhe_group_ggsw per tenant");
+  XqGrpPlan pl;
+  int rc = xq_grp_plan(g, items, T, nullptr, true, &pl);  // argument errors first
+  if (rc) return rc;
+  if ((rc = grp_enter(g))) return rc;
+  for (int i = 0; i < pl.nt; ++i) {
+    const int32_t t = pl.tenant[i];
+    const std::string who = "tenant " + std::to_string(t) + ": ";
+    if ((rc = need_pack_key(g->ctxs[t]))) return gfail(rc, who + fhe_last_error(g->ctxs[t]));
+    if (items[t].levels_bit > g->ctxs[t]->pack_key.level)
+      return gfail(FHE_E_ARG, who + "levels_bit exceeds the packing key's levels");
+  }
+  if (!pl.nt) return FHE_OK;
+  if ((rc = grp_ks_fits(g, pl.counts.data()))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const fhe_params& p = g->ctxs[0]->p;
+  const int64_t M = pl.M;
+  const size_t Wb = fhe_big_lwe_words(&p), Ws = fhe_small_lwe_words(&p), tb = grp_table_bytes((size_t)T, M);
+  const size_t rows = up16(8 * (size_t)M * (3 * Wb + Ws));
+  if ((rc = grp_ensure_ws(g, tb + rows + pl.bytes))) return rc;
+  u64* small = (u64*)((char*)g->ws.p + tb);
+  u64* ctv = small + (size_t)M * Ws;
+  u64* sgn = ctv + (size_t)M * Wb;
+  u64* cpy = sgn + (size_t)M * Wb;
+  const int sh = 64 - p.msg_bits;
+  std::vector<u64> cs;
+  for (int i = 0; i < pl.nt; ++i) {
+    const fhe_group_ggsw& it = items[pl.tenant[i]];
+    for (int64_t q = 0; q < it.Q; ++q) cs.push_back((u64)(it.cst - it.h_T[q]) << sh);
+  }
+  // the leveled rows and, from the same launch, the copy the packings read
+  // (the sign extraction consumes the rows)
+  if ((rc = xq_grp_launch(g, pl, cs, (char*)g->ws.p + tb + rows, ctv, cpy, st))) return rc;
+  if ((rc = grp_sign(g, ctv, pl.counts.data(), pl.starts.data(), M, sgn, small, g->ws.p, st))) return rc;
+  // tenant t's two packings with its own key, as fhe_search_ggsws_batch
+  for (int i = 0; i < pl.nt; ++i) {
+    const int32_t t = pl.tenant[i];
+    const fhe_group_ggsw& it = items[t];
+    fhe_ctx* ctx = g->ctxs[t];
+    if ((rc = pack_impl(ctx, cpy + (size_t)pl.starts[t] * Wb, pl.counts[t], ctx->pack_key.level, it.d_glwe_acc, st)))
+      return rc;
+    if ((rc = pack_impl(ctx, sgn + (size_t)pl.starts[t] * Wb, pl.counts[t],
+                        it.levels_bit ? it.levels_bit : ctx->pack_key.level, it.d_glwe_bit, st)))
       return rc;
   }
   return FHE_OK;

@@ -52,6 +52,15 @@ class FheGroupCorpus(C.Structure):
                 ("B_old", C.c_int64), ("d_glwe_acc", C.c_void_p), ("d_glwe_bit", C.c_void_p)]
 
 
+class FheGroupGgsw(C.Structure):
+    # one tenant's part of fhe_linear_ggsws_group_batch / fhe_search_ggsws_group_batch:
+    # struct_size first, then the arguments of fhe_search_ggsws_batch
+    _fields_ = [("struct_size", C.c_int32), ("D", C.c_int32), ("d_ggsw", C.c_void_p), ("base_log", C.c_int32),
+                ("level", C.c_int32), ("d_docs", C.c_void_p), ("Q", C.c_int64), ("B", C.c_int64), ("cst", C.c_int64),
+                ("h_T", C.c_void_p), ("levels_bit", C.c_int32), ("reserved", C.c_int32), ("d_glwe_acc", C.c_void_p),
+                ("d_glwe_bit", C.c_void_p)]
+
+
 # (name, restype, argtypes) for every symbol declared in include/fhe_icp.h
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -189,6 +198,9 @@ SIGNATURES = [
     ("fhe_group_form", C.c_int, [_P]),
     ("fhe_keyswitch_group_batch", C.c_int, [_vp, _vp, C.POINTER(_i64), _i32, _u64, _vp, _vp]),
     ("fhe_search_seeded_queries_group_batch", C.c_int, [_vp, _vp, _i32, _vp]),
+    # a group's both-private search
+    ("fhe_linear_ggsws_group_batch", C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    ("fhe_search_ggsws_group_batch", C.c_int, [_vp, _vp, _i32, _vp]),
     # include/fhe_bert.h: the embedding stage's encoder (fheicp.bert)
     ("fhe_bert_create", C.c_int, [_vp, C.c_int, C.POINTER(C.c_void_p)]),
     ("fhe_bert_destroy", None, [_vp]),

@@ -1015,6 +1015,85 @@ class EngineGroup:
         _lib.check(self._L.fhe_search_seeded_queries_group_batch(self._grp, arr, len(items), _stream(self.device)))
         return out
 
+    # ------------------------- both-private search for a group (§8.14) --
+    def _ggsw_items(self, items):
+        """The fhe_group_ggsw array of items (one per engine, None: the tenant
+        sits out) whose tuples start (ggsws, base_log, level, docs, B, D); the
+        per-tenant Q (0 for None)."""
+        if len(items) != len(self.engines):
+            raise ValueError(f"{len(items)} items for {len(self.engines)} tenants")
+        arr = (_lib.FheGroupGgsw * max(len(items), 1))()
+        Qs = []
+        for t, (eng, it) in enumerate(zip(self.engines, items)):
+            arr[t].struct_size = C.sizeof(_lib.FheGroupGgsw)
+            if it is None:
+                Qs.append(0)
+                continue
+            ggsws, base_log, level, docs, B, D = it[:6]
+            try:
+                Q = eng._ggsws(ggsws, base_log, level)
+            except ValueError as e:
+                raise ValueError(f"tenant {t}: {e}") from None
+            a = arr[t]
+            a.D, a.base_log, a.level, a.Q, a.B = int(D), int(base_log), int(level), Q, int(B)
+            a.d_ggsw, a.d_docs = ggsws.data_ptr(), docs.data_ptr()
+            Qs.append(Q)
+        return arr, Qs
+
+    def linear_ggsws(self, items, csts, out: torch.Tensor | None = None) -> torch.Tensor:
+        """fhe_linear_ggsws_group_batch. items: one per engine, None (the
+        tenant sits this call out) or (ggsws, base_log, level, docs, B, D) as
+        Engine.linear_ggsws takes them; csts: per tenant its Q host constants
+        (None for a tenant sitting out). Returns the M padded rows of
+        rows([Q_t B_t]), kN + 1 words each, the padding rows unwritten
+        (`out`: a buffer of at least M rows to write into)."""
+        arr, Qs = self._ggsw_items(items)
+        if len(csts) != len(items):
+            raise ValueError(f"{len(csts)} constant lists for {len(items)} tenants")
+        keep, ptrs = [], (C.c_void_p * max(len(items), 1))()
+        for t, (Q, cs) in enumerate(zip(Qs, csts)):
+            if not Q:
+                continue
+            k, _ = Engine._i64s(cs)
+            if k.size != Q:
+                raise ValueError(f"tenant {t}: {k.size} constants for {Q} queries")
+            keep.append(k)
+            ptrs[t] = k.ctypes.data
+        M, _ = group_rows([Q * int(it[4]) if it is not None else 0 for Q, it in zip(Qs, items)])
+        if out is not None and out.numel() < M * self.W:
+            raise ValueError(f"out holds {out.numel() // self.W} rows, the layout {M}")
+        rows = torch.empty((M, self.W), dtype=torch.int64, device=self.device) if out is None else out
+        _lib.check(self._L.fhe_linear_ggsws_group_batch(self._grp, arr, len(items), ptrs, _ptr(rows),
+                                                        _stream(self.device)))
+        return rows
+
+    def search_ggsws(self, items) -> list:
+        """fhe_search_ggsws_group_batch. items: one per engine, None (the
+        tenant sits this call out) or the arguments of Engine.search_ggsws as
+        a tuple (ggsws, base_log, level, docs, B, D, cst, Ts, levels_bit); the
+        participating tenants share the gadget level. Returns, per tenant,
+        (glwe_acc, glwe_bit) or None."""
+        arr, Qs = self._ggsw_items(items)
+        keep, out = [], []
+        for t, (eng, it, Q) in enumerate(zip(self.engines, items, Qs)):
+            if it is None:
+                out.append(None)
+                continue
+            B, cst, Ts, levels_bit = it[4], it[6], it[7], it[8]
+            hT, _ = Engine._i64s(Ts)
+            if hT.size != Q:
+                raise ValueError(f"tenant {t}: {hT.size} thresholds for {Q} queries")
+            shape = (eng.glwe_count(Q * int(B)), (eng.params.k + 1) * eng.params.N)
+            ga = torch.empty(shape, dtype=torch.int64, device=self.device)
+            gb = torch.empty(shape, dtype=torch.int64, device=self.device)
+            keep.append(hT)
+            a = arr[t]
+            a.cst, a.levels_bit, a.h_T = int(cst), int(levels_bit), hT.ctypes.data
+            a.d_glwe_acc, a.d_glwe_bit = ga.data_ptr(), gb.data_ptr()
+            out.append((ga, gb))
+        _lib.check(self._L.fhe_search_ggsws_group_batch(self._grp, arr, len(items), _stream(self.device)))
+        return out
+
 
 def u64(t: torch.Tensor) -> np.ndarray:
     """Device int64 tensor -> host uint64 array (bit pattern)."""

@@ -275,3 +275,165 @@ class PrivateServer(QueryServer):
             out.append(pack_replies(ga.cpu().numpy().view(np.uint64), gb.cpu().numpy().view(np.uint64), B, self.P0,
                                     Tc))
         return out
+
+
+# ------------------------------------------------------ several key holders --
+# One evaluation-only host serving tenants that each hold their own keys and
+# their own ENCRYPTED documents: every tenant keeps a
+# PrivateServer; a call that names several of them runs ONE grouped transposed
+# external product and ONE group sign extraction
+# (fhe_search_ggsws_group_batch) and answers each tenant in fheicp.query's
+# version-2 reply format, word for word what its own
+# PrivateServer.search_many returns.
+def private_hub_chunks(sizes: dict, cap: int | None = None) -> list:
+    """sizes: {name: (Q, B, level)} -> query.hub_chunks's chunks with one more
+    rule: a library call has one gadget level (the grouped product's K extent),
+    so a tenant whose level differs from the tenant before it starts a new
+    chunk. Tenants and queries stay in order; no query is split."""
+    from .query import MAX_RESULTS, hub_chunks
+    cap = MAX_RESULTS if cap is None else cap
+    chunks, run, level = [], {}, None
+    for name, (Q, B, lv) in sizes.items():
+        if run and int(lv) != level:
+            chunks += hub_chunks(run, cap)
+            run = {}
+        level = int(lv)
+        run[name] = (Q, B)
+    if run:
+        chunks += hub_chunks(run, cap)
+    return chunks
+
+
+class PrivateHub:
+    """Tenants with their own keys and their own encrypted documents behind
+    one GPU. The host learns which tenant asked, Q and B; documents, queries
+    and results stay under each tenant's own key."""
+
+    def __init__(self, device: int = 0):
+        self.device = device
+        self.tenants = {}       # name -> {"server": PrivateServer, "docs": tensor or None, "B": int}
+        self._group = None
+
+    def add_tenant(self, name, eval_keys, cq, P0: int, scheme=None, server=None):
+        """Builds the tenant's PrivateServer from its evaluation keys (or
+        adopts `server`). Every tenant shares the first one's P0 and scheme
+        parameters: ValueError naming the tenant otherwise."""
+        if name in self.tenants:
+            raise ValueError(f"tenant {name!r} is already registered")
+        from .params import params_for_bits
+        want = (scheme if scheme is not None else params_for_bits(int(P0))).with_msg_bits(int(P0)) \
+            if server is None else server.scheme
+        p0 = int(P0) if server is None else int(server.P0)
+        for other, rec in self.tenants.items():
+            s = rec["server"]
+            if int(s.P0) != p0:
+                raise ValueError(f"tenant {name!r}: P0 = {p0} differs from tenant {other!r}'s {int(s.P0)}")
+            if s.scheme != want:
+                raise ValueError(f"tenant {name!r}: scheme parameters differ from tenant {other!r}'s")
+            break
+        if server is None:
+            server = PrivateServer(eval_keys, cq, p0, self.device, scheme)
+        self.tenants[name] = {"server": server, "docs": None, "B": 0}
+        self.close()
+        return server
+
+    def load(self, name, block) -> int:
+        """Packs the tenant's document block (pack_docs_many) and keeps the
+        operand resident; returns B."""
+        rec = self._tenant(name)
+        try:
+            docs, B = rec["server"].pack_docs_many(block)
+        except ValueError as e:
+            raise ValueError(f"tenant {name!r}: {e}") from None
+        if B < 1:
+            raise ValueError(f"tenant {name!r}: an empty document store")
+        rec["docs"], rec["B"] = docs, int(B)
+        return rec["B"]
+
+    def _tenant(self, name) -> dict:
+        if name not in self.tenants:
+            raise ValueError(f"unknown tenant {name!r}")
+        return self.tenants[name]
+
+    def check_reply(self, name, reply, Q: int) -> dict:
+        """A version-2 reply must be the named tenant's: its P0, its loaded
+        document count, Q queries and the matching size. ValueError otherwise."""
+        from .query import unpack_replies
+        rec = self._tenant(name)
+        s = rec["server"]
+        r = unpack_replies(reply, (s.scheme.k + 1) * s.scheme.N, s.scheme.N)
+        if r["P0"] != s.P0 or r["B"] != rec["B"] or r["Q"] != int(Q):
+            raise ValueError(f"tenant {name!r}: reply of {r['Q']} queries x {r['B']} documents at P0 = {r['P0']}, "
+                             f"expected {int(Q)} x {rec['B']} at P0 = {s.P0}")
+        return r
+
+    def group(self):
+        if self._group is None:
+            from .engine import EngineGroup
+            self._group = EngineGroup([rec["server"].engine for rec in self.tenants.values()])
+        return self._group
+
+    def close(self) -> None:
+        """Releases the group (the tenants' servers stay theirs)."""
+        if self._group is not None:
+            self._group.close()
+            self._group = None
+
+    def _plan(self, requests: dict) -> dict:
+        """The per-tenant checks of search_many, before any device work."""
+        from .query import thresholds_for
+        plan = {}
+        for name, (payloads, min_similarity) in requests.items():
+            rec = self._tenant(name)
+            s = rec["server"]
+            if rec["docs"] is None:
+                raise ValueError(f"tenant {name!r} has no documents loaded")
+            try:
+                pls = [unpack_ggsw_query(p) for p in payloads]
+                check_ggsw_batch(pls)
+                s._check(pls[0], "query 0")
+                if (pls[0]["base_log"], pls[0]["level"]) != (s.base_log, s.level):
+                    raise ValueError("query 0: gadget differs from the one the documents were packed for")
+                ms = thresholds_for(min_similarity, len(pls))
+            except ValueError as e:
+                raise ValueError(f"tenant {name!r}: {e}") from None
+            plan[name] = {"payloads": list(payloads), "pls": pls, "ms": ms, "Ts": [s.plan(t)[2] for t in ms],
+                          "cst": s.plan(None)[1]}
+        return plan
+
+    def search_many(self, requests: dict) -> dict:
+        """requests: {name: (payloads, min_similarity)} -> {name: [replies]},
+        version-2 replies for the tenant's QueryClient.decrypt_replies, its
+        queries in order. One library call carries at most max(largest B,
+        8192) results and one gadget level (private_hub_chunks); a tenant
+        alone in a chunk goes through its own PrivateServer.search_many."""
+        from .query import pack_replies
+        plan = self._plan(requests)
+        out = {name: [] for name in requests}
+        names = list(self.tenants)
+        sizes = {name: (len(plan[name]["pls"]), self.tenants[name]["B"], self.tenants[name]["server"].level)
+                 for name in plan}
+        for chunk in private_hub_chunks(sizes):
+            if len(chunk) == 1:
+                name, rng = chunk[0]
+                rec, pn = self.tenants[name], plan[name]
+                out[name] += rec["server"].search_many([pn["payloads"][q] for q in rng], rec["docs"], rec["B"],
+                                                       [pn["ms"][q] for q in rng])
+                continue
+            items, Tcs = [None] * len(names), {}
+            for name, rng in chunk:
+                rec, pn = self.tenants[name], plan[name]
+                s, pls = rec["server"], pn["pls"]
+                g = s.engine.to_dev(np.concatenate([pls[q]["ggsw"] for q in rng]))
+                Tcs[name] = [pn["Ts"][q] for q in rng]
+                items[names.index(name)] = (g, s.base_log, s.level, rec["docs"], rec["B"], pls[0]["D"], pn["cst"],
+                                            Tcs[name], s.bit_levels)
+            res = self.group().search_ggsws(items)
+            for name, rng in chunk:
+                ga, gb = res[names.index(name)]
+                rec = self.tenants[name]
+                reply = pack_replies(ga.cpu().numpy().view(np.uint64), gb.cpu().numpy().view(np.uint64), rec["B"],
+                                     rec["server"].P0, Tcs[name])
+                self.check_reply(name, reply, len(rng))
+                out[name].append(reply)
+        return out

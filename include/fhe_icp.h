@@ -859,6 +859,51 @@ typedef struct fhe_group_corpus {
  * B_old outside [0, B], levels_bit, 2^31 results and more), then the device,
  * then FHE_E_STATE (no packing key, or no bridge key where B_old > 0). */
 int fhe_search_seeded_queries_group_batch(fhe_group* group, const fhe_group_corpus* items, int32_t T, void* stream);
+
+/* ---- both-private search for a group ---------------------
+ * One tenant's part of the two entries below: the arguments of
+ * fhe_search_ggsws_batch. Q = 0: the tenant sits this call out. */
+typedef struct fhe_group_ggsw {
+  int32_t struct_size;        /* = sizeof(fhe_group_ggsw); else FHE_E_ARG */
+  int32_t D;
+  const uint64_t* d_ggsw;     /* Q GGSW queries of gadget (base_log, level) */
+  int32_t base_log;
+  int32_t level;              /* one level for all participating tenants of a call */
+  const void* d_docs;         /* fhe_glwe_docs_queries_pack of the tenant's B documents */
+  int64_t Q;
+  int64_t B;
+  int64_t cst;
+  const int64_t* h_T;         /* Q thresholds (host); the search entry only */
+  int32_t levels_bit;
+  int32_t reserved;           /* 0 */
+  uint64_t* d_glwe_acc;       /* ceil(Q B / N) x (k+1)N words; the search entry only */
+  uint64_t* d_glwe_bit;
+} fhe_group_ggsw;
+/* The leveled step of fhe_linear_ggsws_batch for the T tenants of a group in
+ * a number of launches that does not depend on T: one tables step, one plane
+ * launch, one grouped transposed external product (k_extprod_queries_mfma_grp,
+ * tenant t's queries against tenant t's documents), one slot extraction, and
+ * one memset when K is split. d_out: the padded layout M x (kN+1) of
+ * fhe_group_rows with counts[t] = Q_t B_t; tenant t's rows (query-major, with
+ * trivial(h_cst[t][q] Delta) added) are word for word those of
+ * fhe_linear_ggsws_batch on its own context, and padding rows are neither read
+ * nor written. Needs a group but uses no key. cst, h_T, levels_bit and the two
+ * outputs of the items are ignored. Timing goes to tenant 0's "linear_ggsws"
+ * bucket (one bracket). FHE_E_ARG first ("tenant t: ...": struct_size,
+ * reserved, fhe_linear_ggsws_batch's bounds, nulls, a level that differs from
+ * the first participating tenant's, 2^31 results and more; a launch beyond
+ * 2^31 tiles: "split the call"), then the device. */
+int fhe_linear_ggsws_group_batch(fhe_group* group, const fhe_group_ggsw* items, int32_t T,
+                                 const int64_t* const* h_cst, uint64_t* d_out, void* stream);
+/* The evaluation-only server of fhe_search_ggsws_batch for the T tenants of a
+ * group (items[t] for context t): the grouped leveled step above with
+ * cst - h_T[q] on query q (it also writes the copy the packings read), one
+ * fhe_sign_group_batch over all segments, then the tenant's two packings with
+ * its own packing key. Tenant t's outputs are word for word those of
+ * fhe_search_ggsws_batch on its own context. FHE_E_ARG first (as above, and
+ * levels_bit), then the device, then FHE_E_STATE (no packing key). All tenants
+ * with Q = 0 returns FHE_OK. */
+int fhe_search_ggsws_group_batch(fhe_group* group, const fhe_group_ggsw* items, int32_t T, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,17 @@ rotating order, with the HIP-event split of each (rotations, key switches,
 bridge, packings, leveled step), then a second pass with every tenant rotated
 (all documents old-generation); it writes profiles/r16/stored_tenants.json.
 
+With --private-tenants (docs/AB_LOG_r17.md) it measures
+several key holders' BOTH-PRIVATE searches in one batched call, two-party, at
+16 dimensions, n_bits 6 (P0 = 21, gadget (7, 6)): PrivateHub.search_many for 8
+tenants x (Q = 1, B = 128 encrypted documents) against the eight
+PrivateServer.search calls one after another and one tenant's 1 x 1024 search,
+24 steps after 4 warm-up in rotating order, with the HIP-event split of each;
+then the grouped leveled step's "linear_ggsws" bucket against the sum of the
+tenants' own fhe_linear_ggsws_batch calls on the same operands (outputs
+compared), at the tenant shape and at 2 x 512; it writes
+profiles/r17/private_tenants.json.
+
 The floor of the leveled step is its output, B * (kN + 1) * 8 bytes, over the
 6.29 TB/s a float4 copy reaches on the MI355X; `floor_fraction` is that floor
 over the measured time. Prints one JSON line and writes it to --out.
@@ -417,6 +428,149 @@ def tenants(cq, oq, D: int, n_bits: int, steps: int, warmup: int, Tn: int = 8, B
     hub.search_many({n: (payloads[t], 0.5) for t, n in enumerate(names)})
     out["rotation_kernel_last_group"] = engines[0].kernel_name("blind_rotate_fast")
     out["meets_bar"] = out["meets_bar_a_over_b"] and parity and exact
+    for e in engines:
+        e.close()
+    for c in corpora:
+        c.engine.close()
+    return out
+
+
+def private_tenants(cq, oq, D: int, n_bits: int, steps: int, warmup: int, Tn: int = 8, B: int = 128) -> dict:
+    """Several key holders' both-private searches behind one host (DESIGN.md
+    §8.14), two-party, one process, three things interleaved in rotating order:
+    (a) PrivateHub.search_many for Tn tenants x (Q = 1, B encrypted documents),
+    each with its own keys, (b) the Tn PrivateServer.search calls one after
+    another (the code path without the hub), (c) one tenant's search at Tn * B
+    documents. Host clock around each (reply copies included); per run the
+    HIP-event split (the profile buckets, summed over the tenants' contexts);
+    parity of (a)'s decrypted replies with (b)'s and the restatement. Then the
+    leveled step alone: the grouped launch sequence against the tenants' own
+    fhe_linear_ggsws_batch calls on the same operands, outputs compared, at
+    (Tn, B) and at (2, Tn * B / 2)."""
+    import numpy as np
+    import torch
+    from oracle import quant_ref as Q
+    from fheicp.corpus import EncryptedCorpus
+    from fheicp.engine import group_rows
+    from fheicp.private import PrivateClient, PrivateHub, unpack_doc_block, unpack_ggsw_query
+    from fheicp import _lib
+    B_full = Tn * B
+    hub, clients, corpora = PrivateHub(0), [], []
+    names = [f"tenant{t}" for t in range(Tn)]
+    _, docs = Q.make_corpus(D, B_full, seed=21)
+    qs = [Q.make_corpus(D, 1, seed=100 + t)[0] for t in range(Tn)]
+    blocks = []
+    for t, name in enumerate(names):
+        c = EncryptedCorpus(cq).compile(key_seed=5 + t, device=0, noise_seed=6 + t)
+        client = PrivateClient(c, count=B_full, pack_seed=17 + t, enc_seed=12 + t)
+        hub.add_tenant(name, client.eval_keys(), cq, c.P0, scheme=c.scheme)
+        blocks.append(client.encrypt_docs(docs[t * B:(t + 1) * B]))      # every tenant its own documents
+        hub.load(name, blocks[t])
+        clients.append(client)
+        corpora.append(c)
+    servers = [hub.tenants[n]["server"] for n in names]
+    gadget = (servers[0].base_log, servers[0].level)
+    docs8 = [servers[t].pack_docs(blocks[t])[0] for t in range(Tn)]
+    docs8_full = servers[0].pack_docs(clients[0].encrypt_docs(docs))[0]
+    payloads = [clients[t].encrypt_queries(qs[t][None, :]) for t in range(Tn)]
+    engines = [s.engine for s in servers]
+    for e in engines:
+        e.profile(True)
+    buckets = ("blind_rotate", "keyswitch", "linear_ggsws", "linear_ggsw", "pack")
+
+    def read_split():
+        split = {k: {"ms": 0.0, "launches": 0} for k in buckets}
+        for e in engines:
+            for k in buckets:
+                r = e.profile_read(k)
+                split[k]["ms"] += r["total_ms"]
+                split[k]["launches"] += r["launches"]
+        return split
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out, read_split()
+
+    runs = {"a": lambda: hub.search_many({n: (payloads[t], 0.5) for t, n in enumerate(names)}),
+            "b": lambda: [servers[t].search(payloads[t][0], docs8[t], B, 0.5) for t in range(Tn)],
+            "c": lambda: servers[0].search(payloads[0][0], docs8_full, B_full, 0.5)}
+    orders = ("abc", "cba", "bca", "acb", "cab", "bac")
+    t_ = {k: [] for k in runs}
+    sp = {k: {b: [] for b in buckets} for k in runs}
+    last = {}
+    for i in range(warmup + steps):
+        for k in orders[i % len(orders)]:
+            sec, out, split = timed(runs[k])
+            last[k] = (out, split)
+            if i >= warmup:
+                t_[k].append(sec)
+                for b in buckets:
+                    sp[k][b].append(split[b]["ms"])
+    parity = exact = True
+    for t, name in enumerate(names):
+        acc_a, below_a = clients[t].decrypt_replies(last["a"][0][name])
+        acc_b, below_b = clients[t].decrypt_reply(last["b"][0][t])
+        parity = parity and bool(torch.equal(acc_a[0], acc_b) and torch.equal(below_a[0], below_b))
+        ref = Q.corpus_accumulate(oq, cq.s_e, n_bits, qs[t], docs[t * B:(t + 1) * B])
+        scores = np.float64(Q.corpus_out_scale(oq, cq.s_e)) * ref.astype(np.float64)
+        exact = exact and bool(np.array_equal(acc_a[0].cpu().numpy(), ref) and
+                               np.array_equal(below_a[0].cpu().numpy(), (scores < 0.5).astype(np.int64)))
+    med = {k: statistics.median(v) * 1e3 for k, v in t_.items()}
+    out = {"tenants": Tn, "Q": 1, "B": B, "B_full": B_full, "gadget": list(gadget),
+           "a_hub_search_many_ms": med["a"], "a_min_ms": min(t_["a"]) * 1e3,
+           "b_sequential_searches_ms": med["b"], "b_min_ms": min(t_["b"]) * 1e3, "b_per_search_ms": med["b"] / Tn,
+           "c_one_tenant_full_search_ms": med["c"], "c_min_ms": min(t_["c"]) * 1e3,
+           "ratio_a_over_b": med["a"] / med["b"], "meets_bar_a_over_b": med["a"] <= 0.5 * med["b"],
+           "ratio_a_over_c": med["a"] / med["c"],
+           "event_split_ms": {k: {b: statistics.median(v) for b, v in sp[k].items()} for k in runs},
+           "event_split_launches": {k: {b: last[k][1][b]["launches"] for b in buckets} for k in runs},
+           "parity_with_sequential": parity, "bit_exact": exact, "steps": steps, "warmup": warmup,
+           "build": _lib.lib().fhe_build_info().decode()}
+
+    # the leveled step alone: one grouped launch sequence against the tenants' own calls
+    def leveled(Tl, Bl):
+        grp = hub.group()
+        items = [None] * Tn
+        for t in range(Tl):
+            eng = engines[t]
+            bl = unpack_doc_block(clients[t].encrypt_docs(docs[t * Bl:(t + 1) * Bl]))
+            dq = eng.pack_docs_glwe_queries(eng.to_dev(bl["glwe"]), Bl, D, *gadget)
+            g = eng.to_dev(unpack_ggsw_query(payloads[t][0])["ggsw"])
+            items[t] = (g, gadget[0], gadget[1], dq, Bl, D)
+        csts = [None if it is None else [3 + t] for t, it in enumerate(items)]
+        M, starts = group_rows([Bl if it is not None else 0 for it in items])
+        buf = torch.empty((M, engines[0].W), dtype=torch.int64, device=engines[0].device)
+        own = [torch.empty((Bl, engines[0].W), dtype=torch.int64, device=engines[0].device) for _ in range(Tl)]
+        legs = {"grouped": lambda: grp.linear_ggsws(items, csts, out=buf),
+                "per_tenant": lambda: [engines[t].linear_ggsws(*items[t], csts[t], out=own[t]) for t in range(Tl)]}
+        ms = {k: [] for k in legs}
+        nl = {}
+        read_split()
+        for i in range(warmup + steps):
+            for k in (("grouped", "per_tenant") if i % 2 == 0 else ("per_tenant", "grouped")):
+                legs[k]()
+                torch.cuda.synchronize()
+                r = read_split()["linear_ggsws"]
+                nl[k] = r["launches"]
+                if i >= warmup:
+                    ms[k].append(r["ms"])
+        same = all(torch.equal(buf[starts[t]:starts[t] + Bl], own[t]) for t in range(Tl))
+        g_ms, p_ms = statistics.median(ms["grouped"]), statistics.median(ms["per_tenant"])
+        return {"T": Tl, "B": Bl, "grouped_ms": g_ms, "per_tenant_sum_ms": p_ms, "ratio": g_ms / p_ms,
+                "grouped_brackets": nl["grouped"], "per_tenant_brackets": nl["per_tenant"],
+                "identical_words": bool(same), "meets_bar": bool(g_ms < p_ms and same)}
+    out["leveled"] = [leveled(Tn, B), leveled(2, B_full // 2)]
+    for e in engines:
+        e.profile(False)
+    # the buckets name what ran last: one more hub call names the group kernels
+    hub.search_many({n: (payloads[t], 0.5) for t, n in enumerate(names)})
+    out["leveled_kernel_group"] = engines[0].kernel_name("linear_ggsws")
+    out["rotation_kernel_last_group"] = engines[0].kernel_name("blind_rotate_fast")
+    out["meets_bar"] = bool(out["meets_bar_a_over_b"] and parity and exact and all(l["meets_bar"] for l in out["leveled"]))
+    hub.close()
     for e in engines:
         e.close()
     for c in corpora:
@@ -1018,15 +1172,22 @@ def main() -> int:
                          "CorpusServer.search calls and one tenant's B = 1024 search, 24 interleaved steps after 4 "
                          "warm-up, with the HIP-event split per run, then again with every tenant rotated (all "
                          "documents old); writes profiles/r16/stored_tenants.json")
+    ap.add_argument("--private-tenants", action="store_true",
+                    help="measure several key holders' both-private searches in one batched call (two-party, "
+                         "DESIGN.md §8.14): PrivateHub.search_many for 8 tenants x (Q = 1, B = 128) against the eight "
+                         "PrivateServer.search calls and one tenant's B = 1024 search, 24 interleaved steps after 4 "
+                         "warm-up, with the HIP-event split per run, then the grouped leveled step against the "
+                         "tenants' own calls; writes profiles/r17/private_tenants.json")
     ap.add_argument("--tenant-shape", type=int, nargs=2, default=[8, 128], metavar=("T", "B"),
-                    help="--tenants / --stored-tenants: T tenants of B documents each (default 8 128)")
+                    help="--tenants / --stored-tenants / --private-tenants: T tenants of B documents each (default 8 128)")
     ap.add_argument("--out", default=None, help="default profiles/query_bench.json "
                                                 "(--multi-query: profiles/r11/multi_query.json, "
                                                 "--stored-queries: profiles/r12/stored_queries.json, "
                                                 "--private-queries: profiles/r13/private_queries.json)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = str(REPO / "profiles" / ("r16/stored_tenants.json" if a.stored_tenants else
+        a.out = str(REPO / "profiles" / ("r17/private_tenants.json" if a.private_tenants else
+                                         "r16/stored_tenants.json" if a.stored_tenants else
                                          "r15/rotated.json" if a.rotated else
                                          "r14/tenants.json" if a.tenants else
                                          "r11/multi_query.json" if a.multi_query else
@@ -1047,6 +1208,16 @@ def main() -> int:
         res = {"bench": "query_bench --rotated", "device": torch.cuda.get_device_name(0), "D": 16, "n_bits": 6,
                "P0": cq.worst_msg_bits(), "build": _lib.lib().fhe_build_info().decode(), "rotated": ro,
                "bit_exact": ro["bit_exact"]}
+        line = json.dumps(res)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(line + "\n")
+        print(line)
+        return 0
+    if a.private_tenants:
+        cq, oq = corpus_quant(16, 6)
+        tn = private_tenants(cq, oq, 16, 6, steps=24, warmup=4, Tn=a.tenant_shape[0], B=a.tenant_shape[1])
+        res = {"bench": "query_bench --private-tenants", "device": torch.cuda.get_device_name(0), "D": 16, "n_bits": 6,
+               "P0": cq.worst_msg_bits(), "private_tenants": tn, "meets_bar": tn["meets_bar"]}
         line = json.dumps(res)
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(line + "\n")
