@@ -45,6 +45,7 @@
 #include "k_bridge.h"
 #include "k_extprod.h"
 #include "k_extprod_q.h"
+#include "k_private_seeded.h"
 #include "k_blind_rotate.h"
 #include "k_extprod_grp.h"
 
@@ -133,6 +134,10 @@ struct fhe_ctx {
   // the batched entries (k_extprod_q.h) use xp_ws as: the Q queries' byte
   // planes | the Q x G x (k+1)N result | the Q scaled constants
   ProfAcc prof_xq;          // fhe_linear_ggsws_batch: k_ggsws_planes + the GEMM + k_extprod_extract_queries
+  // seeded GGSW queries (k_private_seeded.h): their full form, Q x fhe_ggsw_words
+  // (grown on demand), and the time of k_expand_ggsw_seeded
+  DevBuf xs_ws;
+  ProfAcc prof_xs;
 };
 
 static std::mutex g_err_mu;
@@ -640,7 +645,7 @@ void fhe_ctx_destroy(fhe_ctx* ctx) {
                       (void*)ctx->bskf[4], (void*)ctx->bskf_fft[4],
                       (void*)ctx->ksk8, ctx->ks_ws[0].p, ctx->ks_ws[1].p, (void*)ctx->tw4, (void*)ctx->bsk_fft_v2,
                       (void*)ctx->psi, (void*)ctx->mb_msg, ctx->lq_ws.p, (void*)ctx->pack_key.key,
-                      (void*)ctx->pack_key.planes, ctx->pack_ws.p, ctx->xp_ws.p, ctx->lsq_cst.p,
+                      (void*)ctx->pack_key.planes, ctx->pack_ws.p, ctx->xp_ws.p, ctx->xs_ws.p, ctx->lsq_cst.p,
                       (void*)ctx->bridge_key.key, (void*)ctx->bridge_key.planes, ctx->bridge_ws.p})
       (void)hipFree(ptr);
     for (hipStream_t s : ctx->lane_st)
@@ -657,6 +662,7 @@ void fhe_ctx_destroy(fhe_ctx* ctx) {
     free_ev(ctx->prof_bridge);
     free_ev(ctx->prof_xp);
     free_ev(ctx->prof_xq);
+    free_ev(ctx->prof_xs);
   }
   delete ctx;
 }
@@ -988,8 +994,10 @@ int fhe_encrypt_batch_key(fhe_ctx* ctx, const int64_t* d_msg, int64_t count, con
 // GLWEs per pair of the packed feature encoding (k_client.h)
 static int packed_chunks(const fhe_params& p, int32_t D) { return (D + p.N - 1) / p.N; }
 
-static int encrypt_packed_impl(fhe_ctx* ctx, const int64_t* d_qx, int64_t B, int32_t D, const ChaKey& K,
-                               uint64_t id0, uint64_t* d_glwe, void* stream) {
+// Km: masks, Kn: noise (the full form passes its one key twice); body_only: the
+// seeded form's output, B x G x N body words
+static int encrypt_packed_impl(fhe_ctx* ctx, const int64_t* d_qx, int64_t B, int32_t D, const ChaKey& Km,
+                               const ChaKey& Kn, bool body_only, uint64_t id0, uint64_t* d_glwe, void* stream) {
   int rc = need_secret(ctx);
   if (rc) return rc;
   if (B < 0 || D <= 0 || (B > 0 && (!d_qx || !d_glwe))) return fail(ctx, FHE_E_ARG, "bad packed-encrypt arguments");
@@ -998,20 +1006,21 @@ static int encrypt_packed_impl(fhe_ctx* ctx, const int64_t* d_qx, int64_t B, int
   const int G = packed_chunks(p, D);
   if (B * G > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "packed-encrypt batch too large: split the call");
   const size_t lds = (size_t)p.k * p.N * 9;
-  hipLaunchKernelGGL(k_encrypt_packed, dim3((unsigned)(B * G)), dim3(256), lds, (hipStream_t)stream, K, p.N, p.k,
-                     p.msg_bits, p.glwe_noise_bits, ctx->s_big, d_qx, (int)D, G, id0, d_glwe);
+  hipLaunchKernelGGL(k_encrypt_packed, dim3((unsigned)(B * G)), dim3(256), lds, (hipStream_t)stream, Km, Kn, p.N,
+                     p.k, p.msg_bits, p.glwe_noise_bits, ctx->s_big, d_qx, (int)D, G, id0, d_glwe, (int)body_only);
   HIPCHK(ctx, hipGetLastError());
   return FHE_OK;
 }
 int fhe_encrypt_packed_batch(fhe_ctx* ctx, const int64_t* d_qx, int64_t B, int32_t D, uint64_t seed, uint64_t id0,
                              uint64_t* d_glwe, void* stream) {
-  return encrypt_packed_impl(ctx, d_qx, B, D, key_from_seed(seed), id0, d_glwe, stream);
+  const ChaKey K = key_from_seed(seed);
+  return encrypt_packed_impl(ctx, d_qx, B, D, K, K, false, id0, d_glwe, stream);
 }
 int fhe_encrypt_packed_batch_key(fhe_ctx* ctx, const int64_t* d_qx, int64_t B, int32_t D, const uint32_t h_key[8],
                                  uint64_t id0, uint64_t* d_glwe, void* stream) {
   ChaKey K;
   if (!key_arg(h_key, K)) return fail(ctx, FHE_E_ARG, "null encryption key");
-  return encrypt_packed_impl(ctx, d_qx, B, D, K, id0, d_glwe, stream);
+  return encrypt_packed_impl(ctx, d_qx, B, D, K, K, false, id0, d_glwe, stream);
 }
 
 int fhe_linear_packed_batch(fhe_ctx* ctx, const uint64_t* d_glwe, int64_t B, int32_t D, const int64_t* d_w,
@@ -2865,28 +2874,31 @@ int fhe_extprod_plan(const fhe_params* params, double w_norm2, int32_t* base_log
   return fail(nullptr, FHE_E_STATE, "no ggsw gadget keeps 2^(63 - msg_bits) at 9.2 sigma for this query norm");
 }
 
-static int encrypt_ggsw_impl(fhe_ctx* ctx, const int64_t* d_w, int32_t D, int32_t beta, int32_t L, const ChaKey& K,
-                             uint64_t id0, uint64_t* d_ggsw, void* stream) {
+// Km: masks, Kn: noise (the full form passes its one key twice); body_only: the
+// seeded form's output, (k+1) L x N body words
+static int encrypt_ggsw_impl(fhe_ctx* ctx, const int64_t* d_w, int32_t D, int32_t beta, int32_t L, const ChaKey& Km,
+                             const ChaKey& Kn, bool body_only, uint64_t id0, uint64_t* d_ggsw, void* stream) {
   int rc = ggsw_args(ctx, 0, D, beta, L);  // argument errors first: a host-only context reports them too
   if (rc) return rc;
   if ((rc = need_secret(ctx))) return rc;
   if (!d_w || !d_ggsw) return fail(ctx, FHE_E_ARG, "null ggsw buffers");
   const fhe_params& p = ctx->p;
   hipLaunchKernelGGL(k_encrypt_ggsw, dim3((unsigned)((p.k + 1) * L)), dim3(256), 8 * (size_t)p.N + p.N,
-                     (hipStream_t)stream, K, p.N, p.k, (int)L, (int)beta, p.glwe_noise_bits, ctx->s_big, d_w, (int)D,
-                     (u64)id0, d_ggsw);
+                     (hipStream_t)stream, Km, Kn, p.N, p.k, (int)L, (int)beta, p.glwe_noise_bits, ctx->s_big, d_w,
+                     (int)D, (u64)id0, d_ggsw, (int)body_only);
   HIPCHK(ctx, hipGetLastError());
   return FHE_OK;
 }
 int fhe_encrypt_ggsw(fhe_ctx* ctx, const int64_t* d_w, int32_t D, int32_t base_log, int32_t level, uint64_t seed,
                      uint64_t id0, uint64_t* d_ggsw, void* stream) {
-  return encrypt_ggsw_impl(ctx, d_w, D, base_log, level, key_from_seed(seed), id0, d_ggsw, stream);
+  const ChaKey K = key_from_seed(seed);
+  return encrypt_ggsw_impl(ctx, d_w, D, base_log, level, K, K, false, id0, d_ggsw, stream);
 }
 int fhe_encrypt_ggsw_key(fhe_ctx* ctx, const int64_t* d_w, int32_t D, int32_t base_log, int32_t level,
                          const uint32_t h_key[8], uint64_t id0, uint64_t* d_ggsw, void* stream) {
   ChaKey K;
   if (!key_arg(h_key, K)) return fail(ctx, FHE_E_ARG, "null encryption key");
-  return encrypt_ggsw_impl(ctx, d_w, D, base_log, level, K, id0, d_ggsw, stream);
+  return encrypt_ggsw_impl(ctx, d_w, D, base_log, level, K, K, false, id0, d_ggsw, stream);
 }
 
 // documents per GLWE and GLWEs per batch
@@ -3153,6 +3165,194 @@ int fhe_search_ggsws_batch(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t base_lo
   return post_leveled_search(ctx, w, Q * B, levels_bit, d_glwe_acc, d_glwe_bit, stream);
 }
 
+// ---- both-private search on seeded payloads (k_private_seeded.h, §8.15) -----
+size_t fhe_ggsw_body_words(const fhe_params* p, int32_t base_log, int32_t level) {
+  if (!p || !pack_gadget_ok(base_log, level)) return 0;
+  return (size_t)(p->k + 1) * level * p->N;
+}
+// an argument error of a full-form sibling's checks, told as a seeded entry's
+static int seeded_arg(fhe_ctx* ctx, int rc) {
+  if (rc != FHE_E_ARG) return rc;
+  return fail(ctx, FHE_E_ARG, std::string("seeded: ") + fhe_last_error(ctx));
+}
+
+int fhe_encrypt_packed_seeded_batch(fhe_ctx* ctx, const int64_t* d_qx, int64_t B, int32_t D,
+                                    const uint32_t h_mask_key[8], const uint32_t h_noise_key[8], uint64_t id0,
+                                    uint64_t* d_body, void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  ChaKey Km, Kn;  // argument errors first: a host-only context reports them too
+  if (!key_arg(h_mask_key, Km) || !key_arg(h_noise_key, Kn))
+    return fail(ctx, FHE_E_ARG, "seeded packed-encrypt: null mask or noise key");
+  if (B < 0 || D <= 0 || (B > 0 && (!d_qx || !d_body)))
+    return fail(ctx, FHE_E_ARG, "bad seeded packed-encrypt arguments");
+  return seeded_arg(ctx, encrypt_packed_impl(ctx, d_qx, B, D, Km, Kn, true, id0, d_body, stream));
+}
+
+int fhe_encrypt_ggsw_seeded(fhe_ctx* ctx, const int64_t* d_w, int32_t D, int32_t base_log, int32_t level,
+                            const uint32_t h_mask_key[8], const uint32_t h_noise_key[8], uint64_t id0,
+                            uint64_t* d_body, void* stream) {
+  int rc = seeded_arg(ctx, ggsw_args(ctx, 0, D, base_log, level));  // argument errors first
+  if (rc) return rc;
+  ChaKey Km, Kn;
+  if (!key_arg(h_mask_key, Km) || !key_arg(h_noise_key, Kn))
+    return fail(ctx, FHE_E_ARG, "seeded ggsw: null mask or noise key");
+  if (!d_w || !d_body) return fail(ctx, FHE_E_ARG, "null seeded ggsw buffers");
+  return seeded_arg(ctx, encrypt_ggsw_impl(ctx, d_w, D, base_log, level, Km, Kn, true, id0, d_body, stream));
+}
+
+// rows x N bodies -> rows x (k+1)N full form (k_expand_ggsw_seeded's addressing)
+static int expand_private_impl(fhe_ctx* ctx, const ChaKey& Km, uint32_t tag, const uint64_t* d_body,
+                               const uint64_t* d_ids, uint64_t id_base, int64_t items, int64_t rows, int row_ids,
+                               int comp_ids, int comp_blk, uint64_t* d_out, hipStream_t st) {
+  const fhe_params& p = ctx->p;
+  if (items * rows > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "seeded expansion too large: split the call");
+  hipEvent_t e1;
+  prof_begin(ctx, ctx->prof_xs, st, &e1);
+  ctx->prof_xs.kernel = "k_expand_ggsw_seeded";
+  hipLaunchKernelGGL(k_expand_ggsw_seeded, dim3((unsigned)(items * rows)), dim3(256), 0, st, Km, tag, d_body, d_ids,
+                     (u64)id_base, rows, row_ids, comp_ids, comp_blk, p.N, p.k, d_out);
+  prof_end(ctx, ctx->prof_xs, st, e1, items);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+int fhe_expand_packed_seeded_batch(fhe_ctx* ctx, const uint64_t* d_body, uint64_t id0, int64_t B, int32_t D,
+                                   const uint32_t h_mask_key[8], uint64_t* d_glwe, void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  ChaKey Km;  // argument errors first: a host-only context reports them too
+  if (!key_arg(h_mask_key, Km)) return fail(ctx, FHE_E_ARG, "seeded packed expansion: null mask key");
+  if (B < 0 || D <= 0 || (B > 0 && (!d_body || !d_glwe)))
+    return fail(ctx, FHE_E_ARG, "bad seeded packed expansion arguments");
+  int rc = need_device(ctx);
+  if (rc) return rc;
+  if (B == 0) return FHE_OK;
+  const fhe_params& p = ctx->p;
+  const int64_t G = packed_chunks(p, D);
+  if (B * G > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "seeded packed expansion too large: split the call");
+  return expand_private_impl(ctx, Km, TAG_ENC_MASK, d_body, nullptr, id0, 1, B * G, 1, 0, p.N / 8, d_glwe,
+                             (hipStream_t)stream);
+}
+
+// Q queries' bodies -> Q GGSWs; the stream ids from d_ids (Q of them, device) or, for one query, id_base
+static int expand_ggsws_impl(fhe_ctx* ctx, const ChaKey& Km, const uint64_t* d_body, const uint64_t* d_ids,
+                             uint64_t id_base, int64_t Q, int32_t L, uint64_t* d_ggsw, hipStream_t st) {
+  const fhe_params& p = ctx->p;
+  return expand_private_impl(ctx, Km, TAG_GGSW_MASK, d_body, d_ids, id_base, Q, (int64_t)(p.k + 1) * L, p.k, 1, 0,
+                             d_ggsw, st);
+}
+
+int fhe_expand_ggsws_seeded(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t Q, int32_t base_log,
+                            int32_t level, const uint32_t h_mask_key[8], uint64_t* d_ggsw, void* stream) {
+  int rc = seeded_arg(ctx, ggsw_args(ctx, 0, 1, base_log, level));  // argument errors first
+  if (rc) return rc;
+  ChaKey Km;
+  if (!key_arg(h_mask_key, Km)) return fail(ctx, FHE_E_ARG, "seeded ggsw expansion: null mask key");
+  if (Q < 1 || Q > 65535) return fail(ctx, FHE_E_ARG, "bad seeded ggsw expansion arguments (Q outside [1, 65535])");
+  if (!d_body || !d_id0 || !d_ggsw) return fail(ctx, FHE_E_ARG, "null seeded ggsw expansion buffers");
+  if ((rc = need_device(ctx))) return rc;
+  return expand_ggsws_impl(ctx, Km, d_body, d_id0, 0, Q, level, d_ggsw, (hipStream_t)stream);
+}
+
+int fhe_glwe_docs_pack_seeded(fhe_ctx* ctx, const uint64_t* d_body, uint64_t id0, int64_t B, int32_t D,
+                              int32_t base_log, int32_t level, const uint32_t h_mask_key[8], void* d_docs8,
+                              void* stream) {
+  int rc = seeded_arg(ctx, ggsw_args(ctx, B, D, base_log, level));  // argument errors first
+  if (rc) return rc;
+  ChaKey Km;
+  if (!key_arg(h_mask_key, Km)) return fail(ctx, FHE_E_ARG, "seeded ggsw documents: null mask key");
+  if (B > 0 && (!d_body || !d_docs8)) return fail(ctx, FHE_E_ARG, "null seeded ggsw document buffers");
+  const fhe_params& p = ctx->p;
+  const int n1 = (p.k + 1) * p.N, KB = n1 * level / 64;
+  if (n1 % 128) return fail(ctx, FHE_E_ARG, "seeded ggsw documents need (k+1)N a multiple of 128");
+  const int64_t G = ggsw_glwes(p, B, D), ncb = (G + 15) / 16;
+  if (ncb > 65535) return fail(ctx, FHE_E_ARG, "seeded ggsw document batch too large: split the call");
+  if ((rc = need_device(ctx))) return rc;
+  if (B == 0) return FHE_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(ctx, hipMemsetAsync(d_docs8, 0, fhe_glwe_docs_bytes(&p, B, D, level), st));
+  hipLaunchKernelGGL(k_glwe_digits_seeded, dim3((unsigned)(n1 / 128), (unsigned)ncb), dim3(256), 0, st, Km, d_body,
+                     (u64)id0, G, p.N, p.k, (int)base_log, (int)level, KB, (uint32_t*)d_docs8);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+int fhe_glwe_docs_queries_pack_seeded(fhe_ctx* ctx, const uint64_t* d_body, uint64_t id0, int64_t B, int32_t D,
+                                      int32_t base_log, int32_t level, const uint32_t h_mask_key[8], void* d_docs,
+                                      void* stream) {
+  int rc = seeded_arg(ctx, ggsws_args(ctx, 1, B, D, base_log, level));  // argument errors first
+  if (rc) return rc;
+  ChaKey Km;
+  if (!key_arg(h_mask_key, Km)) return fail(ctx, FHE_E_ARG, "seeded ggsw queries documents: null mask key");
+  if (!d_body || !d_docs) return fail(ctx, FHE_E_ARG, "null seeded ggsw queries document buffers");
+  const fhe_params& p = ctx->p;
+  const int n1 = (p.k + 1) * p.N;
+  const int64_t G = ggsw_glwes(p, B, D);
+  if (G > 65535) return fail(ctx, FHE_E_ARG, "seeded ggsw queries document batch too large: split the call");
+  if ((rc = need_device(ctx))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(ctx, hipMemsetAsync(d_docs, 0, fhe_glwe_docs_queries_bytes(&p, B, D, level), st));
+  hipLaunchKernelGGL(k_glwe_digits_rev_seeded, dim3((unsigned)((n1 + 2047) / 2048), (unsigned)G), dim3(256), 0, st, Km,
+                     d_body, (u64)id0, p.N, p.k, (int)base_log, (int)level, (uint8_t*)d_docs);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+// the search entries on seeded queries: expand into the context's workspace,
+// then the full-form entry, whose checks ran here first (no work is queued
+// for a call that fails)
+static int search_seeded_keys(fhe_ctx* ctx, int32_t levels_bit) {
+  int rc = need_eval_keys(ctx);
+  if (rc) return rc;
+  if ((rc = need_pack_key(ctx))) return rc;
+  if (levels_bit > ctx->pack_key.level)
+    return fail(ctx, FHE_E_ARG, "seeded search ggsw levels_bit exceeds the packing key's levels");
+  return FHE_OK;
+}
+static int expand_queries_ws(fhe_ctx* ctx, const ChaKey& Km, const uint64_t* d_body, const uint64_t* d_ids,
+                             uint64_t id_base, int64_t Q, int32_t base_log, int32_t level, void* stream) {
+  const size_t need = 8 * (size_t)Q * fhe_ggsw_words(&ctx->p, base_log, level);
+  int rc = reserve(ctx, ctx->xs_ws, need, FHE_E_DEVICE, "hipMalloc of the seeded ggsw expansion workspace failed");
+  if (rc) return rc;
+  return expand_ggsws_impl(ctx, Km, d_body, d_ids, id_base, Q, level, (uint64_t*)ctx->xs_ws.p, (hipStream_t)stream);
+}
+
+int fhe_search_ggsw_seeded_batch(fhe_ctx* ctx, const uint64_t* d_body, uint64_t id0, int32_t base_log, int32_t level,
+                                 const uint32_t h_mask_key[8], const void* d_docs8, int64_t B, int32_t D, int64_t cst,
+                                 int64_t T, int32_t levels_bit, uint64_t* d_glwe_acc, uint64_t* d_glwe_bit,
+                                 void* stream) {
+  int rc = seeded_arg(ctx, ggsw_args(ctx, B, D, base_log, level));  // argument errors first
+  if (rc) return rc;
+  ChaKey Km;
+  if (!key_arg(h_mask_key, Km)) return fail(ctx, FHE_E_ARG, "seeded search ggsw: null mask key");
+  if (levels_bit < 0 || levels_bit > 8)
+    return fail(ctx, FHE_E_ARG, "bad seeded search ggsw arguments (levels_bit outside [0, 8])");
+  if (B > 0 && (!d_body || !d_docs8 || !d_glwe_acc || !d_glwe_bit))
+    return fail(ctx, FHE_E_ARG, "null seeded search ggsw arguments");
+  if ((rc = search_seeded_keys(ctx, levels_bit))) return rc;
+  if (B == 0) return FHE_OK;
+  if ((rc = expand_queries_ws(ctx, Km, d_body, nullptr, id0, 1, base_log, level, stream))) return rc;
+  return seeded_arg(ctx, fhe_search_ggsw_batch(ctx, (const uint64_t*)ctx->xs_ws.p, base_log, level, d_docs8, B, D, cst,
+                                               T, levels_bit, d_glwe_acc, d_glwe_bit, stream));
+}
+
+int fhe_search_ggsws_seeded_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int32_t base_log,
+                                  int32_t level, const uint32_t h_mask_key[8], const void* d_docs, int64_t Q,
+                                  int64_t B, int32_t D, int64_t cst, const int64_t* h_T, int32_t levels_bit,
+                                  uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream) {
+  int rc = seeded_arg(ctx, ggsws_args(ctx, Q, B, D, base_log, level));  // argument errors first
+  if (rc) return rc;
+  ChaKey Km;
+  if (!key_arg(h_mask_key, Km)) return fail(ctx, FHE_E_ARG, "seeded search ggsw queries: null mask key");
+  if (levels_bit < 0 || levels_bit > 8)
+    return fail(ctx, FHE_E_ARG, "bad seeded search ggsw queries arguments (levels_bit outside [0, 8])");
+  if (!d_body || !d_id0 || !d_docs || !h_T || !d_glwe_acc || !d_glwe_bit)
+    return fail(ctx, FHE_E_ARG, "null seeded search ggsw queries arguments");
+  if ((rc = search_seeded_keys(ctx, levels_bit))) return rc;
+  if ((rc = expand_queries_ws(ctx, Km, d_body, d_id0, 0, Q, base_log, level, stream))) return rc;
+  return seeded_arg(ctx, fhe_search_ggsws_batch(ctx, (const uint64_t*)ctx->xs_ws.p, base_log, level, d_docs, Q, B, D,
+                                                cst, h_T, levels_bit, d_glwe_acc, d_glwe_bit, stream));
+}
+
 int fhe_threshold_batch(fhe_ctx* ctx, const uint64_t* d_ct_acc, int64_t count, int64_t T, uint64_t* d_bit,
                         void* stream) {
   int rc = need_eval_keys(ctx);
@@ -3347,6 +3547,7 @@ static ProfAcc* prof_bucket(fhe_ctx* ctx, const char* kernel) {
   if (!strcmp(kernel, "bridge")) return &ctx->prof_bridge;
   if (!strcmp(kernel, "linear_ggsw")) return &ctx->prof_xp;
   if (!strcmp(kernel, "linear_ggsws")) return &ctx->prof_xq;
+  if (!strcmp(kernel, "expand_ggsw_seeded")) return &ctx->prof_xs;
   return nullptr;
 }
 

@@ -221,9 +221,13 @@ __device__ __forceinline__ void packed_mac8(const u64* A, int N, int u0, const i
 // Client side: GLWE encryption of the packed features (fhe_encrypt_packed_batch).
 // One 256-thread workgroup per GLWE (pair b, chunk g); the body's negacyclic
 // products with the binary key run as in k_keygen_bsk. glwe: [B][G][(k+1)N].
-__global__ void __launch_bounds__(256) k_encrypt_packed(ChaKey K, int N, int k, int msg_bits, int noise_bits,
-                                                        const u64* __restrict__ s_big, const int64_t* __restrict__ x,
-                                                        int D, int G, u64 id0, u64* __restrict__ glwe) {
+// The masks come from the key Km and the noise from Kn: one secret key twice
+// for the full form, a public mask key and a secret noise key for the seeded
+// form, which stores the bodies alone, [B][G][N] (body_only).
+__global__ void __launch_bounds__(256) k_encrypt_packed(ChaKey Km, ChaKey Kn, int N, int k, int msg_bits,
+                                                        int noise_bits, const u64* __restrict__ s_big,
+                                                        const int64_t* __restrict__ x, int D, int G, u64 id0,
+                                                        u64* __restrict__ glwe, int body_only) {
   extern __shared__ u64 shm[];
   u64* A = shm;                                              // kN
   unsigned char* S = reinterpret_cast<unsigned char*>(shm + (size_t)k * N);  // kN
@@ -231,11 +235,16 @@ __global__ void __launch_bounds__(256) k_encrypt_packed(ChaKey K, int N, int k, 
   const int g = (int)(bg - b * G), Dg = min(D - g * N, N);
   const u64 id = id0 + (u64)bg;
   u64* o = glwe + (size_t)bg * (k + 1) * N;
+  u64* ob = body_only ? glwe + (size_t)bg * N : o + (size_t)k * N;
   for (int blk = threadIdx.x; blk < k * N / 8; blk += 256) {
     u64 m[8];
-    stream_block(K, TAG_ENC_MASK, id, (uint32_t)blk, m);
+    stream_block(Km, TAG_ENC_MASK, id, (uint32_t)blk, m);
 #pragma unroll
-    for (int q = 0; q < 8; ++q) A[8 * blk + q] = o[8 * blk + q] = m[q];
+    for (int q = 0; q < 8; ++q) A[8 * blk + q] = m[q];
+    if (!body_only) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) o[8 * blk + q] = m[q];
+    }
   }
   for (int t = threadIdx.x; t < k * N; t += 256) S[t] = (unsigned char)s_big[t];
   __syncthreads();
@@ -251,13 +260,13 @@ __global__ void __launch_bounds__(256) k_encrypt_packed(ChaKey K, int N, int k, 
     }
   }
   u64 e[8];
-  stream_block(K, TAG_ENC_NOISE, id, (uint32_t)(t0 >> 3), e);
+  stream_block(Kn, TAG_ENC_NOISE, id, (uint32_t)(t0 >> 3), e);
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
     if (q >= per) break;
     const int t = t0 + q;
     const u64 msg = t < Dg ? (u64)x[(size_t)b * D + g * N + t] << (64 - msg_bits) : 0;
-    o[(size_t)k * N + t] = body[q] + msg + (u64)tuniform(e[(t & 7)], noise_bits);
+    ob[t] = body[q] + msg + (u64)tuniform(e[(t & 7)], noise_bits);
   }
 }
 

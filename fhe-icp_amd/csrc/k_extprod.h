@@ -24,16 +24,21 @@
 // D <= N). Rows as k_keygen_pack's: masks from stream (TAG_GGSW_MASK,
 // id0 + row k + c'), noise from (TAG_GGSW_NOISE, id0 + row), body = sum_c'
 // A_c' S_c' + E + message. (S_c X^-j)[t] = S_c[t + j], or -S_c[t + j - N] past
-// the end. Layout [c][l][component][coef].
-__global__ void __launch_bounds__(256) k_encrypt_ggsw(ChaKey K, int N, int k, int L, int beta, int noise_bits,
-                                                      const u64* __restrict__ s_big, const int64_t* __restrict__ W,
-                                                      int D, u64 id0, u64* __restrict__ ggsw) {
+// the end. Layout [c][l][component][coef]. The masks come from the key Km and
+// the noise from Kn: one secret key twice for the full form, a public mask
+// key and a secret noise key for the seeded form, which
+// stores the bodies alone, [c][l][coef] (body_only).
+__global__ void __launch_bounds__(256) k_encrypt_ggsw(ChaKey Km, ChaKey Kn, int N, int k, int L, int beta,
+                                                      int noise_bits, const u64* __restrict__ s_big,
+                                                      const int64_t* __restrict__ W, int D, u64 id0,
+                                                      u64* __restrict__ ggsw, int body_only) {
   extern __shared__ u64 shm[];
   u64* A = shm;                                  // N
   unsigned char* S = (unsigned char*)(shm + N);  // N
   const int row = blockIdx.x;  // c * L + l
   const int c = row / L, l = row % L;
   u64* dst = ggsw + (size_t)row * (k + 1) * N;
+  u64* bdst = body_only ? ggsw + (size_t)row * N : dst + (size_t)k * N;
   constexpr int MAXC = 8;  // N <= 2048 -> 8 coefficients per thread
   u64 body[MAXC];
   const int per = N / 256;
@@ -42,11 +47,12 @@ __global__ void __launch_bounds__(256) k_encrypt_ggsw(ChaKey K, int N, int k, in
     const u64 sid = id0 + (u64)row * k + cc;
     for (int blk = threadIdx.x; blk < N / 8; blk += 256) {
       u64 w[8];
-      stream_block(K, TAG_GGSW_MASK, sid, (uint32_t)blk, w);
+      stream_block(Km, TAG_GGSW_MASK, sid, (uint32_t)blk, w);
 #pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        A[8 * blk + q] = w[q];
-        dst[(size_t)cc * N + 8 * blk + q] = w[q];
+      for (int q = 0; q < 8; ++q) A[8 * blk + q] = w[q];
+      if (!body_only) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) dst[(size_t)cc * N + 8 * blk + q] = w[q];
       }
     }
     for (int t = threadIdx.x; t < N; t += 256) S[t] = (unsigned char)s_big[(size_t)cc * N + t];
@@ -76,8 +82,28 @@ __global__ void __launch_bounds__(256) k_encrypt_ggsw(ChaKey K, int N, int k, in
         else m += Sc[i - N] ? wj : (u64)0;
       }
     }
-    dst[(size_t)k * N + t] =
-        body[q] + (m << sh) + (u64)tuniform(stream_word(K, TAG_GGSW_NOISE, id0 + (u64)row, (u64)t), noise_bits);
+    bdst[t] =
+        body[q] + (m << sh) + (u64)tuniform(stream_word(Kn, TAG_GGSW_NOISE, id0 + (u64)row, (u64)t), noise_bits);
+  }
+}
+
+// The key switch's balanced digits with tie coins of one document word,
+// LSB-first (digit s is level levels - 1 - s), handed to put(s, d): the one
+// digit code of the document operands here, in k_extprod_q.h and in
+// k_private_seeded.h.
+template <typename Put>
+__device__ __forceinline__ void glwe_word_digits(u64 x, int beta, int levels, Put&& put) {
+  const int prec = levels * beta;
+  const u64 half = 1ull << (beta - 1), mask = (1ull << beta) - 1;
+  u64 r = ((x >> (63 - prec)) + 1) >> 1;
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    if (s >= levels) break;
+    const u64 low = (r >> (s * beta)) & mask;
+    const u64 coin = (x >> (62 - prec - s)) & 1;
+    const int d = (low > half || (low == half && coin)) ? (int)low - (1 << beta) : (int)low;
+    r -= (u64)(int64_t)d << (s * beta);
+    put(s, d);
   }
 }
 
@@ -93,25 +119,13 @@ __global__ void __launch_bounds__(256) k_glwe_digits(const u64* __restrict__ in,
   const int i0 = blockIdx.x * 64 + iq * 4;
   if (c >= count) return;
   const u64* src = in + (size_t)c * n1;
-  const int prec = levels * beta;
-  const u64 half = 1ull << (beta - 1), mask = (1ull << beta) - 1;
   uint32_t packed[8];
 #pragma unroll
   for (int s = 0; s < 8; ++s) packed[s] = 0;
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const u64 x = src[i0 + q];
-    u64 r = ((x >> (63 - prec)) + 1) >> 1;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {  // LSB-first: digit s is level levels - 1 - s
-      if (s >= levels) break;
-      const u64 low = (r >> (s * beta)) & mask;
-      const u64 coin = (x >> (62 - prec - s)) & 1;
-      const int d = (low > half || (low == half && coin)) ? (int)low - (1 << beta) : (int)low;
-      r -= (u64)(int64_t)d << (s * beta);
-      packed[s] |= (uint32_t)(uint8_t)(int8_t)d << (8 * q);
-    }
-  }
+  for (int q = 0; q < 4; ++q)
+    glwe_word_digits(src[i0 + q], beta, levels,
+                     [&](int s, int d) { packed[s] |= (uint32_t)(uint8_t)(int8_t)d << (8 * q); });
   const int lane = cl + 16 * ((i0 >> 4) & 3);
   const int kbi = i0 >> 6, kbl = n1 >> 6;
 #pragma unroll

@@ -33,26 +33,15 @@ __global__ void __launch_bounds__(256) k_glwe_digits_rev(const u64* __restrict__
   const size_t g = blockIdx.y;
   const int c = i0 / N, m0 = i0 - c * N;
   const u64* src = in + g * n1;
-  const int prec = levels * beta;
-  const u64 half = 1ull << (beta - 1), mask = (1ull << beta) - 1;
   uint32_t pos[8], neg[8];
 #pragma unroll
   for (int s = 0; s < 8; ++s) pos[s] = neg[s] = 0;
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const u64 x = src[i0 + q];
-    u64 r = ((x >> (63 - prec)) + 1) >> 1;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {  // LSB-first: digit s is level levels - 1 - s
-      if (s >= levels) break;
-      const u64 low = (r >> (s * beta)) & mask;
-      const u64 coin = (x >> (62 - prec - s)) & 1;
-      const int d = (low > half || (low == half && coin)) ? (int)low - (1 << beta) : (int)low;
-      r -= (u64)(int64_t)d << (s * beta);
+  for (int q = 0; q < 4; ++q)
+    glwe_word_digits(src[i0 + q], beta, levels, [&](int s, int d) {
       pos[s] |= (uint32_t)(uint8_t)(int8_t)d << (8 * (3 - q));
       neg[s] |= (uint32_t)(uint8_t)(int8_t)-d << (8 * (3 - q));
-    }
-  }
+    });
   const size_t fs = xq_fstride(N);
 #pragma unroll
   for (int s = 0; s < 8; ++s) {

@@ -201,6 +201,18 @@ SIGNATURES = [
     # a group's both-private search
     ("fhe_linear_ggsws_group_batch", C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
     ("fhe_search_ggsws_group_batch", C.c_int, [_vp, _vp, _i32, _vp]),
+    # both-private search on seeded documents and queries
+    ("fhe_ggsw_body_words", C.c_size_t, [_P, _i32, _i32]),
+    ("fhe_encrypt_packed_seeded_batch", C.c_int, [_CTXP, _vp, _i64, _i32, _vp, _vp, _u64, _vp, _vp]),
+    ("fhe_encrypt_ggsw_seeded", C.c_int, [_CTXP, _vp, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp]),
+    ("fhe_expand_packed_seeded_batch", C.c_int, [_CTXP, _vp, _u64, _i64, _i32, _vp, _vp, _vp]),
+    ("fhe_expand_ggsws_seeded", C.c_int, [_CTXP, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    ("fhe_glwe_docs_pack_seeded", C.c_int, [_CTXP, _vp, _u64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    ("fhe_glwe_docs_queries_pack_seeded", C.c_int, [_CTXP, _vp, _u64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    ("fhe_search_ggsw_seeded_batch", C.c_int, [_CTXP, _vp, _u64, _i32, _i32, _vp, _vp, _i64, _i32, _i64, _i64, _i32,
+                                               _vp, _vp, _vp]),
+    ("fhe_search_ggsws_seeded_batch", C.c_int, [_CTXP, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _i64, _i32, _i64, _vp,
+                                                _i32, _vp, _vp, _vp]),
     # include/fhe_bert.h: the embedding stage's encoder (fheicp.bert)
     ("fhe_bert_create", C.c_int, [_vp, C.c_int, C.POINTER(C.c_void_p)]),
     ("fhe_bert_destroy", None, [_vp]),

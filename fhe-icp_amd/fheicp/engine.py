@@ -851,6 +851,106 @@ class Engine:
                                                  _stream(self.device)))
         return ga, gb
 
+    # ------- both-private search on seeded documents and queries (§8.15) --
+    def ggsw_body_words(self, base_log: int, level: int) -> int:
+        return self._L.fhe_ggsw_body_words(C.byref(self._P), int(base_log), int(level))
+
+    def _ids(self, id0s) -> torch.Tensor:
+        """Stream ids (python ints modulo 2^64) as a device int64 tensor."""
+        a = np.array([int(i) % (1 << 64) for i in id0s], dtype=np.uint64)
+        return torch.from_numpy(a.view(np.int64)).to(self.device)
+
+    def encrypt_docs_glwe_seeded(self, dq, mask_key, noise_key, id0: int = 0) -> torch.Tensor:
+        """encrypt_docs_glwe with a public mask key and a secret noise key:
+        the bodies alone, int64 [G, N] (fhe_encrypt_packed_seeded_batch)."""
+        m = self.to_dev(dq)
+        B, D = m.shape
+        S, G = self.doc_slots(D), self.doc_glwes(B, D)
+        rows = torch.zeros((G * S, D), dtype=torch.int64, device=self.device)
+        rows[:B] = m
+        rows = rows.reshape(G, S * D).contiguous()
+        out = torch.empty((G, self.params.N), dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_encrypt_packed_seeded_batch(self._ctx, _ptr(rows), G, S * D, self._key(mask_key),
+                                                          self._key(noise_key), C.c_uint64(int(id0) % (1 << 64)),
+                                                          _ptr(out), _stream(self.device)))
+        return out
+
+    def encrypt_ggsw_seeded(self, w, base_log: int, level: int, mask_key, noise_key, id0: int = 0) -> torch.Tensor:
+        """encrypt_ggsw's bodies alone, int64 [(k+1) level, N] (fhe_encrypt_ggsw_seeded)."""
+        wd = self.to_dev(np.asarray(w, dtype=np.int64) if not isinstance(w, torch.Tensor) else w).reshape(-1)
+        p = self.params
+        out = torch.empty(((p.k + 1) * int(level), p.N), dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_encrypt_ggsw_seeded(self._ctx, _ptr(wd), wd.numel(), int(base_log), int(level),
+                                                  self._key(mask_key), self._key(noise_key),
+                                                  C.c_uint64(int(id0) % (1 << 64)), _ptr(out), _stream(self.device)))
+        return out
+
+    def expand_docs_glwe_seeded(self, body: torch.Tensor, id0: int, mask_key) -> torch.Tensor:
+        """Seeded document bodies [G, N] -> full-form GLWEs [G, (k+1)N] (fhe_expand_packed_seeded_batch)."""
+        p = self.params
+        G = body.numel() // p.N
+        out = torch.empty((G, (p.k + 1) * p.N), dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_expand_packed_seeded_batch(self._ctx, _ptr(body), C.c_uint64(int(id0) % (1 << 64)), G,
+                                                         p.N, self._key(mask_key), _ptr(out), _stream(self.device)))
+        return out
+
+    def expand_ggsws_seeded(self, bodies: torch.Tensor, id0s, base_log: int, level: int, mask_key) -> torch.Tensor:
+        """Q seeded queries' bodies -> Q full-form GGSWs, int64 [Q, ggsw_words] (fhe_expand_ggsws_seeded)."""
+        ids = self._ids(id0s)
+        Q = ids.numel()
+        bw = self.ggsw_body_words(base_log, level)
+        if bw == 0 or bodies.numel() != Q * bw:
+            raise ValueError(f"{bodies.numel()} words are not the bodies of {Q} GGSWs of gadget ({base_log}, {level})")
+        out = torch.empty((Q, self.ggsw_words(base_log, level)), dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_expand_ggsws_seeded(self._ctx, _ptr(bodies), _ptr(ids), Q, int(base_log), int(level),
+                                                  self._key(mask_key), _ptr(out), _stream(self.device)))
+        return out
+
+    def pack_docs_glwe_seeded(self, body: torch.Tensor, id0: int, mask_key, B: int, D: int, base_log: int,
+                              level: int, queries: bool = False) -> torch.Tensor:
+        """pack_docs_glwe (queries=True: pack_docs_glwe_queries) straight from
+        seeded bodies: the same operand byte for byte, the masks regenerated
+        in registers (fhe_glwe_docs_pack_seeded, fhe_glwe_docs_queries_pack_seeded)."""
+        size = self._L.fhe_glwe_docs_queries_bytes if queries else self._L.fhe_glwe_docs_bytes
+        pack = self._L.fhe_glwe_docs_queries_pack_seeded if queries else self._L.fhe_glwe_docs_pack_seeded
+        if body.numel() != self.doc_glwes(B, D) * self.params.N:
+            raise ValueError(f"{body.numel()} body words for {self.doc_glwes(B, D)} document GLWEs")
+        docs = torch.empty(size(C.byref(self._P), int(B), int(D), int(level)), dtype=torch.uint8, device=self.device)
+        self._chk(pack(self._ctx, _ptr(body), C.c_uint64(int(id0) % (1 << 64)), int(B), int(D), int(base_log),
+                       int(level), self._key(mask_key), _ptr(docs), _stream(self.device)))
+        return docs
+
+    def search_ggsw_seeded(self, body: torch.Tensor, id0: int, mask_key, base_log: int, level: int,
+                           docs8: torch.Tensor, B: int, D: int, cst: int, T: int, levels_bit: int = 0):
+        """search_ggsw on one seeded query (fhe_search_ggsw_seeded_batch)."""
+        shape = (self.glwe_count(B), (self.params.k + 1) * self.params.N)
+        ga = torch.empty(shape, dtype=torch.int64, device=self.device)
+        gb = torch.empty(shape, dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_search_ggsw_seeded_batch(self._ctx, _ptr(body), C.c_uint64(int(id0) % (1 << 64)),
+                                                       int(base_log), int(level), self._key(mask_key), _ptr(docs8),
+                                                       int(B), int(D), int(cst), int(T), int(levels_bit), _ptr(ga),
+                                                       _ptr(gb), _stream(self.device)))
+        return ga, gb
+
+    def search_ggsws_seeded(self, bodies: torch.Tensor, id0s, mask_key, base_log: int, level: int,
+                            docs: torch.Tensor, B: int, D: int, cst: int, Ts, levels_bit: int = 0):
+        """search_ggsws on Q seeded queries (fhe_search_ggsws_seeded_batch)."""
+        ids = self._ids(id0s)
+        Q = ids.numel()
+        keep, hT = self._i64s(Ts)
+        if keep.size != Q:
+            raise ValueError(f"{keep.size} thresholds for {Q} queries")
+        if bodies.numel() != Q * self.ggsw_body_words(base_log, level):
+            raise ValueError(f"{bodies.numel()} words are not the bodies of {Q} GGSWs of gadget ({base_log}, {level})")
+        shape = (self.glwe_count(Q * B), (self.params.k + 1) * self.params.N)
+        ga = torch.empty(shape, dtype=torch.int64, device=self.device)
+        gb = torch.empty(shape, dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_search_ggsws_seeded_batch(self._ctx, _ptr(bodies), _ptr(ids), int(base_log), int(level),
+                                                        self._key(mask_key), _ptr(docs), Q, int(B), int(D), int(cst),
+                                                        hT, int(levels_bit), _ptr(ga), _ptr(gb),
+                                                        _stream(self.device)))
+        return ga, gb
+
     def topk(self, acc: torch.Tensor, below: torch.Tensor | None, k: int, base_idx: int = 0):
         oa = torch.empty(k, dtype=torch.int64, device=self.device)
         oi = torch.empty(k, dtype=torch.int64, device=self.device)

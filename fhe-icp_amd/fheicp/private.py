@@ -31,6 +31,19 @@ Query payload (uint64 vector):
      GGSW words [c][l][component][coef]]
 Document block (uint64 vector):
     [DOCS_MAGIC, 1, B, D, P0, N | k << 32, ceil(B / (N // D)) GLWEs of (k+1)N words]
+
+Seeded payloads (``PrivateClient(..., seeded=True)``): the
+body polynomials alone, a third of the full forms; the masks are ChaCha20
+streams under the PUBLIC mask key in the payload (4 words = 32 bytes), the
+noise came from the client's secret key. GLWE g of a block takes stream id
+id0 + g, GGSW row r = c level + l, component c', id0 + r k + c'. An id must not
+repeat under one mask key.
+Seeded query payload (uint64 vector):
+    [SEEDED_QUERY_MAGIC, 1, D, P0, base_log | level << 32, N | k << 32, id0, mask key (4 words),
+     (k+1) level bodies of N words [c][l][coef]]
+Seeded document block (uint64 vector):
+    [SEEDED_DOCS_MAGIC, 1, B, D, P0, N | k << 32, id0, mask key (4 words),
+     ceil(B / (N // D)) bodies of N words]
 """
 from __future__ import annotations
 
@@ -116,6 +129,118 @@ def unpack_doc_block(arr) -> dict:
     return {"B": B, "D": D, "P0": int(a[4]), "N": N, "k": k, "glwe": a[HEADER_WORDS:].copy()}
 
 
+# ------------------------------------------------ seeded payloads (§8.15) --
+SEEDED_QUERY_MAGIC = int.from_bytes(b"FHEICPSQ", "little")
+SEEDED_DOCS_MAGIC = int.from_bytes(b"FHEICPSD", "little")
+SEEDED_HEADER_WORDS = HEADER_WORDS + 1 + 4       # the v1 header, id0, the mask key
+
+
+def _mask_key_words(mask_key) -> np.ndarray:
+    """A 32-byte mask key (bytes or 8 uint32 words) as the payload's 4 uint64 words."""
+    if isinstance(mask_key, (bytes, bytearray)):
+        mask_key = np.frombuffer(bytes(mask_key), dtype="<u4")
+    k = np.ascontiguousarray(mask_key, dtype=np.uint32).reshape(-1)
+    if k.size != 8:
+        raise ValueError("a mask key is 32 bytes")
+    return k.view(np.uint64).copy()
+
+
+def pack_ggsw_query_seeded(body, id0: int, mask_key, D: int, P0: int, base_log: int, level: int, N: int,
+                           k: int) -> np.ndarray:
+    b = np.asarray(body, dtype=np.uint64).reshape(-1)
+    head = np.array([SEEDED_QUERY_MAGIC, 1, D, P0, int(base_log) | (int(level) << 32), int(N) | (int(k) << 32),
+                     int(id0) % (1 << 64)], np.uint64)
+    return np.concatenate([head, _mask_key_words(mask_key), b])
+
+
+def _seeded_head(arr, magic: int, what: str) -> np.ndarray:
+    a = np.asarray(arr)
+    if a.dtype != np.uint64 or a.ndim != 1 or a.size < SEEDED_HEADER_WORDS or int(a[0]) != magic:
+        raise ValueError(f"not an fheicp seeded {what}")
+    if int(a[1]) != 1:
+        raise ValueError(f"unsupported seeded {what} version {int(a[1])}")
+    return a
+
+
+def unpack_ggsw_query_seeded(arr) -> dict:
+    a = _seeded_head(arr, SEEDED_QUERY_MAGIC, "GGSW query payload")
+    base_log, level = int(a[4]) & 0xFFFFFFFF, int(a[4]) >> 32
+    N, k = int(a[5]) & 0xFFFFFFFF, int(a[5]) >> 32
+    D = int(a[2])
+    if not 0 < D <= N:
+        raise ValueError(f"seeded GGSW query of D = {D} features does not fit one GLWE (N = {N})")
+    if a.size != SEEDED_HEADER_WORDS + (k + 1) * level * N:
+        raise ValueError("seeded GGSW query payload size does not match its gadget and parameters")
+    return {"seeded": True, "D": D, "P0": int(a[3]), "base_log": base_log, "level": level, "N": N, "k": k,
+            "id0": int(a[6]), "mask_key": a[7:11].copy().view(np.uint32), "body": a[SEEDED_HEADER_WORDS:].copy()}
+
+
+def pack_doc_block_seeded(body, id0: int, mask_key, B: int, D: int, P0: int, N: int, k: int) -> np.ndarray:
+    b = np.asarray(body, dtype=np.uint64).reshape(-1)
+    head = np.array([SEEDED_DOCS_MAGIC, 1, B, D, P0, int(N) | (int(k) << 32), int(id0) % (1 << 64)], np.uint64)
+    return np.concatenate([head, _mask_key_words(mask_key), b])
+
+
+def unpack_doc_block_seeded(arr) -> dict:
+    a = _seeded_head(arr, SEEDED_DOCS_MAGIC, "GLWE document block")
+    B, D = int(a[2]), int(a[3])
+    N, k = int(a[5]) & 0xFFFFFFFF, int(a[5]) >> 32
+    if not 0 < D <= N:
+        raise ValueError(f"seeded document block of D = {D} features does not fit one GLWE (N = {N})")
+    if a.size != SEEDED_HEADER_WORDS + -(-B // (N // D)) * N:
+        raise ValueError("seeded document block size does not match its document count")
+    return {"seeded": True, "B": B, "D": D, "P0": int(a[4]), "N": N, "k": k, "id0": int(a[6]),
+            "mask_key": a[7:11].copy().view(np.uint32), "body": a[SEEDED_HEADER_WORDS:].copy()}
+
+
+def _is_seeded(arr, magic: int) -> bool:
+    a = np.asarray(arr)
+    return a.dtype == np.uint64 and a.ndim == 1 and a.size > 0 and int(a[0]) == magic
+
+
+def unpack_any_query(arr) -> dict:
+    """A query payload of either form, dispatched on the magic; "seeded" says which."""
+    if _is_seeded(arr, SEEDED_QUERY_MAGIC):
+        return unpack_ggsw_query_seeded(arr)
+    return dict(unpack_ggsw_query(arr), seeded=False)
+
+
+def unpack_any_docs(arr) -> dict:
+    """A document block of either form, dispatched on the magic; "seeded" says which."""
+    if _is_seeded(arr, SEEDED_DOCS_MAGIC):
+        return unpack_doc_block_seeded(arr)
+    return dict(unpack_doc_block(arr), seeded=False)
+
+
+def id_ranges_overlap(a0: int, an: int, b0: int, bn: int) -> bool:
+    """Whether [a0, a0 + an) and [b0, b0 + bn) meet modulo 2^64 (lengths below 2^64)."""
+    M = 1 << 64
+    return an > 0 and bn > 0 and ((int(b0) - int(a0)) % M < an or (int(a0) - int(b0)) % M < bn)
+
+
+def check_query_batch(pls) -> bool:
+    """check_ggsw_batch for unpacked payloads of either form; returns whether
+    the batch is seeded. One form per batch; seeded queries share one mask key
+    and their id ranges [id0, id0 + ggsw_id_span) are disjoint modulo 2^64
+    (an id must not repeat under one mask key). ValueError names the query."""
+    check_ggsw_batch(pls)
+    first = pls[0]
+    for i, pl in enumerate(pls[1:], 1):
+        if pl["seeded"] != first["seeded"]:
+            raise ValueError(f"query {i}: {'a seeded' if pl['seeded'] else 'a full-form'} payload in a batch of "
+                             f"{'seeded' if first['seeded'] else 'full-form'} ones")
+    if not first["seeded"]:
+        return False
+    span = ggsw_id_span(first["k"], first["level"])
+    for i, pl in enumerate(pls):
+        if i and not np.array_equal(pl["mask_key"], first["mask_key"]):
+            raise ValueError(f"query {i}: mask key differs from query 0's")
+        for j in range(i):
+            if id_ranges_overlap(pls[j]["id0"], span, pl["id0"], span):
+                raise ValueError(f"query {i}: stream ids [{pl['id0']}, +{span}) overlap query {j}'s under one mask key")
+    return True
+
+
 def worst_norm2(cq) -> float:
     """The squared query norm the gadget is planned for, over every query
     (|qq_j| <= 2^(n_e - 1)). The model of params.extprod_var takes the
@@ -145,8 +270,13 @@ class PrivateClient(QueryClient):
     evaluation keys, decrypts replies (QueryClient's). Owns the secret context
     of a compiled EncryptedCorpus."""
 
-    def __init__(self, corpus: EncryptedCorpus, count: int = 1024, pack_seed=None, enc_seed: int | None = None):
-        """enc_seed: the 64-bit test form of the session's encryption key."""
+    def __init__(self, corpus: EncryptedCorpus, count: int = 1024, pack_seed=None, enc_seed: int | None = None,
+                 seeded: bool = False, mask_seed: int | None = None):
+        """enc_seed: the 64-bit test form of the session's encryption key.
+        seeded: encrypt_docs / encrypt_query / encrypt_queries emit the seeded
+        payloads of DESIGN.md §8.15: masks from the client's own fresh PUBLIC
+        mask key (mask_seed: its 64-bit test form), which travels in every
+        payload, noise from the secret encryption key, which does not."""
         from .params import extprod_var
         corpus._need()
         scheme = corpus.scheme.with_msg_bits(corpus.P0)
@@ -158,6 +288,11 @@ class PrivateClient(QueryClient):
         self.base_log, self.level = self.gadget
         self._enc_key = (np.frombuffer(os.urandom(32), np.uint32).copy() if enc_seed is None
                          else corpus.engine.key_from_seed(enc_seed))
+        self.seeded = bool(seeded)
+        self._mask_key = (np.frombuffer(os.urandom(32), np.uint32).copy() if mask_seed is None
+                          else corpus.engine.key_from_seed(mask_seed))
+        if self.seeded and np.array_equal(self._mask_key, self._enc_key):
+            raise ValueError("the public mask key must differ from the secret encryption key")
 
     def _ids(self, id0):
         return int.from_bytes(os.urandom(8), "little") if id0 is None else int(id0)
@@ -170,27 +305,43 @@ class PrivateClient(QueryClient):
         B, D = docs.shape
         eng.set_msg_bits(self.P0)
         dq = eng.quantize(torch.from_numpy(docs).to(eng.device), self.cq.s_e, 0, self.cq.qmin, self.cq.qmax)
+        if self.seeded:
+            i = self._ids(id0)
+            body = eng.encrypt_docs_glwe_seeded(dq, self._mask_key, self._enc_key, i)
+            return pack_doc_block_seeded(body.cpu().numpy().view(np.uint64), i, self._mask_key, B, D, self.P0,
+                                         eng.params.N, eng.params.k)
         glwe = eng.encrypt_docs_glwe(dq, self._enc_key, self._ids(id0))
         return pack_doc_block(glwe.cpu().numpy().view(np.uint64), B, D, self.P0, eng.params.N, eng.params.k)
 
     def decrypt_docs(self, block) -> np.ndarray:
-        """The quantized documents of a block (the key holder's view; tests)."""
+        """The quantized documents of a block of either form (the key holder's view; tests)."""
         eng = self.corpus.engine
-        bl = unpack_doc_block(block)
+        bl = unpack_any_docs(block)
         eng.set_msg_bits(self.P0)
         S = bl["N"] // bl["D"]
         G = -(-bl["B"] // S)
-        v = eng.decrypt_packed(eng.to_dev(bl["glwe"]), G * bl["N"], 0).cpu().numpy().reshape(G, bl["N"])
+        glwe = (eng.expand_docs_glwe_seeded(eng.to_dev(bl["body"]), bl["id0"], bl["mask_key"]) if bl["seeded"]
+                else eng.to_dev(bl["glwe"]))
+        v = eng.decrypt_packed(glwe, G * bl["N"], 0).cpu().numpy().reshape(G, bl["N"])
         return v[:, :S * bl["D"]].reshape(G * S, bl["D"])[:bl["B"]]
+
+    def _encrypt_w(self, W, i: int) -> np.ndarray:
+        """The payload of one weight vector under stream id i, in the client's form."""
+        eng = self.corpus.engine
+        if self.seeded:
+            b = eng.encrypt_ggsw_seeded(W, self.base_log, self.level, self._mask_key, self._enc_key, i)
+            return pack_ggsw_query_seeded(b.cpu().numpy().view(np.uint64), i, self._mask_key, len(W), self.P0,
+                                          self.base_log, self.level, eng.params.N, eng.params.k)
+        g = eng.encrypt_ggsw(W, self.base_log, self.level, self._enc_key, i)
+        return pack_ggsw_query(g.cpu().numpy().view(np.uint64), len(W), self.P0, self.base_log, self.level,
+                               eng.params.N, eng.params.k)
 
     def encrypt_query(self, q, id0: int | None = None) -> np.ndarray:
         """A reduced query vector -> the GGSW payload sent to the server."""
         eng = self.corpus.engine
         W = self.cq.weights(self.cq.quant(np.asarray(q).reshape(-1)))
         eng.set_msg_bits(self.P0)
-        g = eng.encrypt_ggsw(W, self.base_log, self.level, self._enc_key, self._ids(id0))
-        return pack_ggsw_query(g.cpu().numpy().view(np.uint64), len(W), self.P0, self.base_log, self.level,
-                               eng.params.N, eng.params.k)
+        return self._encrypt_w(W, self._ids(id0))
 
     def encrypt_queries(self, vectors, id0: int | None = None) -> list:
         """Q reduced query vectors [Q, D] -> Q GGSW payloads. One random id0;
@@ -201,13 +352,7 @@ class PrivateClient(QueryClient):
         qq = self.cq.quant(np.atleast_2d(np.asarray(vectors)))
         ids = ggsw_query_ids(self._ids(id0), len(qq), eng.params.k, self.level)
         eng.set_msg_bits(self.P0)
-        out = []
-        for q, i in zip(qq, ids):
-            W = self.cq.weights(q)
-            g = eng.encrypt_ggsw(W, self.base_log, self.level, self._enc_key, i)
-            out.append(pack_ggsw_query(g.cpu().numpy().view(np.uint64), len(W), self.P0, self.base_log, self.level,
-                                       eng.params.N, eng.params.k))
-        return out
+        return [self._encrypt_w(self.cq.weights(q), i) for q, i in zip(qq, ids)]
 
 
 class PrivateServer(QueryServer):
@@ -216,6 +361,36 @@ class PrivateServer(QueryServer):
     def __init__(self, eval_keys: dict, cq, P0: int, device: int = 0, scheme=None):
         super().__init__(eval_keys, cq, P0, device, scheme)
         self.base_log, self.level = plan_gadget(self.scheme, cq)
+        self._seeded_docs = {}      # mask key bytes -> [(id0, GLWEs, end words)] of the seeded blocks packed so far
+
+    def _note_seeded_docs(self, bl: dict) -> None:
+        """An id must not repeat under one mask key: a seeded block whose ids
+        [id0, id0 + G) meet those of ANOTHER block packed under the same mask
+        key is refused (the same block packed again, for the other operand,
+        is the same ciphertexts and passes). A courtesy of the host, not the
+        defence: the client owns its ids."""
+        G = -(-bl["B"] // (bl["N"] // bl["D"]))
+        # the block's first and last body words tell it from another block (bodies are pseudorandom)
+        rec = (bl["id0"], G, bl["body"][:4].tobytes() + bl["body"][-4:].tobytes())
+        seen = self._seeded_docs.setdefault(bl["mask_key"].tobytes(), [])
+        if rec in seen:
+            return
+        for id0, n, _ in seen:
+            if id_ranges_overlap(id0, n, rec[0], G):
+                raise ValueError(f"document block: stream ids [{rec[0]}, +{G}) overlap those of a block already "
+                                 f"packed under the same mask key ([{id0}, +{n}))")
+        seen.append(rec)
+
+    def _docs_operand(self, block, queries: bool):
+        bl = unpack_any_docs(block)
+        self._check(bl, "document block")
+        eng = self.engine
+        if bl["seeded"]:
+            self._note_seeded_docs(bl)
+            return eng.pack_docs_glwe_seeded(eng.to_dev(bl["body"]), bl["id0"], bl["mask_key"], bl["B"], bl["D"],
+                                             self.base_log, self.level, queries=queries), bl["B"]
+        pack = eng.pack_docs_glwe_queries if queries else eng.pack_docs_glwe
+        return pack(eng.to_dev(bl["glwe"]), bl["B"], bl["D"], self.base_log, self.level), bl["B"]
 
     def _check(self, pl: dict, what: str) -> None:
         if pl["P0"] != self.P0 or pl["N"] != self.scheme.N or pl["k"] != self.scheme.k:
@@ -224,43 +399,45 @@ class PrivateServer(QueryServer):
             raise ValueError(f"{what} holds {pl['D']} features, the model {len(self.cq.model.q_w)}")
 
     def pack_docs(self, block):
-        """A document block -> (the device-resident digit operand, B)."""
-        bl = unpack_doc_block(block)
-        self._check(bl, "document block")
-        eng = self.engine
-        return eng.pack_docs_glwe(eng.to_dev(bl["glwe"]), bl["B"], bl["D"], self.base_log, self.level), bl["B"]
+        """A document block of either form -> (the device-resident digit
+        operand, B). A seeded block is never expanded: the operand is made
+        from its bodies (fhe_glwe_docs_pack_seeded)."""
+        return self._docs_operand(block, False)
 
     def search(self, payload, docs8, B: int, min_similarity: float | None) -> np.ndarray:
         """One GGSW query against B packed encrypted documents -> the reply."""
         eng = self.engine
-        pl = unpack_ggsw_query(payload)
+        pl = unpack_any_query(payload)
         self._check(pl, "query")
         if (pl["base_log"], pl["level"]) != (self.base_log, self.level):
             raise ValueError("query gadget differs from the one the documents were packed for")
         _, cst, T = self.plan(min_similarity)
-        ga, gb = eng.search_ggsw(eng.to_dev(pl["ggsw"]), self.base_log, self.level, docs8, int(B), pl["D"], cst, T,
-                                 self.bit_levels)
+        if pl["seeded"]:
+            ga, gb = eng.search_ggsw_seeded(eng.to_dev(pl["body"]), pl["id0"], pl["mask_key"], self.base_log,
+                                            self.level, docs8, int(B), pl["D"], cst, T, self.bit_levels)
+        else:
+            ga, gb = eng.search_ggsw(eng.to_dev(pl["ggsw"]), self.base_log, self.level, docs8, int(B), pl["D"], cst,
+                                     T, self.bit_levels)
         return pack_reply(ga.cpu().numpy().view(np.uint64), gb.cpu().numpy().view(np.uint64), B, self.P0, T)
 
     # -------------------------------------------------- batches of queries --
     def pack_docs_many(self, block):
-        """A document block -> (the device-resident operand of search_many, B)."""
-        bl = unpack_doc_block(block)
-        self._check(bl, "document block")
-        eng = self.engine
-        return eng.pack_docs_glwe_queries(eng.to_dev(bl["glwe"]), bl["B"], bl["D"], self.base_log,
-                                          self.level), bl["B"]
+        """A document block of either form -> (the device-resident operand of
+        search_many, B); seeded blocks as in pack_docs
+        (fhe_glwe_docs_queries_pack_seeded)."""
+        return self._docs_operand(block, True)
 
     def search_many(self, payloads, docs, B: int, min_similarity=None) -> list:
-        """Q GGSW queries of one key holder against B encrypted documents
+        """Q GGSW queries of one key holder, all full form or all seeded
+        (check_query_batch), against B encrypted documents
         packed by pack_docs_many, in one pass (fhe_search_ggsws_batch) -> a
         LIST of version-2 replies (query.pack_replies), one per chunk of
         query_chunks(Q, B). min_similarity: a float, None, or a sequence of Q
         of them. QueryClient.decrypt_replies takes the list."""
         from .query import pack_replies, query_chunks, thresholds_for
         eng = self.engine
-        pls = [unpack_ggsw_query(p) for p in payloads]
-        check_ggsw_batch(pls)
+        pls = [unpack_any_query(p) for p in payloads]
+        seeded = check_query_batch(pls)
         self._check(pls[0], "query 0")
         if (pls[0]["base_log"], pls[0]["level"]) != (self.base_log, self.level):
             raise ValueError("query 0: gadget differs from the one the documents were packed for")
@@ -269,9 +446,14 @@ class PrivateServer(QueryServer):
         Ts = [self.plan(t)[2] for t in thresholds_for(min_similarity, Q)]
         out = []
         for ch in query_chunks(Q, int(B)):
-            g = eng.to_dev(np.concatenate([pls[q]["ggsw"] for q in ch]))
             Tc = [Ts[q] for q in ch]
-            ga, gb = eng.search_ggsws(g, self.base_log, self.level, docs, int(B), D, cst, Tc, self.bit_levels)
+            if seeded:
+                b = eng.to_dev(np.concatenate([pls[q]["body"] for q in ch]))
+                ga, gb = eng.search_ggsws_seeded(b, [pls[q]["id0"] for q in ch], pls[0]["mask_key"], self.base_log,
+                                                 self.level, docs, int(B), D, cst, Tc, self.bit_levels)
+            else:
+                g = eng.to_dev(np.concatenate([pls[q]["ggsw"] for q in ch]))
+                ga, gb = eng.search_ggsws(g, self.base_log, self.level, docs, int(B), D, cst, Tc, self.bit_levels)
             out.append(pack_replies(ga.cpu().numpy().view(np.uint64), gb.cpu().numpy().view(np.uint64), B, self.P0,
                                     Tc))
         return out
@@ -306,7 +488,8 @@ def private_hub_chunks(sizes: dict, cap: int | None = None) -> list:
 
 class PrivateHub:
     """Tenants with their own keys and their own encrypted documents behind
-    one GPU. The host learns which tenant asked, Q and B; documents, queries
+    one GPU; each tenant's blocks and queries in either form, full or seeded
+    (DESIGN.md §8.15), mixed freely between tenants of one call. The host learns which tenant asked, Q and B; documents, queries
     and results stay under each tenant's own key."""
 
     def __init__(self, device: int = 0):
@@ -389,8 +572,8 @@ class PrivateHub:
             if rec["docs"] is None:
                 raise ValueError(f"tenant {name!r} has no documents loaded")
             try:
-                pls = [unpack_ggsw_query(p) for p in payloads]
-                check_ggsw_batch(pls)
+                pls = [unpack_any_query(p) for p in payloads]
+                check_query_batch(pls)
                 s._check(pls[0], "query 0")
                 if (pls[0]["base_log"], pls[0]["level"]) != (s.base_log, s.level):
                     raise ValueError("query 0: gadget differs from the one the documents were packed for")
@@ -424,7 +607,12 @@ class PrivateHub:
             for name, rng in chunk:
                 rec, pn = self.tenants[name], plan[name]
                 s, pls = rec["server"], pn["pls"]
-                g = s.engine.to_dev(np.concatenate([pls[q]["ggsw"] for q in rng]))
+                if pls[0]["seeded"]:    # expanded on the tenant's own context; the group entry takes full forms
+                    b = s.engine.to_dev(np.concatenate([pls[q]["body"] for q in rng]))
+                    g = s.engine.expand_ggsws_seeded(b, [pls[q]["id0"] for q in rng], s.base_log, s.level,
+                                                     pls[0]["mask_key"])
+                else:
+                    g = s.engine.to_dev(np.concatenate([pls[q]["ggsw"] for q in rng]))
                 Tcs[name] = [pn["Ts"][q] for q in rng]
                 items[names.index(name)] = (g, s.base_log, s.level, rec["docs"], rec["B"], pls[0]["D"], pn["cst"],
                                             Tcs[name], s.bit_levels)

@@ -904,6 +904,69 @@ int fhe_linear_ggsws_group_batch(fhe_group* group, const fhe_group_ggsw* items, 
  * levels_bit), then the device, then FHE_E_STATE (no packing key). All tenants
  * with Q = 0 returns FHE_OK. */
 int fhe_search_ggsws_group_batch(fhe_group* group, const fhe_group_ggsw* items, int32_t T, void* stream);
+
+/* ---- both-private search: seeded documents and queries ----
+ * In a document GLWE and in every GGSW row, k of the k+1 polynomials are
+ * uniform masks. The seeded forms keep the body polynomial alone: the masks
+ * are words of ChaCha20 streams under a PUBLIC mask key that travels with the
+ * payload, the noise comes from a SECRET noise key that never leaves the
+ * client. Tags, stream ids and word addressing are the full forms':
+ *   document GLWE g, component i < k:  word iN + t of (tag 7, id0 + g),
+ *   GGSW row r = cL + l, component c': word t of (tag 31, id0 + r k + c'),
+ * so with mask key = noise key = K the expansion of a seeded ciphertext is,
+ * word for word, the full-form ciphertext under K (tests only: a deployment
+ * never sets the two equal). An id must not repeat under one mask key.
+ * A seeded document GLWE is N words instead of (k+1)N, a seeded GGSW
+ * fhe_ggsw_body_words = (k+1) L N instead of fhe_ggsw_words (0 for a null
+ * params or a bad gadget).
+ *
+ * Argument errors (null pointers or keys, D > N, a bad gadget, Q or B outside
+ * the full-form sibling's range) return FHE_E_ARG with "seeded" in
+ * fhe_last_error and come first, on host-only contexts too; then the device
+ * (FHE_E_DEVICE), then missing keys (FHE_E_STATE). */
+size_t fhe_ggsw_body_words(const fhe_params* params, int32_t base_log, int32_t level);
+/* fhe_encrypt_packed_batch_key / fhe_encrypt_ggsw_key with the key split in
+ * two and the bodies alone as output: d_body B x ceil(D / N) x N words, and
+ * (k+1) L x N words [c][l][coef]. Both need the secret key. */
+int fhe_encrypt_packed_seeded_batch(fhe_ctx* ctx, const int64_t* d_qx, int64_t B, int32_t D,
+                                    const uint32_t h_mask_key[8], const uint32_t h_noise_key[8], uint64_t id0,
+                                    uint64_t* d_body, void* stream);
+int fhe_encrypt_ggsw_seeded(fhe_ctx* ctx, const int64_t* d_w, int32_t D, int32_t base_log, int32_t level,
+                            const uint32_t h_mask_key[8], const uint32_t h_noise_key[8], uint64_t id0,
+                            uint64_t* d_body, void* stream);
+/* Bodies -> full form (k_expand_ggsw_seeded); no keys needed. Documents:
+ * B x ceil(D / N) GLWEs of (k+1)N words, GLWE g under stream id id0 + g.
+ * Queries: d_body Q x fhe_ggsw_body_words, d_id0 Q stream ids (device),
+ * d_ggsw Q x fhe_ggsw_words; 1 <= Q <= 65535. Timing goes to the
+ * "expand_ggsw_seeded" profile bucket. */
+int fhe_expand_packed_seeded_batch(fhe_ctx* ctx, const uint64_t* d_body, uint64_t id0, int64_t B, int32_t D,
+                                   const uint32_t h_mask_key[8], uint64_t* d_glwe, void* stream);
+int fhe_expand_ggsws_seeded(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t Q, int32_t base_log,
+                            int32_t level, const uint32_t h_mask_key[8], uint64_t* d_ggsw, void* stream);
+/* fhe_glwe_docs_pack / fhe_glwe_docs_queries_pack from seeded documents:
+ * d_body ceil(B / (N / D)) x N body words, document GLWE g under stream id
+ * id0 + g. The operands (fhe_glwe_docs_bytes, fhe_glwe_docs_queries_bytes) are
+ * byte for byte those of the full-form entries on the expanded GLWEs; the
+ * masks are regenerated in registers, no full-form GLWE exists on host or
+ * device. (k+1)N a multiple of 128. No keys needed. */
+int fhe_glwe_docs_pack_seeded(fhe_ctx* ctx, const uint64_t* d_body, uint64_t id0, int64_t B, int32_t D,
+                              int32_t base_log, int32_t level, const uint32_t h_mask_key[8], void* d_docs8,
+                              void* stream);
+int fhe_glwe_docs_queries_pack_seeded(fhe_ctx* ctx, const uint64_t* d_body, uint64_t id0, int64_t B, int32_t D,
+                                      int32_t base_log, int32_t level, const uint32_t h_mask_key[8], void* d_docs,
+                                      void* stream);
+/* fhe_search_ggsw_batch / fhe_search_ggsws_batch on seeded queries: the
+ * queries are expanded into a context-owned workspace (Q x fhe_ggsw_words,
+ * allocated on first use), then the full-form entry runs unchanged; the
+ * outputs are those of the full-form entry on the expanded queries. */
+int fhe_search_ggsw_seeded_batch(fhe_ctx* ctx, const uint64_t* d_body, uint64_t id0, int32_t base_log, int32_t level,
+                                 const uint32_t h_mask_key[8], const void* d_docs8, int64_t B, int32_t D, int64_t cst,
+                                 int64_t T, int32_t levels_bit, uint64_t* d_glwe_acc, uint64_t* d_glwe_bit,
+                                 void* stream);
+int fhe_search_ggsws_seeded_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int32_t base_log,
+                                  int32_t level, const uint32_t h_mask_key[8], const void* d_docs, int64_t Q,
+                                  int64_t B, int32_t D, int64_t cst, const int64_t* h_T, int32_t levels_bit,
+                                  uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,18 @@ _PROTOS = {
     "fhe_compare_ggsws_batch": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
     "fhe_search_ggsws_batch": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _i64, _i32, _i64, _vp, _i32, _vp, _vp,
                                          _vp]),
+    # both sides encrypted, seeded documents and queries
+    "fhe_ggsw_body_words": (C.c_size_t, [C.POINTER(fhe_params), _i32, _i32]),
+    "fhe_encrypt_packed_seeded_batch": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _u64, _vp, _vp]),
+    "fhe_encrypt_ggsw_seeded": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp]),
+    "fhe_expand_packed_seeded_batch": (C.c_int, [_vp, _vp, _u64, _i64, _i32, _vp, _vp, _vp]),
+    "fhe_expand_ggsws_seeded": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "fhe_glwe_docs_pack_seeded": (C.c_int, [_vp, _vp, _u64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "fhe_glwe_docs_queries_pack_seeded": (C.c_int, [_vp, _vp, _u64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "fhe_search_ggsw_seeded_batch": (C.c_int, [_vp, _vp, _u64, _i32, _i32, _vp, _vp, _i64, _i32, _i64, _i64, _i32,
+                                               _vp, _vp, _vp]),
+    "fhe_search_ggsws_seeded_batch": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _i64, _i32, _i64, _vp,
+                                                _i32, _vp, _vp, _vp]),
 }
 
 
@@ -488,6 +500,128 @@ class GpuCompare:
             self._ok(self.L.fhe_search_ggsws_batch(self.ctx, bufs[0], base_log, level, d, Q, B, D, int(cst),
                                                    hT.ctypes.data, int(levels_bit), bufs[1], bufs[2], None))
             return self._to_host(bufs[1], words).view(np.uint64), self._to_host(bufs[2], words).view(np.uint64)
+        finally:
+            for b in bufs:
+                self.L.fhe_dev_free(self.ctx, b)
+
+    # ---- seeded documents and queries ----------------------
+    # mask_key: PUBLIC, travels with the payload; noise_key: SECRET, stays with
+    # the key holder (both 8 u32 words, e.g. _key32()); never the same key.
+    @staticmethod
+    def _k8(key) -> C.Array:
+        return (C.c_uint32 * 8)(*[int(x) for x in np.asarray(key, np.uint32).reshape(8)])
+
+    def encrypt_docs_glwe_seeded(self, dq: np.ndarray, mask_key, noise_key, id0: int | None = None):
+        """Key holder: quantized documents (int64 [B, D]) -> (bodies uint64
+        [G N], id0): N words per document GLWE instead of (k+1) N."""
+        dq = np.asarray(dq, np.int64)
+        B, D = dq.shape
+        S = self.P.N // D
+        G = -(-B // S)
+        rows = np.zeros((G * S, D), np.int64)
+        rows[:B] = dq
+        bufs = [self._to_dev(rows), self._alloc(8 * G * self.P.N)]
+        try:
+            id0 = self._take_ids(G) if id0 is None else int(id0)
+            self._ok(self.L.fhe_encrypt_packed_seeded_batch(self.ctx, bufs[0], G, S * D, self._k8(mask_key),
+                                                            self._k8(noise_key), id0, bufs[1], None))
+            return self._to_host(bufs[1], G * self.P.N).view(np.uint64), id0
+        finally:
+            for d in bufs:
+                self.L.fhe_dev_free(self.ctx, d)
+
+    def encrypt_ggsw_seeded(self, W: np.ndarray, base_log: int, level: int, mask_key, noise_key,
+                            id0: int | None = None):
+        """Key holder: W (int64 [D]) -> (bodies uint64 [fhe_ggsw_body_words], id0)."""
+        W = np.asarray(W, np.int64).reshape(-1)
+        words = self.L.fhe_ggsw_body_words(C.byref(self.P), base_log, level)
+        bufs = [self._to_dev(W), self._alloc(8 * words)]
+        try:
+            id0 = self._take_ids((self.P.k + 1) * level * self.P.k) if id0 is None else int(id0)
+            self._ok(self.L.fhe_encrypt_ggsw_seeded(self.ctx, bufs[0], W.size, base_log, level, self._k8(mask_key),
+                                                    self._k8(noise_key), id0, bufs[1], None))
+            return self._to_host(bufs[1], words).view(np.uint64), id0
+        finally:
+            for d in bufs:
+                self.L.fhe_dev_free(self.ctx, d)
+
+    def expand_docs_glwe_seeded(self, bodies, id0: int, mask_key) -> np.ndarray:
+        """Bodies -> the full-form document GLWEs (interop; fhe_expand_packed_seeded_batch)."""
+        b = np.ascontiguousarray(bodies, np.uint64).reshape(-1)
+        G, words = b.size // self.P.N, b.size * (self.P.k + 1)
+        bufs = [self._to_dev(b), self._alloc(8 * words)]
+        try:
+            self._ok(self.L.fhe_expand_packed_seeded_batch(self.ctx, bufs[0], int(id0), G, self.P.N,
+                                                           self._k8(mask_key), bufs[1], None))
+            return self._to_host(bufs[1], words).view(np.uint64)
+        finally:
+            for d in bufs:
+                self.L.fhe_dev_free(self.ctx, d)
+
+    def expand_ggsws_seeded(self, bodies, id0s, base_log: int, level: int, mask_key) -> np.ndarray:
+        """Q queries' bodies -> Q full-form GGSWs (fhe_expand_ggsws_seeded)."""
+        b = np.ascontiguousarray(bodies, np.uint64).reshape(-1)
+        ids = np.ascontiguousarray([int(i) for i in id0s], np.uint64)
+        Q = ids.size
+        words = Q * self.L.fhe_ggsw_words(C.byref(self.P), base_log, level)
+        bufs = [self._to_dev(b), self._to_dev(ids), self._alloc(8 * words)]
+        try:
+            self._ok(self.L.fhe_expand_ggsws_seeded(self.ctx, bufs[0], bufs[1], Q, base_log, level,
+                                                    self._k8(mask_key), bufs[2], None))
+            return self._to_host(bufs[2], words).view(np.uint64)
+        finally:
+            for d in bufs:
+                self.L.fhe_dev_free(self.ctx, d)
+
+    def pack_docs_glwe_seeded(self, bodies, id0: int, mask_key, B: int, D: int, base_log: int, level: int,
+                              queries: bool = False):
+        """Server: seeded document bodies -> the device-resident operand
+        (handle, B, D) of search_ggsw[_seeded] (fhe_glwe_docs_pack_seeded) or,
+        with queries=True, of the batched calls
+        (fhe_glwe_docs_queries_pack_seeded); free it with free_docs."""
+        src = self._to_dev(np.ascontiguousarray(bodies, np.uint64))
+        size = self.L.fhe_glwe_docs_queries_bytes if queries else self.L.fhe_glwe_docs_bytes
+        pack = self.L.fhe_glwe_docs_queries_pack_seeded if queries else self.L.fhe_glwe_docs_pack_seeded
+        try:
+            docs = self._alloc(size(C.byref(self.P), B, D, level))
+            self._ok(pack(self.ctx, src, int(id0), B, D, base_log, level, self._k8(mask_key), docs, None))
+            self._to_host(docs, 1)  # fhe_memcpy_d2h synchronises: the pack is done before src is freed
+            return docs, B, D
+        finally:
+            self.L.fhe_dev_free(self.ctx, src)
+
+    def search_ggsw_seeded(self, body, id0: int, mask_key, base_log: int, level: int, docs, cst: int, T: int,
+                           levels_bit: int = 0):
+        """Untrusted host, one seeded query: search_ggsw's outputs (fhe_search_ggsw_seeded_batch)."""
+        docs8, B, D = docs
+        words = -(-B // self.P.N) * (self.P.k + 1) * self.P.N
+        bufs = [self._to_dev(np.ascontiguousarray(body, np.uint64)), self._alloc(8 * words), self._alloc(8 * words)]
+        try:
+            self._ok(self.L.fhe_search_ggsw_seeded_batch(self.ctx, bufs[0], int(id0), base_log, level,
+                                                         self._k8(mask_key), docs8, B, D, int(cst), int(T),
+                                                         int(levels_bit), bufs[1], bufs[2], None))
+            return self._to_host(bufs[1], words).view(np.uint64), self._to_host(bufs[2], words).view(np.uint64)
+        finally:
+            for d in bufs:
+                self.L.fhe_dev_free(self.ctx, d)
+
+    def search_ggsws_seeded(self, bodies, id0s, mask_key, base_log: int, level: int, docs, cst: int, Ts,
+                            levels_bit: int = 0):
+        """Untrusted host, Q seeded queries: search_ggsws' outputs (fhe_search_ggsws_seeded_batch)."""
+        d, B, D = docs
+        ids = np.ascontiguousarray([int(i) for i in id0s], np.uint64)
+        hT = np.ascontiguousarray([int(t) for t in Ts], np.int64)
+        Q = ids.size
+        if hT.size != Q:
+            raise ValueError(f"{hT.size} thresholds for {Q} queries")
+        words = -(-(Q * B) // self.P.N) * (self.P.k + 1) * self.P.N
+        bufs = [self._to_dev(np.ascontiguousarray(bodies, np.uint64)), self._to_dev(ids), self._alloc(8 * words),
+                self._alloc(8 * words)]
+        try:
+            self._ok(self.L.fhe_search_ggsws_seeded_batch(self.ctx, bufs[0], bufs[1], base_log, level,
+                                                          self._k8(mask_key), d, Q, B, D, int(cst), hT.ctypes.data,
+                                                          int(levels_bit), bufs[2], bufs[3], None))
+            return self._to_host(bufs[2], words).view(np.uint64), self._to_host(bufs[3], words).view(np.uint64)
         finally:
             for b in bufs:
                 self.L.fhe_dev_free(self.ctx, b)

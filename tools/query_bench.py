@@ -94,6 +94,17 @@ tenants' own fhe_linear_ggsws_batch calls on the same operands (outputs
 compared), at the tenant shape and at 2 x 512; it writes
 profiles/r17/private_tenants.json.
 
+With --seeded-private (docs/AB_LOG_r18.md) it measures the
+both-private search on seeded payloads against the full form at 16 dimensions,
+n_bits 6 (P0 = 21, gadget (7, 6)), one process, one evaluation-only server:
+the payload bytes; PrivateServer.pack_docs_many (parse, host-to-device copy,
+operand kernel) at B = 1024 and B = 65536 with the operand step alone on
+resident inputs; PrivateServer.search_many for 8 queries x 128 documents,
+seeded between two full-form series, 24 steps after 4 warm-up in rotating
+order; and k_expand_ggsw_seeded alone. The two clients' ciphertext words
+coincide, so operands and replies are compared word for word; it writes
+profiles/r18/seeded_private.json.
+
 The floor of the leveled step is its output, B * (kN + 1) * 8 bytes, over the
 6.29 TB/s a float4 copy reaches on the MI355X; `floor_fraction` is that floor
 over the measured time. Prints one JSON line and writes it to --out.
@@ -1054,6 +1065,118 @@ def private_queries(cq, oq, D: int, n_bits: int, steps: int, warmup: int, Qn: in
     return out
 
 
+def seeded_private(cq, oq, D: int, n_bits: int, steps: int, warmup: int, Qn: int = 8, B: int = 128,
+                   load_sizes=(1024, 65536)) -> dict:
+    """The both-private search on seeded payloads against the
+    full form, one process, one server. Payload bytes; per corpus size the load
+    (PrivateServer.pack_docs_many: parse, host-to-device copy, operand kernel)
+    seeded against full form, interleaved in alternating order, and the
+    operand step alone on resident inputs (HIP events); then
+    PrivateServer.search_many, Qn queries x B documents, three legs
+    interleaved in rotating order: (a) full form, (b) seeded, (c) full form
+    again, whose spread against (a) is the margin the ratio b / a is read
+    with; and k_expand_ggsw_seeded alone (HIP events). The seeded client's
+    words are the full-form client's (one key for masks and noise, a test
+    arrangement), so the replies are compared word for word."""
+    import numpy as np
+    import torch
+    from oracle import quant_ref as Q
+    from fheicp.corpus import EncryptedCorpus
+    from fheicp import private as P
+    c = EncryptedCorpus(cq).compile(key_seed=5, device=0, noise_seed=6)
+    full = P.PrivateClient(c, count=Qn * B, pack_seed=17, enc_seed=18)
+    seeded = P.PrivateClient(c, count=Qn * B, pack_seed=17, enc_seed=18, seeded=True)
+    seeded._mask_key = full._enc_key.copy()      # measurement only: the two clients' ciphertext words coincide
+    server = P.PrivateServer(full.eval_keys(), cq, c.P0, scheme=c.scheme)
+    eng = server.engine
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    def events(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), out
+
+    out = {"Q": Qn, "B": B, "ggsw_gadget": list(full.gadget), "steps": steps, "warmup": warmup, "load": {}}
+    same = True
+    for n, Bl in enumerate(load_sizes):
+        _, docs = Q.make_corpus(D, Bl, seed=21)
+        id0 = (n + 1) << 32                      # every block its own ids: the server refuses a repeat
+        blocks = {"full": full.encrypt_docs(docs, id0=id0), "seeded": seeded.encrypt_docs(docs, id0=id0)}
+        t = {k: [] for k in blocks}
+        tk = {k: [] for k in blocks}
+        last = {}
+        bl_f, bl_s = P.unpack_doc_block(blocks["full"]), P.unpack_doc_block_seeded(blocks["seeded"])
+        d_f, d_s = eng.to_dev(bl_f["glwe"]), eng.to_dev(bl_s["body"])
+        kern = {"full": lambda: eng.pack_docs_glwe_queries(d_f, Bl, D, server.base_log, server.level),
+                "seeded": lambda: eng.pack_docs_glwe_seeded(d_s, bl_s["id0"], bl_s["mask_key"], Bl, D, server.base_log,
+                                                            server.level, queries=True)}
+        for i in range(warmup + steps):
+            for k in (("full", "seeded") if i % 2 == 0 else ("seeded", "full")):
+                sec, (last[k], _) = timed(lambda k=k: server.pack_docs_many(blocks[k]))
+                ms, _ = events(kern[k])
+                if i >= warmup:
+                    t[k].append(sec)
+                    tk[k].append(ms)
+        same = same and bool(torch.equal(last["full"], last["seeded"]))
+        med = {k: statistics.median(v) * 1e3 for k, v in t.items()}
+        medk = {k: statistics.median(v) for k, v in tk.items()}
+        out["load"][str(Bl)] = {
+            "block_bytes": {k: int(b.nbytes) for k, b in blocks.items()},
+            "pack_docs_many_ms": med, "pack_docs_many_min_ms": {k: min(v) * 1e3 for k, v in t.items()},
+            "operand_step_alone_ms": medk, "ratio_seeded_over_full": med["seeded"] / med["full"],
+            "ratio_operand_step_seeded_over_full": medk["seeded"] / medk["full"],
+            "seeded_no_slower": med["seeded"] <= med["full"]}
+        del d_f, d_s, last
+    _, docs = Q.make_corpus(D, B, seed=21)
+    qs = np.stack([Q.make_corpus(D, 1, seed=100 + i)[0] for i in range(Qn)])
+    docs_op, _ = server.pack_docs_many(seeded.encrypt_docs(docs, id0=5000))
+    pay = {"full": full.encrypt_queries(qs, id0=7000), "seeded": seeded.encrypt_queries(qs, id0=7000)}
+    runs = {"a": lambda: server.search_many(pay["full"], docs_op, B, 0.5),
+            "b": lambda: server.search_many(pay["seeded"], docs_op, B, 0.5),
+            "c": lambda: server.search_many(pay["full"], docs_op, B, 0.5)}
+    orders = ("abc", "cba", "bca", "acb", "cab", "bac")
+    t = {k: [] for k in runs}
+    last = {}
+    for i in range(warmup + steps):
+        for k in orders[i % len(orders)]:
+            sec, last[k] = timed(runs[k])
+            if i >= warmup:
+                t[k].append(sec)
+    med = {k: statistics.median(v) * 1e3 for k, v in t.items()}
+    pls = [P.unpack_ggsw_query_seeded(p) for p in pay["seeded"]]
+    bodies = eng.to_dev(np.concatenate([pl["body"] for pl in pls]))
+    ids = [pl["id0"] for pl in pls]
+    ex = [events(lambda: eng.expand_ggsws_seeded(bodies, ids, server.base_log, server.level, pls[0]["mask_key"]))[0]
+          for _ in range(warmup + steps)][warmup:]
+    acc, below = full.decrypt_replies(last["b"])
+    ref = np.stack([Q.corpus_accumulate(oq, cq.s_e, n_bits, q, docs) for q in qs])
+    scores = np.float64(Q.corpus_out_scale(oq, cq.s_e)) * ref.astype(np.float64)
+    exact = bool(np.array_equal(acc.cpu().numpy(), ref) and
+                 np.array_equal(below.cpu().numpy(), (scores < 0.5).astype(np.int64)))
+    words = bool(len(last["a"]) == len(last["b"]) and all(np.array_equal(x, y) for x, y in zip(last["a"], last["b"])))
+    spread = abs(med["c"] / med["a"] - 1.0)
+    out.update({
+        "query_bytes": {k: int(p[0].nbytes) for k, p in pay.items()},
+        "a_full_ms": med["a"], "b_seeded_ms": med["b"], "c_full_again_ms": med["c"],
+        "min_ms": {k: min(v) * 1e3 for k, v in t.items()},
+        "ratio_seeded_over_full": med["b"] / med["a"], "full_against_full_spread": spread,
+        "seeded_within_spread": abs(med["b"] / med["a"] - 1.0) <= spread,
+        "expand_ggsw_seeded_ms": statistics.median(ex), "expand_ggsw_seeded_min_ms": min(ex),
+        "operands_equal": same, "replies_equal_word_for_word": words, "bit_exact": exact})
+    server.engine.close()
+    c.engine.close()
+    return out
+
+
 def both_private(cq, oq, B: int, D: int, n_bits: int, steps: int, warmup: int) -> dict:
     """fhe_compare_ggsw_batch against fhe_compare_query_batch on one context,
     interleaved in alternating order."""
@@ -1178,15 +1301,23 @@ def main() -> int:
                          "PrivateServer.search calls and one tenant's B = 1024 search, 24 interleaved steps after 4 "
                          "warm-up, with the HIP-event split per run, then the grouped leveled step against the "
                          "tenants' own calls; writes profiles/r17/private_tenants.json")
+    ap.add_argument("--seeded-private", action="store_true",
+                    help="the both-private search on seeded payloads (DESIGN.md §8.15) at 16-dim n_bits 6: payload "
+                         "bytes, the corpus load (pack_docs_many, copy included) seeded against full form at B = 1024 "
+                         "and 65536 with the operand step alone, search_many 8 queries x 128 documents seeded against "
+                         "two full-form series, and k_expand_ggsw_seeded alone; 24 interleaved steps after 4 warm-up; "
+                         "writes profiles/r18/seeded_private.json")
     ap.add_argument("--tenant-shape", type=int, nargs=2, default=[8, 128], metavar=("T", "B"),
                     help="--tenants / --stored-tenants / --private-tenants: T tenants of B documents each (default 8 128)")
     ap.add_argument("--out", default=None, help="default profiles/query_bench.json "
                                                 "(--multi-query: profiles/r11/multi_query.json, "
                                                 "--stored-queries: profiles/r12/stored_queries.json, "
-                                                "--private-queries: profiles/r13/private_queries.json)")
+                                                "--private-queries: profiles/r13/private_queries.json, "
+                                                "--seeded-private: profiles/r18/seeded_private.json)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = str(REPO / "profiles" / ("r17/private_tenants.json" if a.private_tenants else
+        a.out = str(REPO / "profiles" / ("r18/seeded_private.json" if a.seeded_private else
+                                         "r17/private_tenants.json" if a.private_tenants else
                                          "r16/stored_tenants.json" if a.stored_tenants else
                                          "r15/rotated.json" if a.rotated else
                                          "r14/tenants.json" if a.tenants else
@@ -1201,6 +1332,18 @@ def main() -> int:
         return 2
     from fheicp.engine import Engine
     from fheicp.params import params_for_bits
+    if a.seeded_private:
+        cq, oq = corpus_quant(16, 6)
+        sp = seeded_private(cq, oq, 16, 6, steps=24, warmup=4)
+        from fheicp import _lib
+        res = {"bench": "query_bench --seeded-private", "device": torch.cuda.get_device_name(0), "D": 16, "n_bits": 6,
+               "P0": cq.worst_msg_bits(), "build": _lib.lib().fhe_build_info().decode(), "seeded_private": sp,
+               "bit_exact": bool(sp["bit_exact"] and sp["operands_equal"] and sp["replies_equal_word_for_word"])}
+        line = json.dumps(res)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(line + "\n")
+        print(line)
+        return 0
     if a.rotated:
         cq, oq = corpus_quant(16, 6)
         ro = rotated(cq, oq, 16, 6, steps=24, warmup=4)
