@@ -18,6 +18,8 @@
 //                     digits, Toeplitz byte planes, slot extraction
 //   k_extprod_q.h     both-private search, Q queries in one pass: reversed
 //                     document digits, GGSW byte planes, the transposed i8 GEMM
+//   k_private_seeded.h  both-private search on seeded documents and queries
+//   k_seeded_keys.h   seeded evaluation keys: LWE-row expansion, body gather
 //   k_blind_rotate.h  blind rotation (external products over an f64 wave FFT):
 //                     v4 (br_v4.h, the default hot kernel), v2/v3, v1
 //   this file         context, launch selection, profiling, the C ABI
@@ -46,6 +48,7 @@
 #include "k_extprod.h"
 #include "k_extprod_q.h"
 #include "k_private_seeded.h"
+#include "k_seeded_keys.h"
 #include "k_blind_rotate.h"
 #include "k_extprod_grp.h"
 
@@ -69,6 +72,8 @@ struct GadgetKey {
   u64* key = nullptr;
   int8_t* planes = nullptr;
   int beta = 0, level = 0;
+  bool seeded = false;  // the masks are the streams of `mask` (§8.16): the key can be exported seeded
+  ChaKey mask{};
 };
 
 struct fhe_ctx;
@@ -138,6 +143,15 @@ struct fhe_ctx {
   // (grown on demand), and the time of k_expand_ggsw_seeded
   DevBuf xs_ws;
   ProfAcc prof_xs;
+  // seeded evaluation keys (k_seeded_keys.h): the public mask
+  // key of bsk and ksk (eval_seeded) and of the other gadgets' keys
+  // (fast_seeded: fhe_import_keys re-encrypts those under a private key), every
+  // mask key a seeded keygen of this context has used, and the bodies' staging
+  // buffer of an export or import (freed when the entry returns)
+  bool eval_seeded = false, fast_seeded = false;
+  ChaKey eval_mask{};
+  std::vector<ChaKey> used_masks;
+  DevBuf sk_ws;
 };
 
 static std::mutex g_err_mu;
@@ -645,7 +659,7 @@ void fhe_ctx_destroy(fhe_ctx* ctx) {
                       (void*)ctx->bskf[4], (void*)ctx->bskf_fft[4],
                       (void*)ctx->ksk8, ctx->ks_ws[0].p, ctx->ks_ws[1].p, (void*)ctx->tw4, (void*)ctx->bsk_fft_v2,
                       (void*)ctx->psi, (void*)ctx->mb_msg, ctx->lq_ws.p, (void*)ctx->pack_key.key,
-                      (void*)ctx->pack_key.planes, ctx->pack_ws.p, ctx->xp_ws.p, ctx->xs_ws.p, ctx->lsq_cst.p,
+                      (void*)ctx->pack_key.planes, ctx->pack_ws.p, ctx->xp_ws.p, ctx->xs_ws.p, ctx->lsq_cst.p, ctx->sk_ws.p,
                       (void*)ctx->bridge_key.key, (void*)ctx->bridge_key.planes, ctx->bridge_ws.p})
       (void)hipFree(ptr);
     for (hipStream_t s : ctx->lane_st)
@@ -749,7 +763,7 @@ static const uint32_t kTagNoise[NGAD] = {TAG_BSK_NOISE, TAG_BSK2_NOISE, TAG_BSK3
                                          TAG_BSK6_NOISE};
 static const uint32_t kTagMbMask[NGAD] = {0, TAG_MB2_MASK, TAG_MB3_MASK, TAG_MB4_MASK, TAG_MB5_MASK, TAG_MB6_MASK};
 static const uint32_t kTagMbNoise[NGAD] = {0, TAG_MB2_NOISE, TAG_MB3_NOISE, TAG_MB4_NOISE, TAG_MB5_NOISE, TAG_MB6_NOISE};
-static void keygen_fast_bsks(fhe_ctx* ctx, const ChaKey& K, hipStream_t st) {
+static void keygen_fast_bsks(fhe_ctx* ctx, const ChaKey& Km, const ChaKey& Kn, hipStream_t st, int msg_body = 0) {
   const fhe_params& p = ctx->p;
   const size_t shm = 8 * (size_t)p.N + p.N;
   for (int g = 1; g < NGAD; ++g) {
@@ -757,10 +771,11 @@ static void keygen_fast_bsks(fhe_ctx* ctx, const ChaKey& K, hipStream_t st) {
     const fhe_params q = fast_params(p, g);
     const bool mb = mb_for(p, g);
     if (mb) hipLaunchKernelGGL(k_mb_msgs, dim3((q.n + 255) / 256), dim3(256), 0, st, ctx->s_small, q.n, ctx->mb_msg);
-    hipLaunchKernelGGL(k_keygen_bsk, dim3(fast_ggsws(p, g) * (q.k + 1) * q.pbs_level), dim3(256), shm, st, K, q.N,
+    hipLaunchKernelGGL(k_keygen_bsk, dim3(fast_ggsws(p, g) * (q.k + 1) * q.pbs_level), dim3(256), shm, st, Km, Kn,
+                       q.N,
                        q.k, q.pbs_level, q.pbs_base_log, q.glwe_noise_bits, mb ? ctx->mb_msg : ctx->s_small,
                        ctx->s_big, ctx->bskf[g - 1],
-                       mb ? kTagMbMask[g] : kTagMask[g], mb ? kTagMbNoise[g] : kTagNoise[g]);
+                       mb ? kTagMbMask[g] : kTagMask[g], mb ? kTagMbNoise[g] : kTagNoise[g], msg_body);
   }
 }
 // Device buffers of the keys: the evaluation keys always, the secrets (and
@@ -831,26 +846,25 @@ static int convert_bsk(fhe_ctx* ctx, hipStream_t st) {
   return FHE_OK;
 }
 
-int fhe_keygen_key(fhe_ctx* ctx, const uint32_t h_key[8], void* stream) {
-  int rc = need_device(ctx);
-  if (rc) return rc;
-  if (!h_key) return fail(ctx, FHE_E_ARG, "null key");
-  rc = alloc_keys(ctx);
+// The whole key set: the secrets from the noise key Kn (its TAG_SK_* streams),
+// every key's masks from Km and noise from Kn. Km = Kn, msg_body = 0:
+// fhe_keygen_key. msg_body = 1 (the seeded keygen): the bootstrapping keys'
+// messages go to the bodies, every mask word is a stream word (k_keygen_bsk).
+static int keygen_impl(fhe_ctx* ctx, const ChaKey& Km, const ChaKey& Kn, hipStream_t st, int msg_body) {
+  int rc = alloc_keys(ctx);
   if (rc) return rc;
   const fhe_params& p = ctx->p;
-  hipStream_t st = (hipStream_t)stream;
-  ChaKey K;
-  memcpy(K.w, h_key, 32);
+  ctx->eval_seeded = ctx->fast_seeded = false;
   const int big = p.k * p.N;
   const int mx = std::max(p.n, big);
-  hipLaunchKernelGGL(k_keygen_secrets, dim3((mx + 255) / 256), dim3(256), 0, st, K, p.n, big, ctx->s_small, ctx->s_big);
+  hipLaunchKernelGGL(k_keygen_secrets, dim3((mx + 255) / 256), dim3(256), 0, st, Kn, p.n, big, ctx->s_small, ctx->s_big);
   const int rows_bsk = p.n * (p.k + 1) * p.pbs_level;
   const size_t shm = 8 * (size_t)p.N + p.N;
-  hipLaunchKernelGGL(k_keygen_bsk, dim3(rows_bsk), dim3(256), shm, st, K, p.N, p.k, p.pbs_level, p.pbs_base_log,
+  hipLaunchKernelGGL(k_keygen_bsk, dim3(rows_bsk), dim3(256), shm, st, Km, Kn, p.N, p.k, p.pbs_level, p.pbs_base_log,
                      p.glwe_noise_bits, ctx->s_small, ctx->s_big, ctx->bsk, (uint32_t)TAG_BSK_MASK,
-                     (uint32_t)TAG_BSK_NOISE);
-  keygen_fast_bsks(ctx, K, st);
-  hipLaunchKernelGGL(k_keygen_ksk, dim3(big * p.ks_level), dim3(256), 0, st, K, p.n, p.ks_level, p.ks_base_log,
+                     (uint32_t)TAG_BSK_NOISE, msg_body);
+  keygen_fast_bsks(ctx, Km, Kn, st, msg_body);
+  hipLaunchKernelGGL(k_keygen_ksk, dim3(big * p.ks_level), dim3(256), 0, st, Km, Kn, p.n, p.ks_level, p.ks_base_log,
                      p.lwe_noise_bits, ctx->s_small, ctx->s_big, ctx->ksk);
   HIPCHK(ctx, hipGetLastError());
   rc = convert_bsk(ctx, st);
@@ -859,6 +873,15 @@ int fhe_keygen_key(fhe_ctx* ctx, const uint32_t h_key[8], void* stream) {
   ctx->keys = true;
   ctx->secret = true;
   return FHE_OK;
+}
+
+int fhe_keygen_key(fhe_ctx* ctx, const uint32_t h_key[8], void* stream) {
+  int rc = need_device(ctx);
+  if (rc) return rc;
+  if (!h_key) return fail(ctx, FHE_E_ARG, "null key");
+  ChaKey K;
+  memcpy(K.w, h_key, 32);
+  return keygen_impl(ctx, K, K, (hipStream_t)stream, 0);
 }
 
 int fhe_keygen(fhe_ctx* ctx, uint64_t seed, void* stream) {
@@ -899,6 +922,7 @@ int fhe_import_keys(fhe_ctx* ctx, const uint64_t* h_s_small, const uint64_t* h_s
   rc = alloc_keys(ctx);
   if (rc) return rc;
   const fhe_params& p = ctx->p;
+  ctx->eval_seeded = ctx->fast_seeded = false;  // masks of unknown origin
   HIPCHK(ctx, hipMemcpy(ctx->s_small, h_s_small, 8 * (size_t)p.n, hipMemcpyHostToDevice));
   HIPCHK(ctx, hipMemcpy(ctx->s_big, h_s_big, 8 * (size_t)p.k * p.N, hipMemcpyHostToDevice));
   HIPCHK(ctx, hipMemcpy(ctx->bsk, h_bsk, 8 * fhe_bsk_words(&p), hipMemcpyHostToDevice));
@@ -909,7 +933,7 @@ int fhe_import_keys(fhe_ctx* ctx, const uint64_t* h_s_small, const uint64_t* h_s
     ChaKey K;
     std::random_device rd;
     for (int i = 0; i < 8; ++i) K.w[i] = rd();
-    keygen_fast_bsks(ctx, K, nullptr);
+    keygen_fast_bsks(ctx, K, K, nullptr);
     HIPCHK(ctx, hipGetLastError());
   }
   rc = convert_bsk(ctx, nullptr);
@@ -917,6 +941,25 @@ int fhe_import_keys(fhe_ctx* ctx, const uint64_t* h_s_small, const uint64_t* h_s
   HIPCHK(ctx, hipDeviceSynchronize());
   ctx->keys = true;
   ctx->secret = true;
+  return FHE_OK;
+}
+
+// An evaluation-only import's first step: the context holds no s_small, s_big
+// or mb_msg afterwards (zeroed and freed if it had them).
+static int drop_secrets(fhe_ctx* ctx) {
+  const fhe_params& p = ctx->p;
+  ctx->secret = false;
+  if (ctx->s_small || ctx->s_big || ctx->mb_msg) {
+    HIPCHK(ctx, hipDeviceSynchronize());
+    if (ctx->s_small) HIPCHK(ctx, hipMemset(ctx->s_small, 0, 8 * (size_t)p.n));
+    if (ctx->s_big) HIPCHK(ctx, hipMemset(ctx->s_big, 0, 8 * (size_t)p.k * p.N));
+    if (ctx->mb_msg) HIPCHK(ctx, hipMemset(ctx->mb_msg, 0, 8 * 3 * (size_t)((p.n + 1) / 2)));
+    HIPCHK(ctx, hipDeviceSynchronize());
+    for (u64** q : {&ctx->s_small, &ctx->s_big, &ctx->mb_msg}) {
+      if (*q) HIPCHK(ctx, hipFree(*q));
+      *q = nullptr;
+    }
+  }
   return FHE_OK;
 }
 
@@ -933,20 +976,10 @@ int fhe_import_eval_keys(fhe_ctx* ctx, const uint64_t* h_bsk, const uint64_t* h_
     if (fast_level(p, g) && (!h_gadget_bsk || !h_gadget_bsk[g - 1]))
       return fail(ctx, FHE_E_ARG, "missing bootstrapping key of gadget " + std::to_string(g) +
                                       " (these parameters have it)");
-  ctx->secret = false;
-  if (ctx->s_small || ctx->s_big || ctx->mb_msg) {
-    HIPCHK(ctx, hipDeviceSynchronize());
-    if (ctx->s_small) HIPCHK(ctx, hipMemset(ctx->s_small, 0, 8 * (size_t)p.n));
-    if (ctx->s_big) HIPCHK(ctx, hipMemset(ctx->s_big, 0, 8 * (size_t)p.k * p.N));
-    if (ctx->mb_msg) HIPCHK(ctx, hipMemset(ctx->mb_msg, 0, 8 * 3 * (size_t)((p.n + 1) / 2)));
-    HIPCHK(ctx, hipDeviceSynchronize());
-    for (u64** q : {&ctx->s_small, &ctx->s_big, &ctx->mb_msg}) {
-      if (*q) HIPCHK(ctx, hipFree(*q));
-      *q = nullptr;
-    }
-  }
+  if ((rc = drop_secrets(ctx))) return rc;
   rc = alloc_keys(ctx, false);
   if (rc) return rc;
+  ctx->eval_seeded = ctx->fast_seeded = false;  // masks of unknown origin
   HIPCHK(ctx, hipMemcpy(ctx->bsk, h_bsk, 8 * fhe_bsk_words(&p), hipMemcpyHostToDevice));
   HIPCHK(ctx, hipMemcpy(ctx->ksk, h_ksk, 8 * fhe_ksk_words(&p), hipMemcpyHostToDevice));
   for (int g = 1; g < NGAD; ++g)
@@ -2169,17 +2202,22 @@ static bool pack_gadget_ok(int32_t beta, int32_t L) {
 // columns n1 ((k+1)N for the packing key, kN + 1 for the bridge key; the byte
 // planes pad them to NB whole 16-column blocks) and the words of its messages.
 // Each key's keygen kernel stays at its ABI entry: their arguments differ.
+// For the seeded form (§8.16): the tag of the mask streams and the body of a
+// row (the last `body(p)` of its n1 words: N of a GLWE row, 1 of an LWE row).
 struct GadgetDesc {
   GadgetKey fhe_ctx::*key;
   int (*n1)(const fhe_params&);
   const char *noun, *abi;
+  uint32_t tag_mask;
+  int (*body)(const fhe_params&);
   int NB(const fhe_params& p) const { return (n1(p) + KSM_NB_COLS - 1) / KSM_NB_COLS; }
   size_t words(const fhe_params& p, int L) const { return (size_t)p.k * p.N * L * n1(p); }
+  size_t body_words(const fhe_params& p, int L) const { return (size_t)p.k * p.N * L * body(p); }
 };
 static const GadgetDesc PACK_KEY = {&fhe_ctx::pack_key, [](const fhe_params& p) { return (p.k + 1) * p.N; }, "packing",
-                                    "pack"};
+                                    "pack", TAG_PACK_MASK, [](const fhe_params& p) { return p.N; }};
 static const GadgetDesc BRIDGE_KEY = {&fhe_ctx::bridge_key, [](const fhe_params& p) { return p.k * p.N + 1; }, "bridge",
-                                      "bridge"};
+                                      "bridge", TAG_BRIDGE_MASK, [](const fhe_params&) { return 1; }};
 
 static int gadget_args(fhe_ctx* ctx, const GadgetDesc& d, int32_t beta, int32_t L) {
   if (!pack_gadget_ok(beta, L))
@@ -2253,6 +2291,7 @@ static int gadget_key_alloc(fhe_ctx* ctx, const GadgetDesc& d, int32_t L) {
     k.planes = nullptr;
   }
   k.beta = k.level = 0;
+  k.seeded = false;
   if (!k.key) {
     HIPCHK(ctx, hipMalloc(&k.key, 8 * words));
     if (hipMalloc(&k.planes, (size_t)ctx->p.k * ctx->p.N * L * d.NB(ctx->p) * KSM_NB_COLS * 8) != hipSuccess) {
@@ -2300,6 +2339,17 @@ static int gadget_key_import(fhe_ctx* ctx, const GadgetDesc& d, int32_t beta, in
   return gadget_key_planes(ctx, d, beta, L, nullptr);
 }
 
+// the packing key under the context's secret: masks from Km, noise from Kn
+static int keygen_pack_impl(fhe_ctx* ctx, int32_t base_log, int32_t level, const ChaKey& Km, const ChaKey& Kn,
+                            hipStream_t st) {
+  int rc = gadget_key_alloc(ctx, PACK_KEY, level);
+  if (rc) return rc;
+  const fhe_params& p = ctx->p;
+  hipLaunchKernelGGL(k_keygen_pack, dim3((unsigned)(p.k * p.N * level)), dim3(256), 8 * (size_t)p.N + p.N, st, Km, Kn,
+                     p.N, p.k, (int)level, (int)base_log, p.glwe_noise_bits, ctx->s_big, ctx->pack_key.key);
+  HIPCHK(ctx, hipGetLastError());
+  return gadget_key_planes(ctx, PACK_KEY, base_log, level, st);
+}
 int fhe_keygen_pack_key_key(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint32_t h_key[8], void* stream) {
   if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
   int rc = gadget_args(ctx, PACK_KEY, base_log, level);  // argument errors first: a host-only context reports them too
@@ -2307,13 +2357,7 @@ int fhe_keygen_pack_key_key(fhe_ctx* ctx, int32_t base_log, int32_t level, const
   if ((rc = need_secret(ctx))) return rc;
   ChaKey K;
   if (!key_arg(h_key, K)) return fail(ctx, FHE_E_ARG, "null key");
-  if ((rc = gadget_key_alloc(ctx, PACK_KEY, level))) return rc;
-  const fhe_params& p = ctx->p;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_keygen_pack, dim3((unsigned)(p.k * p.N * level)), dim3(256), 8 * (size_t)p.N + p.N, st, K, p.N,
-                     p.k, (int)level, (int)base_log, p.glwe_noise_bits, ctx->s_big, ctx->pack_key.key);
-  HIPCHK(ctx, hipGetLastError());
-  return gadget_key_planes(ctx, PACK_KEY, base_log, level, st);
+  return keygen_pack_impl(ctx, base_log, level, K, K, (hipStream_t)stream);
 }
 int fhe_keygen_pack_key(fhe_ctx* ctx, int32_t base_log, int32_t level, uint64_t seed, void* stream) {
   const ChaKey K = key_from_seed(seed);
@@ -2409,26 +2453,20 @@ int fhe_bridge_plan(const fhe_params* params, double in_var, int32_t* base_log, 
   return fhe_pack_plan(params, 1, in_var, base_log, level, nullptr);
 }
 
-int fhe_keygen_bridge_key_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level,
-                              const uint32_t h_key[8], void* stream) {
-  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
-  int rc = gadget_args(ctx, BRIDGE_KEY, base_log, level);  // argument errors first: a host-only context reports them too
-  if (rc) return rc;
-  ChaKey K;
-  if (!h_s_big_old || !key_arg(h_key, K)) return fail(ctx, FHE_E_ARG, "null bridge keygen arguments");
+// the bridge key from the old big key (kN words of 0/1, checked by the
+// caller) to the context's secret: masks from Km, noise from Kn
+static int keygen_bridge_impl(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level,
+                              const ChaKey& Km, const ChaKey& Kn, hipStream_t st) {
   const fhe_params& p = ctx->p;
   const int big = p.k * p.N;
-  for (int i = 0; i < big; ++i)
-    if (h_s_big_old[i] > 1) return fail(ctx, FHE_E_ARG, "old big key word other than 0 or 1");
-  if ((rc = need_secret(ctx))) return rc;
-  if ((rc = gadget_key_alloc(ctx, BRIDGE_KEY, level))) return rc;
-  hipStream_t st = (hipStream_t)stream;
+  int rc = gadget_key_alloc(ctx, BRIDGE_KEY, level);
+  if (rc) return rc;
   // the old secret lives on the device for this launch only
   u64* d_old = nullptr;
   HIPCHK(ctx, hipMalloc(&d_old, 8 * (size_t)big));
   hipError_t e = hipMemcpyAsync(d_old, h_s_big_old, 8 * (size_t)big, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_keygen_bridge, dim3((unsigned)(big * level)), dim3(256), 0, st, K, big, (int)level,
+    hipLaunchKernelGGL(k_keygen_bridge, dim3((unsigned)(big * level)), dim3(256), 0, st, Km, Kn, big, (int)level,
                        (int)base_log, p.glwe_noise_bits, ctx->s_big, d_old, ctx->bridge_key.key);
     e = hipGetLastError();
   }
@@ -2440,6 +2478,24 @@ int fhe_keygen_bridge_key_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t
   HIPCHK(ctx, e3);
   HIPCHK(ctx, e4);
   return gadget_key_planes(ctx, BRIDGE_KEY, base_log, level, st);
+}
+// the argument checks of a bridge keygen, `what` in front of their messages
+static int bridge_keygen_args(fhe_ctx* ctx, const uint64_t* h_s_big_old, bool keys_ok, const char* what) {
+  if (!h_s_big_old || !keys_ok) return fail(ctx, FHE_E_ARG, std::string(what) + "null bridge keygen arguments");
+  const int big = ctx->p.k * ctx->p.N;
+  for (int i = 0; i < big; ++i)
+    if (h_s_big_old[i] > 1) return fail(ctx, FHE_E_ARG, std::string(what) + "old big key word other than 0 or 1");
+  return FHE_OK;
+}
+int fhe_keygen_bridge_key_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level,
+                              const uint32_t h_key[8], void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  int rc = gadget_args(ctx, BRIDGE_KEY, base_log, level);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  ChaKey K;
+  if ((rc = bridge_keygen_args(ctx, h_s_big_old, key_arg(h_key, K), ""))) return rc;
+  if ((rc = need_secret(ctx))) return rc;
+  return keygen_bridge_impl(ctx, h_s_big_old, base_log, level, K, K, (hipStream_t)stream);
 }
 int fhe_keygen_bridge_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level, uint64_t seed,
                           void* stream) {
@@ -3351,6 +3407,260 @@ int fhe_search_ggsws_seeded_batch(fhe_ctx* ctx, const uint64_t* d_body, const ui
   if ((rc = expand_queries_ws(ctx, Km, d_body, d_id0, 0, Q, base_log, level, stream))) return rc;
   return seeded_arg(ctx, fhe_search_ggsws_batch(ctx, (const uint64_t*)ctx->xs_ws.p, base_log, level, d_docs, Q, B, D,
                                                 cst, h_T, levels_bit, d_glwe_acc, d_glwe_bit, stream));
+}
+
+// ---- seeded evaluation keys (k_seeded_keys.h) -------------
+// A key travels as its rows' bodies and the public mask key its masks came
+// from. One mask key serves one generated key: the main set (distinct tags)
+// shares one, the packing key and the bridge key have their own.
+size_t fhe_bsk_body_words(const fhe_params* p) {
+  return p ? (size_t)p->n * (p->k + 1) * p->pbs_level * p->N : 0;
+}
+size_t fhe_ksk_body_words(const fhe_params* p) { return p ? (size_t)p->k * p->N * p->ks_level : 0; }
+size_t fhe_fast_bsk_body_words(const fhe_params* p, int32_t which) {
+  return p ? fhe_fast_bsk_words(p, which) / (size_t)(p->k + 1) : 0;
+}
+size_t fhe_pack_key_body_words(const fhe_params* p, int32_t base_log, int32_t level) {
+  if (!p || !pack_gadget_ok(base_log, level)) return 0;
+  return PACK_KEY.body_words(*p, level);
+}
+size_t fhe_bridge_key_body_words(const fhe_params* p, int32_t base_log, int32_t level) {
+  if (!p || !pack_gadget_ok(base_log, level)) return 0;
+  return BRIDGE_KEY.body_words(*p, level);
+}
+
+// One key as rows: `rows` rows of n1 words in `key`, the last `body` words of a
+// row its body (N: a GLWE row, masks from streams (tag, r k + c); 1: an LWE
+// row, masks from stream (tag, r)).
+struct KeyRows {
+  u64* key;
+  int64_t rows;
+  int n1, body;
+  uint32_t tag;
+};
+static KeyRows bsk_rows(const fhe_ctx* ctx, int g) {  // g = 0: the main key
+  const fhe_params& p = ctx->p;
+  const int n1 = (p.k + 1) * p.N;
+  if (g == 0) return {ctx->bsk, (int64_t)p.n * (p.k + 1) * p.pbs_level, n1, p.N, TAG_BSK_MASK};
+  return {ctx->bskf[g - 1], (int64_t)fast_ggsws(p, g) * (p.k + 1) * fast_level(p, g), n1, p.N,
+          mb_for(p, g) ? kTagMbMask[g] : kTagMask[g]};
+}
+static KeyRows ksk_rows(const fhe_ctx* ctx) {
+  const fhe_params& p = ctx->p;
+  return {ctx->ksk, (int64_t)p.k * p.N * p.ks_level, p.n + 1, 1, TAG_KSK_MASK};
+}
+static KeyRows gadget_rows(const fhe_ctx* ctx, const GadgetDesc& d, int L) {
+  const fhe_params& p = ctx->p;
+  return {(ctx->*d.key).key, (int64_t)p.k * p.N * L, d.n1(p), d.body(p), d.tag_mask};
+}
+static int sk_reserve(fhe_ctx* ctx, size_t words) {
+  return reserve(ctx, ctx->sk_ws, 8 * words, FHE_E_DEVICE, "hipMalloc of the seeded keys' staging buffer failed");
+}
+static int sk_release(fhe_ctx* ctx) {
+  if (ctx->sk_ws.p) {
+    HIPCHK(ctx, hipDeviceSynchronize());
+    HIPCHK(ctx, hipFree(ctx->sk_ws.p));
+    ctx->sk_ws = DevBuf{};
+  }
+  return FHE_OK;
+}
+// the key's bodies, packed, to the host
+static int export_bodies(fhe_ctx* ctx, const KeyRows& r, uint64_t* h_out) {
+  const int64_t words = r.rows * r.body;
+  int rc = sk_reserve(ctx, (size_t)words);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_gather_key_bodies, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, nullptr, r.key, r.rows,
+                     r.n1, r.n1 - r.body, r.body, (u64*)ctx->sk_ws.p);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpy(h_out, ctx->sk_ws.p, 8 * (size_t)words, hipMemcpyDeviceToHost));
+  return FHE_OK;
+}
+// bodies from the host -> the key in standard form, its masks regenerated under Km
+static int import_bodies(fhe_ctx* ctx, const ChaKey& Km, const KeyRows& r, const uint64_t* h_in) {
+  const fhe_params& p = ctx->p;
+  const int64_t words = r.rows * r.body;
+  int rc = sk_reserve(ctx, (size_t)words);
+  if (rc) return rc;
+  HIPCHK(ctx, hipMemcpy(ctx->sk_ws.p, h_in, 8 * (size_t)words, hipMemcpyHostToDevice));
+  if (r.body == 1) {
+    const int64_t blocks = r.rows * ((r.n1 - 1 + 7) / 8);
+    hipLaunchKernelGGL(k_expand_lwe_rows_seeded, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, nullptr, Km,
+                       r.tag, (const u64*)ctx->sk_ws.p, r.rows, r.n1, r.key);
+  } else {
+    hipLaunchKernelGGL(k_expand_ggsw_seeded, dim3((unsigned)r.rows), dim3(256), 0, nullptr, Km, r.tag,
+                       (const u64*)ctx->sk_ws.p, (const u64*)nullptr, (u64)0, r.rows, p.k, 1, 0, p.N, p.k, r.key);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+static bool mask_used(const fhe_ctx* ctx, const ChaKey& K) {
+  for (const ChaKey& u : ctx->used_masks)
+    if (!memcmp(u.w, K.w, 32)) return true;
+  return false;
+}
+static void note_mask(fhe_ctx* ctx, const ChaKey& K) {
+  if (!mask_used(ctx, K)) ctx->used_masks.push_back(K);
+}
+static int mask_reuse(fhe_ctx* ctx, const GadgetDesc& d, const ChaKey& Km) {
+  if (!mask_used(ctx, Km)) return FHE_OK;
+  return fail(ctx, FHE_E_ARG, "seeded " + std::string(d.noun) + " keygen: mask key reuse: a seeded keygen of this context "
+                              "already used this mask key (one mask key serves one generated key)");
+}
+
+int fhe_keygen_seeded(fhe_ctx* ctx, const uint32_t h_mask_key[8], const uint32_t h_noise_key[8], void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  ChaKey Km, Kn;  // argument errors first: a host-only context reports them too
+  if (!key_arg(h_mask_key, Km) || !key_arg(h_noise_key, Kn))
+    return fail(ctx, FHE_E_ARG, "seeded keygen: null mask or noise key");
+  int rc = need_device(ctx);
+  if (rc) return rc;
+  if ((rc = keygen_impl(ctx, Km, Kn, (hipStream_t)stream, 1))) return rc;
+  ctx->eval_seeded = ctx->fast_seeded = true;
+  ctx->eval_mask = Km;
+  note_mask(ctx, Km);
+  return FHE_OK;
+}
+
+int fhe_keygen_pack_key_seeded(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint32_t h_mask_key[8],
+                               const uint32_t h_noise_key[8], void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  int rc = seeded_arg(ctx, gadget_args(ctx, PACK_KEY, base_log, level));
+  if (rc) return rc;
+  ChaKey Km, Kn;
+  if (!key_arg(h_mask_key, Km) || !key_arg(h_noise_key, Kn))
+    return fail(ctx, FHE_E_ARG, "seeded packing keygen: null mask or noise key");
+  if ((rc = mask_reuse(ctx, PACK_KEY, Km))) return rc;
+  if ((rc = need_secret(ctx))) return rc;
+  if ((rc = keygen_pack_impl(ctx, base_log, level, Km, Kn, (hipStream_t)stream))) return rc;
+  ctx->pack_key.seeded = true;
+  ctx->pack_key.mask = Km;
+  note_mask(ctx, Km);
+  return FHE_OK;
+}
+
+int fhe_keygen_bridge_key_seeded(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level,
+                                 const uint32_t h_mask_key[8], const uint32_t h_noise_key[8], void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  int rc = seeded_arg(ctx, gadget_args(ctx, BRIDGE_KEY, base_log, level));
+  if (rc) return rc;
+  ChaKey Km, Kn;
+  const bool keys_ok = key_arg(h_mask_key, Km) && key_arg(h_noise_key, Kn);
+  if ((rc = bridge_keygen_args(ctx, h_s_big_old, keys_ok, "seeded: "))) return rc;
+  if ((rc = mask_reuse(ctx, BRIDGE_KEY, Km))) return rc;
+  if ((rc = need_secret(ctx))) return rc;
+  if ((rc = keygen_bridge_impl(ctx, h_s_big_old, base_log, level, Km, Kn, (hipStream_t)stream))) return rc;
+  ctx->bridge_key.seeded = true;
+  ctx->bridge_key.mask = Km;
+  note_mask(ctx, Km);
+  return FHE_OK;
+}
+
+int fhe_export_eval_keys_seeded(fhe_ctx* ctx, uint32_t h_mask_key_out[8], uint64_t* h_bsk_body, uint64_t* h_ksk_body,
+                                uint64_t* const h_gadget_body[5]) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  if (!h_mask_key_out || !h_bsk_body || !h_ksk_body)
+    return fail(ctx, FHE_E_ARG, "seeded export: the mask key, bsk body and ksk body buffers are required");
+  const fhe_params& p = ctx->p;
+  for (int g = 1; g < NGAD; ++g)
+    if (fast_level(p, g) && (!h_gadget_body || !h_gadget_body[g - 1]))
+      return fail(ctx, FHE_E_ARG, "seeded export: missing body buffer of gadget " + std::to_string(g) +
+                                      " (these parameters have it)");
+  int rc = need_eval_keys(ctx);
+  if (rc) return rc;
+  bool fast = false;
+  for (int g = 1; g < NGAD; ++g) fast = fast || fast_level(p, g);
+  if (!ctx->eval_seeded || (fast && !ctx->fast_seeded))
+    return fail(ctx, FHE_E_STATE, !ctx->eval_seeded
+                                      ? "these evaluation keys were not generated or imported seeded: no mask key "
+                                        "(fhe_keygen_seeded, fhe_import_eval_keys_seeded)"
+                                      : "the fast gadgets' keys were re-encrypted under a private key and cannot be "
+                                        "exported seeded");
+  HIPCHK(ctx, hipDeviceSynchronize());
+  if ((rc = export_bodies(ctx, bsk_rows(ctx, 0), h_bsk_body))) return rc;
+  if ((rc = export_bodies(ctx, ksk_rows(ctx), h_ksk_body))) return rc;
+  for (int g = 1; g < NGAD; ++g)
+    if (fast_level(p, g) && (rc = export_bodies(ctx, bsk_rows(ctx, g), h_gadget_body[g - 1]))) return rc;
+  memcpy(h_mask_key_out, ctx->eval_mask.w, 32);
+  return sk_release(ctx);
+}
+
+// Evaluation keys only, as fhe_import_eval_keys: no secret is ever allocated,
+// and secrets already present are zeroed and freed.
+int fhe_import_eval_keys_seeded(fhe_ctx* ctx, const uint32_t h_mask_key[8], const uint64_t* h_bsk_body,
+                                const uint64_t* h_ksk_body, const uint64_t* const h_gadget_body[5]) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  ChaKey Km;  // argument errors first: a host-only context reports them too
+  if (!key_arg(h_mask_key, Km)) return fail(ctx, FHE_E_ARG, "seeded import: null mask key");
+  if (!h_bsk_body || !h_ksk_body)
+    return fail(ctx, FHE_E_ARG, "seeded import: the bsk body and ksk body buffers are required");
+  const fhe_params& p = ctx->p;
+  for (int g = 1; g < NGAD; ++g)
+    if (fast_level(p, g) && (!h_gadget_body || !h_gadget_body[g - 1]))
+      return fail(ctx, FHE_E_ARG, "seeded import: missing key body of gadget " + std::to_string(g) +
+                                      " (these parameters have it)");
+  int rc = need_device(ctx);
+  if (rc) return rc;
+  if ((rc = drop_secrets(ctx))) return rc;
+  if ((rc = alloc_keys(ctx, false))) return rc;
+  ctx->eval_seeded = ctx->fast_seeded = false;
+  if ((rc = import_bodies(ctx, Km, bsk_rows(ctx, 0), h_bsk_body))) return rc;
+  if ((rc = import_bodies(ctx, Km, ksk_rows(ctx), h_ksk_body))) return rc;
+  for (int g = 1; g < NGAD; ++g)
+    if (fast_level(p, g) && (rc = import_bodies(ctx, Km, bsk_rows(ctx, g), h_gadget_body[g - 1]))) return rc;
+  if ((rc = convert_bsk(ctx, nullptr))) return rc;
+  if ((rc = sk_release(ctx))) return rc;  // synchronises
+  ctx->keys = true;
+  ctx->eval_seeded = ctx->fast_seeded = true;
+  ctx->eval_mask = Km;
+  return FHE_OK;
+}
+
+// the two gadget keys' seeded export and import, shared through GadgetDesc
+static int gadget_key_export_seeded(fhe_ctx* ctx, const GadgetDesc& d, uint32_t* h_mask_key_out, uint64_t* h_body) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  if (!h_mask_key_out || !h_body)
+    return fail(ctx, FHE_E_ARG, "seeded " + std::string(d.noun) + " key export: null buffer");
+  int rc = need_gadget_key(ctx, d);
+  if (rc) return rc;
+  const GadgetKey& k = ctx->*d.key;
+  if (!k.seeded)
+    return fail(ctx, FHE_E_STATE, "the " + std::string(d.noun) + " key was not generated or imported seeded: no mask "
+                                  "key (fhe_keygen_" + d.abi + "_key_seeded, fhe_import_" + d.abi + "_key_seeded)");
+  HIPCHK(ctx, hipDeviceSynchronize());
+  if ((rc = export_bodies(ctx, gadget_rows(ctx, d, k.level), h_body))) return rc;
+  memcpy(h_mask_key_out, k.mask.w, 32);
+  return sk_release(ctx);
+}
+static int gadget_key_import_seeded(fhe_ctx* ctx, const GadgetDesc& d, int32_t beta, int32_t L,
+                                    const uint32_t* h_mask_key, const uint64_t* h_body) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  int rc = seeded_arg(ctx, gadget_args(ctx, d, beta, L));  // argument errors first
+  if (rc) return rc;
+  ChaKey Km;
+  if (!key_arg(h_mask_key, Km) || !h_body)
+    return fail(ctx, FHE_E_ARG, "seeded " + std::string(d.noun) + " key import: null mask key or body buffer");
+  if ((rc = need_device(ctx))) return rc;
+  if ((rc = gadget_key_alloc(ctx, d, L))) return rc;
+  if ((rc = import_bodies(ctx, Km, gadget_rows(ctx, d, L), h_body))) return rc;
+  if ((rc = gadget_key_planes(ctx, d, beta, L, nullptr))) return rc;
+  GadgetKey& k = ctx->*d.key;
+  k.seeded = true;
+  k.mask = Km;
+  return sk_release(ctx);
+}
+int fhe_export_pack_key_seeded(fhe_ctx* ctx, uint32_t h_mask_key_out[8], uint64_t* h_body) {
+  return gadget_key_export_seeded(ctx, PACK_KEY, h_mask_key_out, h_body);
+}
+int fhe_export_bridge_key_seeded(fhe_ctx* ctx, uint32_t h_mask_key_out[8], uint64_t* h_body) {
+  return gadget_key_export_seeded(ctx, BRIDGE_KEY, h_mask_key_out, h_body);
+}
+int fhe_import_pack_key_seeded(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint32_t h_mask_key[8],
+                               const uint64_t* h_body) {
+  return gadget_key_import_seeded(ctx, PACK_KEY, base_log, level, h_mask_key, h_body);
+}
+int fhe_import_bridge_key_seeded(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint32_t h_mask_key[8],
+                                 const uint64_t* h_body) {
+  return gadget_key_import_seeded(ctx, BRIDGE_KEY, base_log, level, h_mask_key, h_body);
 }
 
 int fhe_threshold_batch(fhe_ctx* ctx, const uint64_t* d_ct_acc, int64_t count, int64_t T, uint64_t* d_bit,

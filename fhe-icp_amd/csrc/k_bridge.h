@@ -19,7 +19,8 @@
 // One workgroup per bridge-key row (i, l): LWE_{s'}(s_old[i] * 2^(64 - (l+1) beta)).
 // Rows as k_keygen_ksk's: masks from stream (TAG_BRIDGE_MASK, row), the noise
 // from word 0 of (TAG_BRIDGE_NOISE, row), body = sum_t a_t s'_t + e + message.
-__global__ void __launch_bounds__(256) k_keygen_bridge(ChaKey K, int big, int L, int beta, int noise_bits,
+// Masks under the mask key Km, noise under the noise key Kn.
+__global__ void __launch_bounds__(256) k_keygen_bridge(ChaKey Km, ChaKey Kn, int big, int L, int beta, int noise_bits,
                                                        const u64* __restrict__ s_new, const u64* __restrict__ s_old,
                                                        u64* __restrict__ bk) {
   __shared__ u64 red[4];
@@ -29,7 +30,7 @@ __global__ void __launch_bounds__(256) k_keygen_bridge(ChaKey K, int big, int L,
   u64 part = 0;
   for (int blk = threadIdx.x; blk < big / 8; blk += 256) {  // big % 64 == 0
     u64 w[8];
-    stream_block(K, TAG_BRIDGE_MASK, (u64)row, (uint32_t)blk, w);
+    stream_block(Km, TAG_BRIDGE_MASK, (u64)row, (uint32_t)blk, w);
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int t = 8 * blk + q;
@@ -39,7 +40,7 @@ __global__ void __launch_bounds__(256) k_keygen_bridge(ChaKey K, int big, int L,
   }
   const u64 s = block_sum_u64<256>(part, red);
   if (threadIdx.x == 0) {
-    u64 b = s + (u64)tuniform(stream_word(K, TAG_BRIDGE_NOISE, (u64)row, 0), noise_bits);
+    u64 b = s + (u64)tuniform(stream_word(Kn, TAG_BRIDGE_NOISE, (u64)row, 0), noise_bits);
     if (s_old[i]) b += 1ull << (64 - (l + 1) * beta);
     dst[big] = b;
   }

@@ -12,10 +12,19 @@ __global__ void k_keygen_secrets(ChaKey K, int n, int big, u64* s_small, u64* s_
 }
 
 // One workgroup per GGSW row (i, r): GLWE_S(0) + s_small[i] * g_lvl on
-// component c_in. body = sum_j A_j * S_j (negacyclic, binary S) + E.
-__global__ void __launch_bounds__(256) k_keygen_bsk(ChaKey K, int N, int k, int L, int beta, int noise_bits,
+// component c_in. body = sum_j A_j * S_j (negacyclic, binary S) + E. The masks
+// come from the streams of the mask key Km, the noise from those of the noise
+// key Kn (the one-key entries pass their key twice).
+// Where the message goes on a row with c_in < k: msg_body = 0 adds g to word
+// c_in N of the MASK (the one-key entries' rows, as ever); msg_body = 1 leaves
+// every mask word a stream word and subtracts g S_{c_in} from the body instead,
+// the same phase e - g S_{c_in}: the seeded keygen's rows, whose masks are
+// public (a mask word that differs from the public stream by s_i g would give
+// s_i away). Rows with c_in = k carry g in body word 0 either way.
+__global__ void __launch_bounds__(256) k_keygen_bsk(ChaKey Km, ChaKey Kn, int N, int k, int L, int beta, int noise_bits,
                                                     const u64* __restrict__ s_small, const u64* __restrict__ s_big,
-                                                    u64* __restrict__ bsk, uint32_t tag_mask, uint32_t tag_noise) {
+                                                    u64* __restrict__ bsk, uint32_t tag_mask, uint32_t tag_noise,
+                                                    int msg_body) {
   extern __shared__ u64 shm[];
   u64* A = shm;                                          // N
   unsigned char* S = (unsigned char*)(shm + N);          // N
@@ -32,7 +41,7 @@ __global__ void __launch_bounds__(256) k_keygen_bsk(ChaKey K, int N, int k, int 
     const u64 sid = (u64)row * k + j;
     for (int blk = threadIdx.x; blk < N / 8; blk += 256) {
       u64 w[8];
-      stream_block(K, tag_mask, sid, (uint32_t)blk, w);
+      stream_block(Km, tag_mask, sid, (uint32_t)blk, w);
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
         A[8 * blk + q] = w[q];
@@ -50,13 +59,16 @@ __global__ void __launch_bounds__(256) k_keygen_bsk(ChaKey K, int N, int k, int 
     }
     __syncthreads();
   }
+  const u64 g = s_small[i] ? 1ull << (64 - lvl * beta) : 0;
+  const bool in_body = msg_body && c_in < k;
   for (int q = 0; q < per; ++q) {
     const int t = threadIdx.x + 256 * q;
-    u64 b = body[q] + (u64)tuniform(stream_word(K, tag_noise, (u64)row, (u64)t), noise_bits);
+    u64 b = body[q] + (u64)tuniform(stream_word(Kn, tag_noise, (u64)row, (u64)t), noise_bits);
+    if (in_body) b -= g * s_big[(size_t)c_in * N + t];
     dst[(size_t)k * N + t] = b;
   }
   __syncthreads();
-  if (threadIdx.x == 0 && s_small[i]) dst[(size_t)c_in * N] += 1ull << (64 - lvl * beta);
+  if (threadIdx.x == 0 && !in_body) dst[(size_t)c_in * N] += g;
 }
 
 // Messages of the multi-bit bootstrapping key: pair j of the
@@ -73,7 +85,8 @@ __global__ void k_mb_msgs(const u64* __restrict__ s_small, int n, u64* __restric
 }
 
 // One workgroup per KSK row (i, l): LWE_{s_small}(s_big[i] * 2^(64 - (l+1) beta)).
-__global__ void __launch_bounds__(256) k_keygen_ksk(ChaKey K, int n, int KL, int kbeta, int noise_bits,
+// Masks under Km, noise under Kn, as k_keygen_bsk.
+__global__ void __launch_bounds__(256) k_keygen_ksk(ChaKey Km, ChaKey Kn, int n, int KL, int kbeta, int noise_bits,
                                                     const u64* __restrict__ s_small, const u64* __restrict__ s_big,
                                                     u64* __restrict__ ksk) {
   __shared__ u64 red[4];
@@ -83,7 +96,7 @@ __global__ void __launch_bounds__(256) k_keygen_ksk(ChaKey K, int n, int KL, int
   u64 part = 0;
   for (int blk = threadIdx.x; blk < (n + 7) / 8; blk += 256) {
     u64 w[8];
-    stream_block(K, TAG_KSK_MASK, (u64)row, (uint32_t)blk, w);
+    stream_block(Km, TAG_KSK_MASK, (u64)row, (uint32_t)blk, w);
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int t = 8 * blk + q;
@@ -95,7 +108,7 @@ __global__ void __launch_bounds__(256) k_keygen_ksk(ChaKey K, int n, int KL, int
   }
   const u64 s = block_sum_u64<256>(part, red);
   if (threadIdx.x == 0) {
-    u64 b = s + (u64)tuniform(stream_word(K, TAG_KSK_NOISE, (u64)row, 0), noise_bits);
+    u64 b = s + (u64)tuniform(stream_word(Kn, TAG_KSK_NOISE, (u64)row, 0), noise_bits);
     if (s_big[i]) b += 1ull << (64 - (l + 1) * kbeta);
     dst[n] = b;
   }

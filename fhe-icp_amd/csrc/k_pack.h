@@ -16,7 +16,8 @@
 // as a constant polynomial, S the big key read as k polynomials. Rows as
 // k_keygen_bsk's: masks from stream (tag_mask, row * k + c), noise from
 // (tag_noise, row), body = sum_c A_c * S_c (negacyclic, binary S) + E + message.
-__global__ void __launch_bounds__(256) k_keygen_pack(ChaKey K, int N, int k, int L, int beta, int noise_bits,
+// Masks under the mask key Km, noise under the noise key Kn.
+__global__ void __launch_bounds__(256) k_keygen_pack(ChaKey Km, ChaKey Kn, int N, int k, int L, int beta, int noise_bits,
                                                      const u64* __restrict__ s_big, u64* __restrict__ pk) {
   extern __shared__ u64 shm[];
   u64* A = shm;                                  // N
@@ -32,7 +33,7 @@ __global__ void __launch_bounds__(256) k_keygen_pack(ChaKey K, int N, int k, int
     const u64 sid = (u64)row * k + c;
     for (int blk = threadIdx.x; blk < N / 8; blk += 256) {
       u64 w[8];
-      stream_block(K, TAG_PACK_MASK, sid, (uint32_t)blk, w);
+      stream_block(Km, TAG_PACK_MASK, sid, (uint32_t)blk, w);
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
         A[8 * blk + q] = w[q];
@@ -52,7 +53,7 @@ __global__ void __launch_bounds__(256) k_keygen_pack(ChaKey K, int N, int k, int
   }
   for (int q = 0; q < per; ++q) {
     const int t = threadIdx.x + 256 * q;
-    u64 b = body[q] + (u64)tuniform(stream_word(K, TAG_PACK_NOISE, (u64)row, (u64)t), noise_bits);
+    u64 b = body[q] + (u64)tuniform(stream_word(Kn, TAG_PACK_NOISE, (u64)row, (u64)t), noise_bits);
     if (t == 0 && s_big[i]) b += 1ull << (64 - (l + 1) * beta);
     dst[(size_t)k * N + t] = b;
   }

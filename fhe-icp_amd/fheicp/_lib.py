@@ -213,6 +213,21 @@ SIGNATURES = [
                                                _vp, _vp, _vp]),
     ("fhe_search_ggsws_seeded_batch", C.c_int, [_CTXP, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _i64, _i32, _i64, _vp,
                                                 _i32, _vp, _vp, _vp]),
+    # seeded evaluation keys
+    ("fhe_bsk_body_words", C.c_size_t, [_P]),
+    ("fhe_ksk_body_words", C.c_size_t, [_P]),
+    ("fhe_fast_bsk_body_words", C.c_size_t, [_P, _i32]),
+    ("fhe_pack_key_body_words", C.c_size_t, [_P, _i32, _i32]),
+    ("fhe_bridge_key_body_words", C.c_size_t, [_P, _i32, _i32]),
+    ("fhe_keygen_seeded", C.c_int, [_CTXP, _vp, _vp, _vp]),
+    ("fhe_keygen_pack_key_seeded", C.c_int, [_CTXP, _i32, _i32, _vp, _vp, _vp]),
+    ("fhe_keygen_bridge_key_seeded", C.c_int, [_CTXP, _vp, _i32, _i32, _vp, _vp, _vp]),
+    ("fhe_export_eval_keys_seeded", C.c_int, [_CTXP, _vp, _vp, _vp, C.POINTER(C.c_void_p)]),
+    ("fhe_export_pack_key_seeded", C.c_int, [_CTXP, _vp, _vp]),
+    ("fhe_export_bridge_key_seeded", C.c_int, [_CTXP, _vp, _vp]),
+    ("fhe_import_eval_keys_seeded", C.c_int, [_CTXP, _vp, _vp, _vp, C.POINTER(C.c_void_p)]),
+    ("fhe_import_pack_key_seeded", C.c_int, [_CTXP, _i32, _i32, _vp, _vp]),
+    ("fhe_import_bridge_key_seeded", C.c_int, [_CTXP, _i32, _i32, _vp, _vp]),
     # include/fhe_bert.h: the embedding stage's encoder (fheicp.bert)
     ("fhe_bert_create", C.c_int, [_vp, C.c_int, C.POINTER(C.c_void_p)]),
     ("fhe_bert_destroy", None, [_vp]),

@@ -166,22 +166,46 @@ class EncryptedCorpus:
         self.mask_key = None
         self._noise_key = None
         self._w_cache = {}
+        self.seeded_keys = False     # the evaluation keys are generated seeded
+        self.key_mask_seed = None
+        self._key_masks = 0
+
+    def next_key_mask(self):
+        """The public mask key of this corpus' next seeded key (one mask key
+        serves one generated key: the main set takes the first, every packing
+        or bridge key a client generates the next): fresh OS randomness, or in
+        the 64-bit test form the keys of key_mask_seed, key_mask_seed + 1, ..."""
+        from .engine import Engine
+        if self.key_mask_seed is None:
+            return os.urandom(32)
+        self._key_masks += 1
+        return Engine.key_from_seed((int(self.key_mask_seed) + self._key_masks - 1) % 2 ** 64)
 
     def compile(self, key_seed: int | None = None, device: int = 0, keys: dict | None = None,
-                mask_key=None, noise_seed: int | None = None):
+                mask_key=None, noise_seed: int | None = None, seeded_keys: bool = False,
+                key_mask_seed: int | None = None):
         """Create the context, generate (key_seed) or import (keys) the secret
         keys. mask_key (8 x u32, public) defaults to fresh OS randomness; the
-        noise key is secret and session-local (noise_seed only for tests)."""
+        noise key is secret and session-local (noise_seed only for tests).
+        seeded_keys: generate the evaluation keys seeded (§8.16), their masks
+        under public mask keys of their own (fresh; key_mask_seed is the 64-bit
+        test form), so that the clients' eval_keys() ship bodies alone."""
         from .engine import Engine
         self.engine = Engine(self.scheme, device)
+        self.seeded_keys = bool(seeded_keys)
+        self.key_mask_seed = key_mask_seed
+        self._key_masks = 0
         if keys is not None:
+            if seeded_keys:
+                raise ValueError("imported secret keys have no mask key: seeded_keys needs a keygen")
             self.engine.import_keys(keys)
         else:
             # 256-bit key from the OS CSPRNG; a key_seed is the 64-bit test form
+            mk = self.next_key_mask() if seeded_keys else None
             if key_seed is None:
-                self.engine.keygen(key=os.urandom(32))
+                self.engine.keygen(key=os.urandom(32), mask_key=mk)
             else:
-                self.engine.keygen(seed=int(key_seed))
+                self.engine.keygen(seed=int(key_seed), mask_key=mk)
         self.mask_key = (np.frombuffer(os.urandom(32), np.uint32).copy() if mask_key is None
                          else np.ascontiguousarray(mask_key, dtype=np.uint32).copy())
         self._noise_key = (np.frombuffer(os.urandom(32), np.uint32).copy() if noise_seed is None

@@ -71,14 +71,22 @@ class Engine:
         return self.params.msg_bits
 
     # ---------------------------------------------------------------- keys --
-    def keygen(self, seed: int | None = None, key=None) -> None:
+    def keygen(self, seed: int | None = None, key=None, mask_key=None) -> None:
         """Generate the keys from a 256-bit ChaCha20 key (8 u32 words or 32
         bytes; fhe_keygen_key), or from a 64-bit seed (fhe_keygen: 64 bits of
-        entropy, reproducible tests and benches only). Exactly one is given."""
+        entropy, reproducible tests and benches only). Exactly one is given.
+        With mask_key (a 256-bit key, or True for a fresh os.urandom one) the
+        set is seeded (fhe_keygen_seeded): the masks come from
+        the public mask key, secrets and noise from `key` (or the seed's key),
+        and export_eval_keys(seeded=True) ships bodies and mask key alone."""
         if (seed is None) == (key is None):
             raise ValueError("keygen takes either a 64-bit seed or a 256-bit key")
         with torch.cuda.device(self.device):
-            if key is not None:
+            if mask_key is not None and mask_key is not False:
+                noise = key if key is not None else self.key_from_seed(seed)
+                self._chk(self._L.fhe_keygen_seeded(self._ctx, self._key(self._fresh(mask_key)), self._key(noise),
+                                                    _stream(self.device)))
+            elif key is not None:
                 self._chk(self._L.fhe_keygen_key(self._ctx, self._key(key), _stream(self.device)))
             else:
                 self._chk(self._L.fhe_keygen(self._ctx, C.c_uint64(seed), _stream(self.device)))
@@ -345,6 +353,14 @@ class Engine:
         return out
 
     @staticmethod
+    def _fresh(mask_key):
+        """A mask key argument: True stands for a fresh 32 bytes of the OS CSPRNG."""
+        if mask_key is True:
+            import os
+            return os.urandom(32)
+        return mask_key
+
+    @staticmethod
     def _key(k) -> C.Array:
         if isinstance(k, (bytes, bytearray)):
             if len(k) != 32:
@@ -426,11 +442,20 @@ class Engine:
         return acc, below
 
     # ------------------ two-party private query: evaluation keys, packing --
-    def keygen_pack(self, base_log: int, level: int, key=None, seed: int | None = None) -> None:
+    def keygen_pack(self, base_log: int, level: int, key=None, seed: int | None = None, mask_key=None) -> None:
         """Generate the LWE -> GLWE packing key for gadget (base_log, level)
         (fhe_keygen_pack_key[_key]); `key` is a 256-bit ChaCha20 key (os.urandom
-        when neither is given), `seed` the 64-bit test form."""
-        if seed is not None:
+        when neither is given), `seed` the 64-bit test form. With mask_key (a
+        256-bit key of this packing key alone, or True for a fresh one) the key
+        is seeded (fhe_keygen_pack_key_seeded, §8.16): `key` / `seed` is the
+        secret noise key."""
+        if mask_key is not None and mask_key is not False:
+            import os
+            noise = self.key_from_seed(seed) if seed is not None else (key if key is not None else os.urandom(32))
+            rc = self._L.fhe_keygen_pack_key_seeded(self._ctx, int(base_log), int(level),
+                                                    self._key(self._fresh(mask_key)), self._key(noise),
+                                                    _stream(self.device))
+        elif seed is not None:
             rc = self._L.fhe_keygen_pack_key(self._ctx, int(base_log), int(level), C.c_uint64(seed),
                                              _stream(self.device))
         else:
@@ -458,16 +483,25 @@ class Engine:
     def bridge_key_words(self, base_log: int, level: int) -> int:
         return int(self._L.fhe_bridge_key_words(C.byref(self._P), int(base_log), int(level)))
 
-    def keygen_bridge_key(self, s_big_old, base_log: int, level: int, key=None, seed: int | None = None) -> None:
+    def keygen_bridge_key(self, s_big_old, base_log: int, level: int, key=None, seed: int | None = None,
+                          mask_key=None) -> None:
         """Generate the bridge key from the old big key s_big_old (kN words of
         0/1, export_keys()["s_big"] of the old context) to this context's
         secret (fhe_keygen_bridge_key[_key]); `key` is a 256-bit ChaCha20 key
-        (os.urandom when neither is given), `seed` the 64-bit test form."""
+        (os.urandom when neither is given), `seed` the 64-bit test form. With
+        mask_key (this bridge key's own, or True for a fresh one) the key is
+        seeded (fhe_keygen_bridge_key_seeded, §8.16)."""
         s = np.ascontiguousarray(s_big_old, dtype=np.uint64).reshape(-1)
         if s.size != self.big:
             raise ValueError(f"the old big key holds {s.size} words, these parameters {self.big}")
         sp = C.c_void_p(s.ctypes.data)
-        if seed is not None:
+        if mask_key is not None and mask_key is not False:
+            import os
+            noise = self.key_from_seed(seed) if seed is not None else (key if key is not None else os.urandom(32))
+            rc = self._L.fhe_keygen_bridge_key_seeded(self._ctx, sp, int(base_log), int(level),
+                                                      self._key(self._fresh(mask_key)), self._key(noise),
+                                                      _stream(self.device))
+        elif seed is not None:
             rc = self._L.fhe_keygen_bridge_key(self._ctx, sp, int(base_log), int(level), C.c_uint64(seed),
                                                _stream(self.device))
         else:
@@ -510,11 +544,74 @@ class Engine:
                                                 _stream(self.device)))
         return ct
 
-    def export_eval_keys(self) -> dict:
+    def export_pack_key_seeded(self):
+        """(mask key u32[8], bodies) of a seeded packing key (fhe_export_pack_key_seeded)."""
+        b, L = self.pack_gadget
+        mk = np.zeros(8, np.uint32)
+        out = np.zeros(self._L.fhe_pack_key_body_words(C.byref(self._P), b, L), np.uint64)
+        self._chk(self._L.fhe_export_pack_key_seeded(self._ctx, C.c_void_p(mk.ctypes.data),
+                                                     C.c_void_p(out.ctypes.data)))
+        return mk, out
+
+    def import_pack_key_seeded(self, base_log: int, level: int, mask_key, body) -> None:
+        a = np.ascontiguousarray(body, dtype=np.uint64)
+        if a.size != self._L.fhe_pack_key_body_words(C.byref(self._P), int(base_log), int(level)):
+            raise ValueError("pack_key_body: size does not match its gadget and these parameters")
+        self._chk(self._L.fhe_import_pack_key_seeded(self._ctx, int(base_log), int(level), self._key(mask_key),
+                                                     C.c_void_p(a.ctypes.data)))
+        self.pack_gadget = (int(base_log), int(level))
+
+    def export_bridge_key_seeded(self):
+        """(mask key u32[8], bodies) of a seeded bridge key (fhe_export_bridge_key_seeded)."""
+        if not self.bridge_gadget:
+            raise _lib.FheError("FHE_E_STATE: no bridge key")
+        mk = np.zeros(8, np.uint32)
+        out = np.zeros(self._L.fhe_bridge_key_body_words(C.byref(self._P), *self.bridge_gadget), np.uint64)
+        self._chk(self._L.fhe_export_bridge_key_seeded(self._ctx, C.c_void_p(mk.ctypes.data),
+                                                       C.c_void_p(out.ctypes.data)))
+        return mk, out
+
+    def import_bridge_key_seeded(self, base_log: int, level: int, mask_key, body) -> None:
+        a = np.ascontiguousarray(body, dtype=np.uint64)
+        if a.size != self._L.fhe_bridge_key_body_words(C.byref(self._P), int(base_log), int(level)):
+            raise ValueError("bridge_key_body: size does not match its gadget and these parameters")
+        self._chk(self._L.fhe_import_bridge_key_seeded(self._ctx, int(base_log), int(level), self._key(mask_key),
+                                                       C.c_void_p(a.ctypes.data)))
+        self.bridge_gadget = (int(base_log), int(level))
+
+    def _export_eval_keys_seeded(self) -> dict:
+        from .params import gadget_level
+        p = self.params
+        out = {"eval_mask_key": np.zeros(8, np.uint32),
+               "bsk_body": np.zeros(self._L.fhe_bsk_body_words(C.byref(self._P)), np.uint64),
+               "ksk_body": np.zeros(self._L.fhe_ksk_body_words(C.byref(self._P)), np.uint64)}
+        for g in (1, 2, 3, 4, 5):
+            if gadget_level(p, g):
+                out[f"gadget_bsk{g}_body"] = np.zeros(self._L.fhe_fast_bsk_body_words(C.byref(self._P), g), np.uint64)
+        ptrs = (C.c_void_p * 5)(*[out[f"gadget_bsk{g}_body"].ctypes.data if f"gadget_bsk{g}_body" in out else None
+                                  for g in (1, 2, 3, 4, 5)])
+        self._chk(self._L.fhe_export_eval_keys_seeded(self._ctx, C.c_void_p(out["eval_mask_key"].ctypes.data),
+                                                      C.c_void_p(out["bsk_body"].ctypes.data),
+                                                      C.c_void_p(out["ksk_body"].ctypes.data), ptrs))
+        if self.pack_gadget:
+            out["pack_mask_key"], out["pack_key_body"] = self.export_pack_key_seeded()
+            out["pack_gadget"] = np.array(self.pack_gadget, dtype=np.int64)
+        if self.bridge_gadget:
+            out["bridge_mask_key"], out["bridge_key_body"] = self.export_bridge_key_seeded()
+            out["bridge_gadget"] = np.array(self.bridge_gadget, dtype=np.int64)
+        return out
+
+    def export_eval_keys(self, seeded: bool = False) -> dict:
         """Everything a server needs and nothing more, as numpy arrays: bsk,
         ksk, every present gadget's key (gadget_bsk1..5) and, when one was
         generated, the packing key with its gadget (pack_key, pack_gadget) and
-        the bridge key with its (bridge_key, bridge_gadget)."""
+        the bridge key with its (bridge_key, bridge_gadget). seeded=True: the
+        seeded form of §8.16 instead (eval_mask_key, bsk_body, ksk_body,
+        gadget_bsk{g}_body, pack_mask_key / pack_key_body, bridge_mask_key /
+        bridge_key_body, the gadgets as before), a third of the bytes or less;
+        every key must have been generated or imported seeded."""
+        if seeded:
+            return self._export_eval_keys_seeded()
         from .params import gadget_level
         p = self.params
         out = {"bsk": np.zeros(self._L.fhe_bsk_words(C.byref(self._P)), np.uint64),
@@ -532,9 +629,29 @@ class Engine:
             out["bridge_gadget"] = np.array(self.bridge_gadget, dtype=np.int64)
         return out
 
+    def _import_eval_keys_seeded(self, d: dict) -> None:
+        sizes = seeded_eval_key_sizes(self.params, d)          # ValueError on a size that does not match
+        arr = {k: np.ascontiguousarray(d[k], dtype=np.uint64) for k in sizes}
+        ptrs = (C.c_void_p * 5)(*[arr[f"gadget_bsk{g}_body"].ctypes.data if f"gadget_bsk{g}_body" in arr else None
+                                  for g in (1, 2, 3, 4, 5)])
+        self._chk(self._L.fhe_import_eval_keys_seeded(self._ctx, self._key(d["eval_mask_key"]),
+                                                      C.c_void_p(arr["bsk_body"].ctypes.data),
+                                                      C.c_void_p(arr["ksk_body"].ctypes.data), ptrs))
+        self.has_keys = True
+        if "pack_key_body" in d:
+            b, L = (int(x) for x in np.asarray(d["pack_gadget"]).reshape(2))
+            self.import_pack_key_seeded(b, L, d["pack_mask_key"], arr["pack_key_body"])
+        if "bridge_key_body" in d:
+            b, L = (int(x) for x in np.asarray(d["bridge_gadget"]).reshape(2))
+            self.import_bridge_key_seeded(b, L, d["bridge_mask_key"], arr["bridge_key_body"])
+
     def import_eval_keys(self, d: dict) -> None:
         """Install evaluation keys only (fhe_import_eval_keys; the packing key
-        too when the dict has one). The context holds no secret key afterwards."""
+        too when the dict has one). The context holds no secret key afterwards.
+        A seeded dict (export_eval_keys(seeded=True)) goes through
+        fhe_import_eval_keys_seeded; a dict that holds both forms is refused."""
+        if eval_keys_seeded(d):
+            return self._import_eval_keys_seeded(d)
         bsk = np.ascontiguousarray(d["bsk"], dtype=np.uint64)
         ksk = np.ascontiguousarray(d["ksk"], dtype=np.uint64)
         if bsk.size != self._L.fhe_bsk_words(C.byref(self._P)) or ksk.size != self._L.fhe_ksk_words(C.byref(self._P)):
@@ -974,6 +1091,56 @@ class Engine:
         items = C.c_int64()
         self._chk(self._L.fhe_profile_read(self._ctx, kernel.encode(), C.byref(ms), C.byref(nl), C.byref(items)))
         return {"total_ms": ms.value, "launches": nl.value, "items": items.value}
+
+
+FULL_EVAL_KEYS = ("bsk", "ksk", "pack_key", "bridge_key") + tuple(f"gadget_bsk{g}" for g in (1, 2, 3, 4, 5))
+
+
+def eval_keys_seeded(d: dict) -> bool:
+    """Which form an evaluation-key dict has: True for the seeded form of
+    DESIGN.md §8.16 (it has "bsk_body"), False for the full form. A dict with
+    arrays of both forms is a ValueError."""
+    seeded = "bsk_body" in d
+    if seeded:
+        both = [k for k in FULL_EVAL_KEYS if k in d]
+        if both:
+            raise ValueError(f"evaluation keys mix the seeded and the full form: bsk_body and {', '.join(both)}")
+        for k in ("eval_mask_key", "ksk_body"):
+            if k not in d:
+                raise ValueError(f"seeded evaluation keys without {k}")
+    elif any(k.endswith("_body") for k in d):
+        raise ValueError("evaluation keys mix the seeded and the full form: bodies without bsk_body")
+    return seeded
+
+
+def seeded_eval_key_sizes(params: SchemeParams, d: dict) -> dict:
+    """name -> words of every body array a seeded dict must and does hold for
+    these parameters (the ABI's size functions); ValueError naming the array
+    whose size differs, a missing gadget's key or a mask key that is not 8 words."""
+    from .params import gadget_level
+    L = _lib.lib()
+    P = _lib.params_struct(params.as_dict())
+    want = {"bsk_body": L.fhe_bsk_body_words(C.byref(P)), "ksk_body": L.fhe_ksk_body_words(C.byref(P))}
+    for g in (1, 2, 3, 4, 5):
+        if gadget_level(params, g):
+            want[f"gadget_bsk{g}_body"] = L.fhe_fast_bsk_body_words(C.byref(P), g)
+    masks = ["eval_mask_key"]
+    for name, fn in (("pack", L.fhe_pack_key_body_words), ("bridge", L.fhe_bridge_key_body_words)):
+        if f"{name}_key_body" in d:
+            if f"{name}_gadget" not in d or f"{name}_mask_key" not in d:
+                raise ValueError(f"{name}_key_body without {name}_gadget or {name}_mask_key")
+            b, lv = (int(x) for x in np.asarray(d[f"{name}_gadget"]).reshape(2))
+            want[f"{name}_key_body"] = fn(C.byref(P), b, lv)
+            masks.append(f"{name}_mask_key")
+    for k, n in want.items():
+        if k not in d:
+            raise ValueError(f"seeded evaluation keys without {k} (these parameters have it)")
+        if np.asarray(d[k]).size != n or n == 0:
+            raise ValueError(f"{k}: {np.asarray(d[k]).size} words do not match these parameters ({n})")
+    for k in masks:
+        if np.asarray(d[k]).size != 8:
+            raise ValueError(f"{k}: a mask key is 8 words of 32 bits")
+    return want
 
 
 def group_rows(counts) -> tuple:

@@ -339,15 +339,18 @@ class QueryClient:
         self.base_log, self.level, self.bit_levels = pack_plan(scheme, count, in_var)
         #: the plan's margin in sigmas (below 9.2 when no gadget reaches the bar)
         self.margin = pack_sigmas(scheme, count, in_var, self.base_log, self.level, 63 - self.P0)
-        corpus.engine.keygen_pack(self.base_log, self.level, seed=pack_seed)
+        corpus.engine.keygen_pack(self.base_log, self.level, seed=pack_seed,
+                                  mask_key=corpus.next_key_mask() if corpus.seeded_keys else None)
 
     def encrypt_query(self, q, id0: int | None = None) -> np.ndarray:
         return self.single.encrypt_query(q, id0)
 
-    def eval_keys(self) -> dict:
+    def eval_keys(self, seeded: bool | None = None) -> dict:
         """What the server gets: bsk, ksk, the gadgets' keys, the packing key
-        with its gadget and the bit prefix. No secret key."""
-        d = self.corpus.engine.export_eval_keys()
+        with its gadget and the bit prefix. No secret key. On a corpus compiled
+        with seeded_keys the dict is the seeded form (§8.16: bodies and mask
+        keys); eval_keys(seeded=False) is the full form of the same keys."""
+        d = self.corpus.engine.export_eval_keys(seeded=self.corpus.seeded_keys if seeded is None else seeded)
         d["pack_bit_levels"] = np.array([self.bit_levels], dtype=np.int64)
         return d
 
@@ -402,7 +405,7 @@ class QueryServer:
     def __init__(self, eval_keys: dict, cq, P0: int, device: int = 0, scheme=None):
         from .engine import Engine
         from .params import params_for_bits
-        if "pack_key" not in eval_keys:
+        if "pack_key" not in eval_keys and "pack_key_body" not in eval_keys:
             raise ValueError("the evaluation keys hold no packing key")
         self.cq, self.P0 = cq, int(P0)
         self.scheme = (scheme if scheme is not None else params_for_bits(self.P0)).with_msg_bits(self.P0)

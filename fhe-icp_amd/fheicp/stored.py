@@ -97,7 +97,8 @@ class CorpusClient:
         self.base_log, self.level, self.bit_levels = pack_plan(scheme, count, self.pack_in_var)
         #: the plan's margin in sigmas (below 9.2 when no gadget reaches the bar)
         self.margin = pack_sigmas(scheme, count, self.pack_in_var, self.base_log, self.level, 63 - self.P0)
-        corpus.engine.keygen_pack(self.base_log, self.level, seed=pack_seed)
+        corpus.engine.keygen_pack(self.base_log, self.level, seed=pack_seed,
+                                  mask_key=corpus.next_key_mask() if corpus.seeded_keys else None)
         self.next_id = None if next_id is None else int(next_id) % 2 ** 64
         self._id_end = 0 if next_id is None else self.next_id  # one past the largest stream id handed out
         self.bridge_gadget = None  # (base_log, level) of the bridge key and the fingerprint of the
@@ -142,7 +143,9 @@ class CorpusClient:
         new one, and a packing key planned with the bridge's variance added.
         Its eval_keys() carry bridge_key, bridge_gadget and bridge_from; its
         default stream ids continue after this client's. The *_seed arguments
-        are the 64-bit test forms."""
+        are the 64-bit test forms. When this client's keys are seeded (§8.16)
+        so are the new generation's and its bridge key, under mask keys of
+        their own."""
         from .params import bridge_plan, bridge_var
         src = self if bridge_from is None else bridge_from
         src.corpus._need()
@@ -150,13 +153,17 @@ class CorpusClient:
         scheme = self.corpus.scheme.with_msg_bits(self.P0)
         new_corpus = EncryptedCorpus(self.cq, self.corpus.scheme)
         dev = old.device.index if device is None else device
-        new_corpus.compile(key_seed=key_seed, device=dev, mask_key=self.corpus.mask_key, noise_seed=noise_seed)
+        kms = self.corpus.key_mask_seed
+        new_corpus.compile(key_seed=key_seed, device=dev, mask_key=self.corpus.mask_key, noise_seed=noise_seed,
+                           seeded_keys=self.corpus.seeded_keys,
+                           key_mask_seed=None if kms is None else (int(kms) + 16) % 2 ** 64)
         b, L = bridge_plan(scheme, self.in_var)
         new = CorpusClient(new_corpus, count=self.count if count is None else count, in_var=self.in_var,
                            pack_seed=pack_seed, extra_var=bridge_var(scheme, b, L) / 2.0 ** 128,
                            next_id=max(self.id_end, src.id_end))
         s_old = old.export_key("s_big")
-        new_corpus.engine.keygen_bridge_key(s_old, b, L, seed=bridge_seed)
+        new_corpus.engine.keygen_bridge_key(s_old, b, L, seed=bridge_seed,
+                                            mask_key=new_corpus.next_key_mask() if new_corpus.seeded_keys else None)
         s_old[:] = 0
         new.bridge_gadget = (b, L)
         new.bridge_from = src.key_id
@@ -165,14 +172,17 @@ class CorpusClient:
     def payloads(self, bodies, ids):
         return self.corpus.payloads(bodies, ids)
 
-    def eval_keys(self) -> dict:
+    def eval_keys(self, seeded: bool | None = None) -> dict:
         """What the host gets: bsk, ksk, the gadgets' keys, the packing key
         with its gadget and the bit prefix, and this generation's fingerprint
         (key_id); after rotate() also bridge_key, bridge_gadget and
-        bridge_from, the old generation's fingerprint. No secret key."""
-        d = self.corpus.engine.export_eval_keys()
+        bridge_from, the old generation's fingerprint. No secret key. On a
+        corpus compiled with seeded_keys the dict is the seeded form (§8.16);
+        eval_keys(seeded=False) is the full form of the same keys. key_id is
+        the fingerprint of the full-form ksk in both."""
+        d = self.corpus.engine.export_eval_keys(seeded=self.corpus.seeded_keys if seeded is None else seeded)
         d["pack_bit_levels"] = np.array([self.bit_levels], dtype=np.int64)
-        d["key_id"] = np.array([key_fingerprint(d["ksk"])])
+        d["key_id"] = np.array([self.key_id])
         if self.bridge_from is not None:
             d["bridge_from"] = np.array([self.bridge_from])
         return d
@@ -204,7 +214,7 @@ class CorpusServer:
     only. Honest-but-curious: it runs the search as written."""
 
     def __init__(self, eval_keys: dict, cq: CorpusQuant, P0: int, mask_key, device: int = 0, scheme=None):
-        if "pack_key" not in eval_keys:
+        if "pack_key" not in eval_keys and "pack_key_body" not in eval_keys:
             raise ValueError("the evaluation keys hold no packing key")
         self.cq, self.P0 = cq, int(P0)
         self._plan = EncryptedCorpus(cq, scheme)  # planning only: never compiled, holds no key
@@ -218,9 +228,16 @@ class CorpusServer:
         self.body = self.ids = None
         # key rotation (§8.12): the resident documents b < b_old are under the
         # generation old_key_id and go through the bridge key
-        self.key_id = _fp(eval_keys["key_id"]) if "key_id" in eval_keys else key_fingerprint(eval_keys["ksk"])
+        self.key_id = self._key_id_of(eval_keys)
         self.b_old = 0
         self.old_key_id = None
+
+    def _key_id_of(self, eval_keys: dict) -> str:
+        """The generation's fingerprint: the dict's key_id, else that of the
+        full-form ksk (a seeded dict's: the key this context just expanded)."""
+        if "key_id" in eval_keys:
+            return _fp(eval_keys["key_id"])
+        return key_fingerprint(eval_keys["ksk"] if "ksk" in eval_keys else self.engine.export_key("ksk"))
 
     def _make_engine(self, device):
         from .engine import Engine
@@ -269,11 +286,11 @@ class CorpusServer:
         time: with old-generation documents already resident, the bridge must
         come from THEIR generation (rotate(bridge_from=...)) and every
         resident document must be of it."""
-        if "pack_key" not in eval_keys:
+        if "pack_key" not in eval_keys and "pack_key_body" not in eval_keys:
             raise ValueError("the evaluation keys hold no packing key")
         B = 0 if self.body is None else int(self.body.shape[0])
         if B:
-            if "bridge_key" not in eval_keys or "bridge_from" not in eval_keys:
+            if ("bridge_key" not in eval_keys and "bridge_key_body" not in eval_keys) or "bridge_from" not in eval_keys:
                 raise ValueError("documents are resident and the evaluation keys hold no bridge key")
             src = _fp(eval_keys["bridge_from"])
             if self.b_old > 0:
@@ -291,7 +308,7 @@ class CorpusServer:
         if B and self.b_old == 0:
             self.old_key_id = self.key_id
         self.b_old = B
-        self.key_id = _fp(eval_keys["key_id"]) if "key_id" in eval_keys else key_fingerprint(eval_keys["ksk"])
+        self.key_id = self._key_id_of(eval_keys)
 
     def search_many(self, queries, min_similarity=None) -> list:
         """Q clear queries against the resident corpus -> a LIST of version-2

@@ -967,6 +967,74 @@ int fhe_search_ggsws_seeded_batch(fhe_ctx* ctx, const uint64_t* d_body, const ui
                                   int32_t level, const uint32_t h_mask_key[8], const void* d_docs, int64_t Q,
                                   int64_t B, int32_t D, int64_t cst, const int64_t* h_T, int32_t levels_bit,
                                   uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream);
+
+/* ---- seeded evaluation keys ------------------------------
+ * Every row of an evaluation key is uniform mask words from a ChaCha20 stream
+ * and a body. The seeded form of a key is the body of every row and the PUBLIC
+ * mask key the masks came from; the secrets and every noise word come from a
+ * SECRET noise key that never leaves the client. Tags, stream ids and word
+ * addressing are those of fhe_keygen_key:
+ *   GLWE rows (bsk, the gadgets' keys, the packing key): row r, component
+ *     c < k, is words [0, N) of (mask tag, r k + c); the body is the last N of
+ *     the row's (k+1)N words;
+ *   LWE rows (ksk, the bridge key): row r is words [0, n1 - 1) of (mask tag, r);
+ *     the body is the last of the row's n1 words (n1 = n + 1, kN + 1).
+ * Every mask word of a seeded key is a stream word. fhe_keygen_key's
+ * bootstrapping keys are NOT of that form: a GGSW row (i, c, l) with c < k
+ * carries its message s_i g_l in word cN of the MASK, and a mask word that
+ * differs from a public stream by s_i g_l would give s_i away. The seeded
+ * keygen writes the same encryption with the message in the body: mask =
+ * stream, body = fhe_keygen_key's body - s_i g_l S_c (the phase is e - s_i g_l
+ * S_c in both). So with mask key = noise key = K the set is fhe_keygen_key(K)'s
+ * word for word in ksk, packing and bridge key and in every bsk row but those
+ * (c < k, s_i = 1), which differ by exactly that move: same secrets, same
+ * noise, same phases (tests only: a deployment never sets the two equal).
+ * fhe_keygen_key's words are unchanged. ONE MASK KEY SERVES ONE
+ * GENERATED KEY: the main set (bsk, gadget keys, ksk: distinct tags) shares
+ * one, the packing key has its own and so has the bridge key; rows with equal
+ * masks under one secret differ by messages and noise alone.
+ *
+ * Body sizes in words (0 for a null params, a bad gadget or an absent fast
+ * gadget, as the full-form siblings): n (k+1) L N, kN ks_level, a (k+1)-th of
+ * fhe_fast_bsk_words, kN L N and kN L. */
+size_t fhe_bsk_body_words(const fhe_params* params);
+size_t fhe_ksk_body_words(const fhe_params* params);
+size_t fhe_fast_bsk_body_words(const fhe_params* params, int32_t which);
+size_t fhe_pack_key_body_words(const fhe_params* params, int32_t base_log, int32_t level);
+size_t fhe_bridge_key_body_words(const fhe_params* params, int32_t base_log, int32_t level);
+/* fhe_keygen_key, fhe_keygen_pack_key_key and fhe_keygen_bridge_key_key with
+ * the key split in two; the secrets are the noise key's. The context remembers
+ * each key's mask key. A packing or bridge keygen whose mask key a seeded
+ * keygen of this context already used returns FHE_E_ARG ("mask key reuse": a
+ * courtesy, not the defence). Argument errors say "seeded" and come before the
+ * device and key checks. */
+int fhe_keygen_seeded(fhe_ctx* ctx, const uint32_t h_mask_key[8], const uint32_t h_noise_key[8], void* stream);
+int fhe_keygen_pack_key_seeded(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint32_t h_mask_key[8],
+                               const uint32_t h_noise_key[8], void* stream);
+int fhe_keygen_bridge_key_seeded(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level,
+                                 const uint32_t h_mask_key[8], const uint32_t h_noise_key[8], void* stream);
+/* The mask key and the bodies (host buffers of the sizes above;
+ * h_gadget_body[g - 1] for every gadget the parameters have). FHE_E_STATE
+ * naming "seeded" when the key was not generated or imported with a mask key:
+ * after fhe_keygen_key, a full-form import, and for the fast gadgets' keys
+ * after fhe_import_keys (re-encrypted under a private random key). */
+int fhe_export_eval_keys_seeded(fhe_ctx* ctx, uint32_t h_mask_key_out[8], uint64_t* h_bsk_body, uint64_t* h_ksk_body,
+                                uint64_t* const h_gadget_body[5]);
+int fhe_export_pack_key_seeded(fhe_ctx* ctx, uint32_t h_mask_key_out[8], uint64_t* h_body);
+int fhe_export_bridge_key_seeded(fhe_ctx* ctx, uint32_t h_mask_key_out[8], uint64_t* h_body);
+/* Evaluation-only import: the bodies are copied to a staging buffer, the keys
+ * expanded into the context's standard-form buffers (k_expand_ggsw_seeded,
+ * k_expand_lwe_rows_seeded) and converted as by the full-form imports, whose
+ * result this equals. fhe_import_eval_keys_seeded behaves as
+ * fhe_import_eval_keys: no secret is allocated, secrets already present are
+ * zeroed and freed. The context keeps the mask key, so it can export the keys
+ * seeded again. */
+int fhe_import_eval_keys_seeded(fhe_ctx* ctx, const uint32_t h_mask_key[8], const uint64_t* h_bsk_body,
+                                const uint64_t* h_ksk_body, const uint64_t* const h_gadget_body[5]);
+int fhe_import_pack_key_seeded(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint32_t h_mask_key[8],
+                               const uint64_t* h_body);
+int fhe_import_bridge_key_seeded(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint32_t h_mask_key[8],
+                                 const uint64_t* h_body);
 #ifdef __cplusplus
 }
 #endif

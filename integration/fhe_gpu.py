@@ -122,6 +122,15 @@ _PROTOS = {
                                                _vp, _vp, _vp]),
     "fhe_search_ggsws_seeded_batch": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _i64, _i32, _i64, _vp,
                                                 _i32, _vp, _vp, _vp]),
+    # seeded evaluation keys: bodies and public mask keys
+    "fhe_bsk_body_words": (C.c_size_t, [C.POINTER(fhe_params)]),
+    "fhe_ksk_body_words": (C.c_size_t, [C.POINTER(fhe_params)]),
+    "fhe_fast_bsk_body_words": (C.c_size_t, [C.POINTER(fhe_params), _i32]),
+    "fhe_pack_key_body_words": (C.c_size_t, [C.POINTER(fhe_params), _i32, _i32]),
+    "fhe_bridge_key_body_words": (C.c_size_t, [C.POINTER(fhe_params), _i32, _i32]),
+    "fhe_import_eval_keys_seeded": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "fhe_import_pack_key_seeded": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "fhe_import_bridge_key_seeded": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
 }
 
 
@@ -625,6 +634,33 @@ class GpuCompare:
         finally:
             for b in bufs:
                 self.L.fhe_dev_free(self.ctx, b)
+
+    def import_eval_keys_seeded(self, d: dict) -> None:
+        """Untrusted host: replace this context's keys by a key holder's seeded
+        evaluation keys (eval_mask_key, bsk_body, ksk_body, gadget_bsk{g}_body;
+        pack_key_body / pack_mask_key / pack_gadget and the bridge key's three
+        when present). The masks are regenerated on the device; the context
+        holds no secret afterwards."""
+        P = C.byref(self.P)
+
+        def body(name, words):
+            a = np.ascontiguousarray(d[name], np.uint64)
+            if a.size != words or words == 0:
+                raise ValueError(f"{name}: {a.size} words do not match these parameters ({words})")
+            return a
+
+        bsk, ksk = body("bsk_body", self.L.fhe_bsk_body_words(P)), body("ksk_body", self.L.fhe_ksk_body_words(P))
+        gad = [body(f"gadget_bsk{g}_body", self.L.fhe_fast_bsk_body_words(P, g)) if f"gadget_bsk{g}_body" in d else None
+               for g in (1, 2, 3, 4, 5)]
+        ptrs = (_vp * 5)(*[a.ctypes.data if a is not None else None for a in gad])
+        self._ok(self.L.fhe_import_eval_keys_seeded(self.ctx, self._k8(d["eval_mask_key"]), bsk.ctypes.data,
+                                                    ksk.ctypes.data, ptrs))
+        for name, words, imp in (("pack", self.L.fhe_pack_key_body_words, self.L.fhe_import_pack_key_seeded),
+                                 ("bridge", self.L.fhe_bridge_key_body_words, self.L.fhe_import_bridge_key_seeded)):
+            if f"{name}_key_body" in d:
+                b, lv = (int(x) for x in np.asarray(d[f"{name}_gadget"]).reshape(2))
+                a = body(f"{name}_key_body", words(P, b, lv))
+                self._ok(imp(self.ctx, b, lv, self._k8(d[f"{name}_mask_key"]), a.ctypes.data))
 
     def close(self) -> None:
         if self.ctx:

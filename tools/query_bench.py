@@ -105,6 +105,17 @@ order; and k_expand_ggsw_seeded alone. The two clients' ciphertext words
 coincide, so operands and replies are compared word for word; it writes
 profiles/r18/seeded_private.json.
 
+With --seeded-keys (docs/AB_LOG_r19.md) it measures seeded
+evaluation keys against the full form at 16 dimensions, n_bits 6 (P0 = 21):
+the bytes of both forms of one client's key set, array by array;
+Engine.import_eval_keys (host arrays in, context ready) for each form on one
+evaluation-only context, interleaved in alternating order after warm-up; and
+one search on a QueryServer, a CorpusServer and a PrivateServer built from the
+seeded dict against servers built from the full form of the same keys, the
+replies compared word for word and decrypted against the clear restatement.
+No threshold: the feature's case is size. It writes
+profiles/r19/seeded_keys.json.
+
 The floor of the leveled step is its output, B * (kN + 1) * 8 bytes, over the
 6.29 TB/s a float4 copy reaches on the MI355X; `floor_fraction` is that floor
 over the measured time. Prints one JSON line and writes it to --out.
@@ -1247,6 +1258,97 @@ def both_private(cq, oq, B: int, D: int, n_bits: int, steps: int, warmup: int) -
     return out
 
 
+def seeded_keys(cq, oq, D: int, n_bits: int, steps: int, warmup: int, Qn: int = 2, B: int = 64) -> dict:
+    """Seeded evaluation keys against the full form, one
+    process: sizes of one client's set in both forms, import_eval_keys of each
+    form on one evaluation-only context (interleaved, alternating order), and
+    one search per server kind from either form, replies word for word."""
+    import numpy as np
+    import torch
+    from oracle import quant_ref as Q
+    from fheicp import private as P
+    from fheicp.corpus import EncryptedCorpus
+    from fheicp.engine import Engine
+    from fheicp.query import QueryClient, QueryServer
+    from fheicp.stored import CorpusClient, CorpusServer
+
+    def compiled(i):
+        return EncryptedCorpus(cq).compile(key_seed=5 + i, device=0, noise_seed=6 + i, seeded_keys=True,
+                                           key_mask_seed=50 + 100 * i)
+
+    def sizes(d):
+        return {k: int(np.asarray(v).nbytes) for k, v in d.items()}
+
+    c = compiled(0)
+    client = QueryClient(c, count=Qn * B, pack_seed=17)
+    ds, df = client.eval_keys(), client.eval_keys(seeded=False)
+    out = {"Q": Qn, "B": B, "steps": steps, "warmup": warmup, "pack_gadget": [int(x) for x in ds["pack_gadget"]],
+           "bytes": {"seeded": sizes(ds), "full": sizes(df)}}
+    out["bytes"]["seeded_total"] = sum(out["bytes"]["seeded"].values())
+    out["bytes"]["full_total"] = sum(out["bytes"]["full"].values())
+    out["bytes"]["ratio_seeded_over_full"] = out["bytes"]["seeded_total"] / out["bytes"]["full_total"]
+    eng = Engine(c.scheme, 0)
+    forms = {"seeded": ds, "full": df}
+    t = {k: [] for k in forms}
+    for i in range(warmup + steps):
+        for k in (("full", "seeded") if i % 2 == 0 else ("seeded", "full")):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.import_eval_keys(forms[k])
+            torch.cuda.synchronize()
+            if i >= warmup:
+                t[k].append(time.perf_counter() - t0)
+    eng.close()
+    med = {k: statistics.median(v) * 1e3 for k, v in t.items()}
+    out["import_eval_keys_ms"] = med
+    out["import_eval_keys_min_ms"] = {k: min(v) * 1e3 for k, v in t.items()}
+    out["import_ratio_seeded_over_full"] = med["seeded"] / med["full"]
+    out["seeded_import_faster"] = med["seeded"] < med["full"]
+
+    _, docs = Q.make_corpus(D, B, seed=21)
+    qs = np.stack([Q.make_corpus(D, 1, seed=100 + i)[0] for i in range(Qn)])
+    ref = np.stack([Q.corpus_accumulate(oq, cq.s_e, n_bits, q, docs) for q in qs])
+    out["search"] = {}
+
+    def record(name, replies, decrypt):
+        same = len(replies[0]) == len(replies[1]) and all(np.array_equal(a, b) for a, b in zip(*replies))
+        acc, _ = decrypt(replies[0])
+        out["search"][name] = {"replies_equal_word_for_word": bool(same),
+                               "bit_exact": bool(np.array_equal(acc.cpu().numpy(), ref))}
+
+    payloads, replies = client.encrypt_queries(qs), []
+    for keys in (ds, df):
+        server = QueryServer(keys, cq, c.P0, scheme=c.scheme)
+        replies.append(server.search_many(payloads, server.pack_docs(docs), B, 0.5))
+        server.engine.close()
+    record("QueryServer", replies, client.decrypt_replies)
+    c.engine.close()
+
+    c = compiled(1)
+    client = CorpusClient(c, count=Qn * B, pack_seed=18)
+    stored, replies = client.encrypt_docs(docs), []
+    for keys in (client.eval_keys(), client.eval_keys(seeded=False)):
+        server = CorpusServer(keys, cq, c.P0, c.mask_key, scheme=c.scheme)
+        server.load(*stored)
+        replies.append(server.search_many(qs, 0.5))
+        server.engine.close()
+    record("CorpusServer", replies, client.decrypt_replies)
+    c.engine.close()
+
+    c = compiled(2)
+    client = P.PrivateClient(c, count=Qn * B, pack_seed=19, enc_seed=20)
+    block, payloads, replies = client.encrypt_docs(docs), client.encrypt_queries(qs), []
+    for keys in (client.eval_keys(), client.eval_keys(seeded=False)):
+        server = P.PrivateServer(keys, cq, c.P0, scheme=c.scheme)
+        docs_op, Bn = server.pack_docs_many(block)
+        replies.append(server.search_many(payloads, docs_op, Bn, 0.5))
+        server.engine.close()
+    record("PrivateServer", replies, client.decrypt_replies)
+    c.engine.close()
+    out["bit_exact"] = all(v["bit_exact"] and v["replies_equal_word_for_word"] for v in out["search"].values())
+    return out
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batch", type=int, default=1024)
@@ -1307,16 +1409,23 @@ def main() -> int:
                          "and 65536 with the operand step alone, search_many 8 queries x 128 documents seeded against "
                          "two full-form series, and k_expand_ggsw_seeded alone; 24 interleaved steps after 4 warm-up; "
                          "writes profiles/r18/seeded_private.json")
+    ap.add_argument("--seeded-keys", action="store_true",
+                    help="seeded evaluation keys (DESIGN.md §8.16) at 16-dim n_bits 6: bytes of both forms of one "
+                         "client's key set, import_eval_keys of each form interleaved (8 steps after 2 warm-up), one "
+                         "search per server kind from either form with the replies compared word for word; writes "
+                         "profiles/r19/seeded_keys.json")
     ap.add_argument("--tenant-shape", type=int, nargs=2, default=[8, 128], metavar=("T", "B"),
                     help="--tenants / --stored-tenants / --private-tenants: T tenants of B documents each (default 8 128)")
     ap.add_argument("--out", default=None, help="default profiles/query_bench.json "
                                                 "(--multi-query: profiles/r11/multi_query.json, "
                                                 "--stored-queries: profiles/r12/stored_queries.json, "
                                                 "--private-queries: profiles/r13/private_queries.json, "
-                                                "--seeded-private: profiles/r18/seeded_private.json)")
+                                                "--seeded-private: profiles/r18/seeded_private.json, "
+                                                "--seeded-keys: profiles/r19/seeded_keys.json)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = str(REPO / "profiles" / ("r18/seeded_private.json" if a.seeded_private else
+        a.out = str(REPO / "profiles" / ("r19/seeded_keys.json" if a.seeded_keys else
+                                         "r18/seeded_private.json" if a.seeded_private else
                                          "r17/private_tenants.json" if a.private_tenants else
                                          "r16/stored_tenants.json" if a.stored_tenants else
                                          "r15/rotated.json" if a.rotated else
@@ -1332,6 +1441,18 @@ def main() -> int:
         return 2
     from fheicp.engine import Engine
     from fheicp.params import params_for_bits
+    if a.seeded_keys:
+        cq, oq = corpus_quant(16, 6)
+        sk = seeded_keys(cq, oq, 16, 6, steps=8, warmup=2)
+        from fheicp import _lib
+        res = {"bench": "query_bench --seeded-keys", "device": torch.cuda.get_device_name(0), "D": 16, "n_bits": 6,
+               "P0": cq.worst_msg_bits(), "build": _lib.lib().fhe_build_info().decode(), "seeded_keys": sk,
+               "bit_exact": bool(sk["bit_exact"])}
+        line = json.dumps(res)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(line + "\n")
+        print(line)
+        return 0
     if a.seeded_private:
         cq, oq = corpus_quant(16, 6)
         sp = seeded_private(cq, oq, 16, 6, steps=24, warmup=4)
