@@ -14,6 +14,8 @@
 //                     digits, key generation, rotation, packed decryption
 //   k_bridge.h        LWE -> LWE bridge key switch (key rotation of stored
 //                     ciphertexts): key generation, mapped digits, scatter
+//   k_bridge_grp.h    its group form: several old generations' rows in one
+//                     digits launch, one group GEMM and one scatter
 //   k_extprod.h       both-private search: GGSW query encryption, GLWE document
 //                     digits, Toeplitz byte planes, slot extraction
 //   k_extprod_q.h     both-private search, Q queries in one pass: reversed
@@ -45,6 +47,7 @@
 #include "k_query.h"
 #include "k_pack.h"
 #include "k_bridge.h"
+#include "k_bridge_grp.h"
 #include "k_extprod.h"
 #include "k_extprod_q.h"
 #include "k_private_seeded.h"
@@ -74,6 +77,8 @@ struct GadgetKey {
   int beta = 0, level = 0;
   bool seeded = false;  // the masks are the streams of `mask` (§8.16): the key can be exported seeded
   ChaKey mask{};
+  bool keyed = false;   // generated unseeded with the key `gen` (the bridge slots' courtesy check, §8.17)
+  ChaKey gen{};
 };
 
 struct fhe_ctx;
@@ -128,9 +133,11 @@ struct fhe_ctx {
   GadgetKey pack_key;
   DevBuf pack_ws;           // digits | zero bodies | the GEMM's count x (k+1)N result
   ProfAcc prof_pack;        // fhe_pack_batch: k_pack_digits + the GEMM + k_pack_rotate
-  // LWE -> LWE bridge key of a key rotation (k_bridge.h), kN + 1 columns
-  GadgetKey bridge_key;
-  DevBuf bridge_ws;         // digits | bodies | the GEMM's count x (kN+1) compact result
+  // LWE -> LWE bridge keys of a key rotation (k_bridge.h), kN + 1 columns:
+  // slot 0 is the bridge key of §8.12, the others serve further old
+  // generations (§8.17)
+  GadgetKey bridge_keys[FHE_BRIDGE_SLOTS];
+  DevBuf bridge_ws;         // (the group form's tables |) digits | bodies | the GEMM's count x (kN+1) compact result
   ProfAcc prof_bridge;      // fhe_bridge_batch: k_bridge_digits + the GEMM + k_bridge_scatter
   // both-private search (k_extprod.h): the query's Toeplitz byte planes |
   // zero bodies | the GEMM's G x (k+1)N result, allocated on first use
@@ -660,8 +667,12 @@ void fhe_ctx_destroy(fhe_ctx* ctx) {
                       (void*)ctx->ksk8, ctx->ks_ws[0].p, ctx->ks_ws[1].p, (void*)ctx->tw4, (void*)ctx->bsk_fft_v2,
                       (void*)ctx->psi, (void*)ctx->mb_msg, ctx->lq_ws.p, (void*)ctx->pack_key.key,
                       (void*)ctx->pack_key.planes, ctx->pack_ws.p, ctx->xp_ws.p, ctx->xs_ws.p, ctx->lsq_cst.p, ctx->sk_ws.p,
-                      (void*)ctx->bridge_key.key, (void*)ctx->bridge_key.planes, ctx->bridge_ws.p})
+                      ctx->bridge_ws.p})
       (void)hipFree(ptr);
+    for (GadgetKey& k : ctx->bridge_keys) {
+      (void)hipFree(k.key);
+      (void)hipFree(k.planes);
+    }
     for (hipStream_t s : ctx->lane_st)
       if (s) (void)hipStreamDestroy(s);
     for (hipEvent_t e : ctx->lane_ev)
@@ -2205,18 +2216,21 @@ static bool pack_gadget_ok(int32_t beta, int32_t L) {
 // For the seeded form (§8.16): the tag of the mask streams and the body of a
 // row (the last `body(p)` of its n1 words: N of a GLWE row, 1 of an LWE row).
 struct GadgetDesc {
-  GadgetKey fhe_ctx::*key;
+  GadgetKey* (*at)(fhe_ctx*);  // the context's key, or the first of its slots
   int (*n1)(const fhe_params&);
   const char *noun, *abi;
   uint32_t tag_mask;
   int (*body)(const fhe_params&);
+  int slot = 0;
+  bool named = false;  // an entry that names its slot (§8.17): the slot goes into its messages
+  GadgetKey& key(fhe_ctx* ctx) const { return at(ctx)[slot]; }
   int NB(const fhe_params& p) const { return (n1(p) + KSM_NB_COLS - 1) / KSM_NB_COLS; }
   size_t words(const fhe_params& p, int L) const { return (size_t)p.k * p.N * L * n1(p); }
   size_t body_words(const fhe_params& p, int L) const { return (size_t)p.k * p.N * L * body(p); }
 };
-static const GadgetDesc PACK_KEY = {&fhe_ctx::pack_key, [](const fhe_params& p) { return (p.k + 1) * p.N; }, "packing",
+static const GadgetDesc PACK_KEY = {[](fhe_ctx* c) { return &c->pack_key; }, [](const fhe_params& p) { return (p.k + 1) * p.N; }, "packing",
                                     "pack", TAG_PACK_MASK, [](const fhe_params& p) { return p.N; }};
-static const GadgetDesc BRIDGE_KEY = {&fhe_ctx::bridge_key, [](const fhe_params& p) { return p.k * p.N + 1; }, "bridge",
+static const GadgetDesc BRIDGE_KEY = {[](fhe_ctx* c) { return c->bridge_keys; }, [](const fhe_params& p) { return p.k * p.N + 1; }, "bridge",
                                       "bridge", TAG_BRIDGE_MASK, [](const fhe_params&) { return 1; }};
 
 static int gadget_args(fhe_ctx* ctx, const GadgetDesc& d, int32_t beta, int32_t L) {
@@ -2281,7 +2295,7 @@ int fhe_pack_plan(const fhe_params* params, int64_t count, double in_var, int32_
 // (re)allocate a gadget key's buffers for L levels: 8 * words key bytes and
 // kN * L rows x NB * 16 columns x 8 planes (for the packing key 8 * words too)
 static int gadget_key_alloc(fhe_ctx* ctx, const GadgetDesc& d, int32_t L) {
-  GadgetKey& k = ctx->*d.key;
+  GadgetKey& k = d.key(ctx);
   const size_t words = d.words(ctx->p, L);
   if (k.key && d.words(ctx->p, k.level) != words) {
     HIPCHK(ctx, hipDeviceSynchronize());
@@ -2291,7 +2305,7 @@ static int gadget_key_alloc(fhe_ctx* ctx, const GadgetDesc& d, int32_t L) {
     k.planes = nullptr;
   }
   k.beta = k.level = 0;
-  k.seeded = false;
+  k.seeded = k.keyed = false;
   if (!k.key) {
     HIPCHK(ctx, hipMalloc(&k.key, 8 * words));
     if (hipMalloc(&k.planes, (size_t)ctx->p.k * ctx->p.N * L * d.NB(ctx->p) * KSM_NB_COLS * 8) != hipSuccess) {
@@ -2306,7 +2320,7 @@ static int gadget_key_alloc(fhe_ctx* ctx, const GadgetDesc& d, int32_t L) {
 // [i][l][n1] with no rounding (the padded columns of a last block are zero)
 static int gadget_key_planes(fhe_ctx* ctx, const GadgetDesc& d, int32_t beta, int32_t L, hipStream_t st) {
   const fhe_params& p = ctx->p;
-  GadgetKey& k = ctx->*d.key;
+  GadgetKey& k = d.key(ctx);
   const int big = p.k * p.N, K = big * L, n1 = d.n1(p), NB = d.NB(p);
   const int64_t tot = (int64_t)K * NB * KSM_NB_COLS;
   hipLaunchKernelGGL(k_ksk_to_i8, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, k.key, K, big, (int)L, n1, NB,
@@ -2320,14 +2334,17 @@ static int gadget_key_planes(fhe_ctx* ctx, const GadgetDesc& d, int32_t beta, in
 static int need_gadget_key(fhe_ctx* ctx, const GadgetDesc& d) {
   int rc = need_device(ctx);
   if (rc) return rc;
-  if (!(ctx->*d.key).level)
+  if (!d.key(ctx).level && d.named)
+    return fail(ctx, FHE_E_STATE, "no " + std::string(d.noun) + " key in slot " + std::to_string(d.slot) + ": call fhe_keygen_" +
+                                      d.abi + "_key_slot or fhe_import_" + d.abi + "_key_slot");
+  if (!d.key(ctx).level)
     return fail(ctx, FHE_E_STATE, "no " + std::string(d.noun) + " key: call fhe_keygen_" + d.abi + "_key or fhe_import_" +
                                       d.abi + "_key");
   return FHE_OK;
 }
 // the ABI entries' tails, after their own checks (whose order differs)
 static int gadget_key_export(fhe_ctx* ctx, const GadgetDesc& d, uint64_t* h_out) {
-  const GadgetKey& k = ctx->*d.key;
+  const GadgetKey& k = d.key(ctx);
   HIPCHK(ctx, hipDeviceSynchronize());
   HIPCHK(ctx, hipMemcpy(h_out, k.key, 8 * d.words(ctx->p, k.level), hipMemcpyDeviceToHost));
   return FHE_OK;
@@ -2335,7 +2352,7 @@ static int gadget_key_export(fhe_ctx* ctx, const GadgetDesc& d, uint64_t* h_out)
 static int gadget_key_import(fhe_ctx* ctx, const GadgetDesc& d, int32_t beta, int32_t L, const uint64_t* h_in) {
   int rc = gadget_key_alloc(ctx, d, L);
   if (rc) return rc;
-  HIPCHK(ctx, hipMemcpy((ctx->*d.key).key, h_in, 8 * d.words(ctx->p, L), hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(d.key(ctx).key, h_in, 8 * d.words(ctx->p, L), hipMemcpyHostToDevice));
   return gadget_key_planes(ctx, d, beta, L, nullptr);
 }
 
@@ -2453,13 +2470,27 @@ int fhe_bridge_plan(const fhe_params* params, double in_var, int32_t* base_log, 
   return fhe_pack_plan(params, 1, in_var, base_log, level, nullptr);
 }
 
-// the bridge key from the old big key (kN words of 0/1, checked by the
-// caller) to the context's secret: masks from Km, noise from Kn
-static int keygen_bridge_impl(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level,
+// bridge slot `slot` of a context (§8.17): BRIDGE_KEY's record on that slot
+static GadgetDesc bridge_slot(int slot) {
+  GadgetDesc d = BRIDGE_KEY;
+  d.slot = slot;
+  d.named = true;
+  return d;
+}
+static int slot_arg(fhe_ctx* ctx, int32_t slot) {
+  if (slot < 0 || slot >= FHE_BRIDGE_SLOTS)
+    return fail(ctx, FHE_E_ARG, "bridge slot " + std::to_string(slot) + " outside [0, " +
+                                    std::to_string(FHE_BRIDGE_SLOTS) + ")");
+  return FHE_OK;
+}
+// the bridge key of `slot` from the old big key (kN words of 0/1, checked by
+// the caller) to the context's secret: masks from Km, noise from Kn
+static int keygen_bridge_impl(fhe_ctx* ctx, int slot, const uint64_t* h_s_big_old, int32_t base_log, int32_t level,
                               const ChaKey& Km, const ChaKey& Kn, hipStream_t st) {
   const fhe_params& p = ctx->p;
   const int big = p.k * p.N;
-  int rc = gadget_key_alloc(ctx, BRIDGE_KEY, level);
+  const GadgetDesc desc = bridge_slot(slot);
+  int rc = gadget_key_alloc(ctx, desc, level);
   if (rc) return rc;
   // the old secret lives on the device for this launch only
   u64* d_old = nullptr;
@@ -2467,7 +2498,7 @@ static int keygen_bridge_impl(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t
   hipError_t e = hipMemcpyAsync(d_old, h_s_big_old, 8 * (size_t)big, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_keygen_bridge, dim3((unsigned)(big * level)), dim3(256), 0, st, Km, Kn, big, (int)level,
-                       (int)base_log, p.glwe_noise_bits, ctx->s_big, d_old, ctx->bridge_key.key);
+                       (int)base_log, p.glwe_noise_bits, ctx->s_big, d_old, ctx->bridge_keys[slot].key);
     e = hipGetLastError();
   }
   const hipError_t e2 = hipStreamSynchronize(st);
@@ -2477,7 +2508,7 @@ static int keygen_bridge_impl(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t
   HIPCHK(ctx, e2);
   HIPCHK(ctx, e3);
   HIPCHK(ctx, e4);
-  return gadget_key_planes(ctx, BRIDGE_KEY, base_log, level, st);
+  return gadget_key_planes(ctx, desc, base_log, level, st);
 }
 // the argument checks of a bridge keygen, `what` in front of their messages
 static int bridge_keygen_args(fhe_ctx* ctx, const uint64_t* h_s_big_old, bool keys_ok, const char* what) {
@@ -2487,23 +2518,53 @@ static int bridge_keygen_args(fhe_ctx* ctx, const uint64_t* h_s_big_old, bool ke
     if (h_s_big_old[i] > 1) return fail(ctx, FHE_E_ARG, std::string(what) + "old big key word other than 0 or 1");
   return FHE_OK;
 }
-int fhe_keygen_bridge_key_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level,
-                              const uint32_t h_key[8], void* stream) {
-  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+// the unseeded keygen of a slot; `courtesy`: refuse a key another live slot
+// was generated with (the slot entries; the §8.12 entry keeps its behaviour)
+static int keygen_bridge_key_at(fhe_ctx* ctx, int32_t slot, const uint64_t* h_s_big_old, int32_t base_log,
+                                int32_t level, const uint32_t h_key[8], bool courtesy, void* stream) {
   int rc = gadget_args(ctx, BRIDGE_KEY, base_log, level);  // argument errors first: a host-only context reports them too
   if (rc) return rc;
   ChaKey K;
   if ((rc = bridge_keygen_args(ctx, h_s_big_old, key_arg(h_key, K), ""))) return rc;
+  if (courtesy)
+    for (int s = 0; s < FHE_BRIDGE_SLOTS; ++s) {
+      const GadgetKey& o = ctx->bridge_keys[s];
+      if (s != slot && o.level && o.keyed && !memcmp(o.gen.w, K.w, 32))
+        return fail(ctx, FHE_E_ARG, "bridge keygen: key reuse: bridge slot " + std::to_string(s) +
+                                        " of this context was generated with this key (one key serves one bridge key)");
+    }
   if ((rc = need_secret(ctx))) return rc;
-  return keygen_bridge_impl(ctx, h_s_big_old, base_log, level, K, K, (hipStream_t)stream);
+  if ((rc = keygen_bridge_impl(ctx, slot, h_s_big_old, base_log, level, K, K, (hipStream_t)stream))) return rc;
+  ctx->bridge_keys[slot].keyed = true;
+  ctx->bridge_keys[slot].gen = K;
+  return FHE_OK;
+}
+int fhe_keygen_bridge_key_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level,
+                              const uint32_t h_key[8], void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  return keygen_bridge_key_at(ctx, 0, h_s_big_old, base_log, level, h_key, false, stream);
 }
 int fhe_keygen_bridge_key(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level, uint64_t seed,
                           void* stream) {
   const ChaKey K = key_from_seed(seed);
   return fhe_keygen_bridge_key_key(ctx, h_s_big_old, base_log, level, K.w, stream);
 }
+int fhe_keygen_bridge_key_slot_key(fhe_ctx* ctx, int32_t slot, const uint64_t* h_s_big_old, int32_t base_log,
+                                   int32_t level, const uint32_t h_key[8], void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  int rc = slot_arg(ctx, slot);
+  if (rc) return rc;
+  return keygen_bridge_key_at(ctx, slot, h_s_big_old, base_log, level, h_key, true, stream);
+}
+int fhe_keygen_bridge_key_slot(fhe_ctx* ctx, int32_t slot, const uint64_t* h_s_big_old, int32_t base_log,
+                               int32_t level, uint64_t seed, void* stream) {
+  const ChaKey K = key_from_seed(seed);
+  return fhe_keygen_bridge_key_slot_key(ctx, slot, h_s_big_old, base_log, level, K.w, stream);
+}
 
 static int need_bridge_key(fhe_ctx* ctx) { return need_gadget_key(ctx, BRIDGE_KEY); }
+// after the device check: the key of a slot the slot entries name
+static int need_bridge_slot(fhe_ctx* ctx, int slot) { return need_gadget_key(ctx, bridge_slot(slot)); }
 
 int fhe_export_bridge_key(fhe_ctx* ctx, uint64_t* h_out) {
   if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
@@ -2511,6 +2572,14 @@ int fhe_export_bridge_key(fhe_ctx* ctx, uint64_t* h_out) {
   int rc = need_bridge_key(ctx);
   if (rc) return rc;
   return gadget_key_export(ctx, BRIDGE_KEY, h_out);
+}
+int fhe_export_bridge_key_slot(fhe_ctx* ctx, int32_t slot, uint64_t* h_out) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  int rc = slot_arg(ctx, slot);
+  if (rc) return rc;
+  if (!h_out) return fail(ctx, FHE_E_ARG, "null buffer");
+  if ((rc = need_bridge_slot(ctx, slot))) return rc;
+  return gadget_key_export(ctx, bridge_slot(slot), h_out);
 }
 
 int fhe_import_bridge_key(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint64_t* h_in) {
@@ -2521,16 +2590,43 @@ int fhe_import_bridge_key(fhe_ctx* ctx, int32_t base_log, int32_t level, const u
   if ((rc = need_device(ctx))) return rc;
   return gadget_key_import(ctx, BRIDGE_KEY, base_log, level, h_in);
 }
+int fhe_import_bridge_key_slot(fhe_ctx* ctx, int32_t slot, int32_t base_log, int32_t level, const uint64_t* h_in) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  int rc = slot_arg(ctx, slot);
+  if (rc) return rc;
+  if ((rc = gadget_args(ctx, BRIDGE_KEY, base_log, level))) return rc;
+  if (!h_in) return fail(ctx, FHE_E_ARG, "null buffer");
+  if ((rc = need_device(ctx))) return rc;
+  return gadget_key_import(ctx, bridge_slot(slot), base_log, level, h_in);
+}
+// frees a slot's words and planes; an empty slot is left as it is
+int fhe_drop_bridge_key_slot(fhe_ctx* ctx, int32_t slot) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  int rc = slot_arg(ctx, slot);
+  if (rc) return rc;
+  if ((rc = need_device(ctx))) return rc;
+  GadgetKey& k = ctx->bridge_keys[slot];
+  if (k.key || k.planes) {
+    HIPCHK(ctx, hipDeviceSynchronize());  // queued work may still read the planes
+    HIPCHK(ctx, hipFree(k.key));
+    k.key = nullptr;
+    HIPCHK(ctx, hipFree(k.planes));
+    k.planes = nullptr;
+  }
+  k = GadgetKey{};
+  return FHE_OK;
+}
 
-// digits -> GEMM on the i8 matrix cores -> copy back, for the Q * B_old rows
-// {q B + b : b < B_old} of d_in (Q x B big LWEs); row r of d_out takes the
-// bridged row r (d_out may be d_in: every digit is formed before the copy).
-// The GEMM is the key switch's kernel on 8 planes with kN + 1 columns, the
-// same K split as pack_impl's (gemm81); it writes a compact count x (kN+1) buffer.
-static int bridge_impl(fhe_ctx* ctx, const uint64_t* d_in, int64_t Q, int64_t B, int64_t B_old, uint64_t* d_out,
-                       hipStream_t st) {
+// digits -> GEMM on the i8 matrix cores -> copy back with the bridge key `k`,
+// for the Q * B_old rows {q B + b : b < B_old} of d_in (Q x B big LWEs); row r
+// of d_out takes the bridged row r (d_out may be d_in: every digit is formed
+// before the copy). The GEMM is the key switch's kernel on 8 planes with
+// kN + 1 columns, the same K split as pack_impl's (gemm81); it writes a
+// compact count x (kN+1) buffer.
+static int bridge_impl(fhe_ctx* ctx, const GadgetKey& k, const uint64_t* d_in, int64_t Q, int64_t B, int64_t B_old,
+                       uint64_t* d_out, hipStream_t st) {
   const fhe_params& p = ctx->p;
-  const int levels = ctx->bridge_key.level;
+  const int levels = k.level;
   const int big = p.k * p.N, K = big * levels, KB = K / 64, n1 = big + 1, NB = (n1 + KSM_NB_COLS - 1) / KSM_NB_COLS;
   const int64_t count = Q * B_old, ncb = (count + 15) / 16;
   if (ncb > 65535 || count > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, "bridge batch too large: split the call");
@@ -2545,10 +2641,8 @@ static int bridge_impl(fhe_ctx* ctx, const uint64_t* d_in, int64_t Q, int64_t B,
   prof_begin(ctx, ctx->prof_bridge, st, &e1);
   // the digits kernel also zeroes the compact rows the split's atomics add into
   hipLaunchKernelGGL(k_bridge_digits, dim3((unsigned)(big / 64), (unsigned)ncb), dim3(256), 0, st, d_in, count, B,
-                     B_old, big, ctx->bridge_key.beta, levels, KB, Dg, body,
-                     gemm81_split(count, NB, KB).S > 1 ? n1 : 0, M);
-  if ((rc = gemm81(ctx, ctx->prof_bridge, "bridge", Dg, ctx->bridge_key.planes, body, count, n1, NB, KB, M, st)))
-    return rc;
+                     B_old, big, k.beta, levels, KB, Dg, body, gemm81_split(count, NB, KB).S > 1 ? n1 : 0, M);
+  if ((rc = gemm81(ctx, ctx->prof_bridge, "bridge", Dg, k.planes, body, count, n1, NB, KB, M, st))) return rc;
   hipLaunchKernelGGL(k_bridge_scatter, dim3((unsigned)count, (unsigned)((n1 + 255) / 256)), dim3(256), 0, st, M, count,
                      B, B_old, n1, d_out);
   prof_end(ctx, ctx->prof_bridge, st, e1, count);
@@ -2564,7 +2658,7 @@ int fhe_bridge_batch(fhe_ctx* ctx, const uint64_t* d_ct, int64_t count, uint64_t
   int rc = need_bridge_key(ctx);
   if (rc) return rc;
   if (count == 0) return FHE_OK;
-  return bridge_impl(ctx, d_ct, 1, count, count, d_out, (hipStream_t)stream);
+  return bridge_impl(ctx, ctx->bridge_keys[0], d_ct, 1, count, count, d_out, (hipStream_t)stream);
 }
 
 int fhe_bridge_rows_batch(fhe_ctx* ctx, uint64_t* d_ct, int64_t Q, int64_t B, int64_t B_old, void* stream) {
@@ -2577,7 +2671,161 @@ int fhe_bridge_rows_batch(fhe_ctx* ctx, uint64_t* d_ct, int64_t Q, int64_t B, in
   int rc = need_bridge_key(ctx);
   if (rc) return rc;
   if (B_old == 0) return FHE_OK;
-  return bridge_impl(ctx, d_ct, Q, B, B_old, d_ct, (hipStream_t)stream);
+  return bridge_impl(ctx, ctx->bridge_keys[0], d_ct, Q, B, B_old, d_ct, (hipStream_t)stream);
+}
+
+// ---- several old generations resident: the generation row map (§8.17) -----
+#ifndef FHEICP_GRP_BRIDGE
+#define FHEICP_GRP_BRIDGE 1  // 0: one single-key bridge per generation behind the same entries (A/B builds,
+                             // tools/build_variant.sh NAME -DFHEICP_GRP_BRIDGE=0; the fallback)
+#endif
+// the row map's argument checks: FHE_E_ARG, on host-only contexts too
+static int gens_args(fhe_ctx* ctx, int64_t B, int32_t G, const int64_t* h_ends, const int32_t* h_slots) {
+  if (G < 0 || G > FHE_BRIDGE_SLOTS)
+    return fail(ctx, FHE_E_ARG, "bad bridge generations arguments (G outside [0, " +
+                                    std::to_string(FHE_BRIDGE_SLOTS) + "])");
+  if (G > 0 && (!h_ends || !h_slots)) return fail(ctx, FHE_E_ARG, "null bridge generations tables");
+  int64_t prev = 0;
+  uint32_t seen = 0;
+  for (int g = 0; g < G; ++g) {
+    if (h_ends[g] < prev || h_ends[g] > B)
+      return fail(ctx, FHE_E_ARG, "bad bridge generations arguments (ends must not decrease and stay within [0, B])");
+    prev = h_ends[g];
+    int rc = slot_arg(ctx, h_slots[g]);
+    if (rc) return rc;
+    if (seen >> h_slots[g] & 1)
+      return fail(ctx, FHE_E_ARG, "bad bridge generations arguments (bridge slot " + std::to_string(h_slots[g]) +
+                                      " named twice)");
+    seen |= 1u << h_slots[g];
+  }
+  return FHE_OK;
+}
+// blocks of 128 rows and digit groups of 16 rows over the generations' segments
+struct GensCount {
+  int64_t nblk = 0, ndg = 0, rows = 0;
+};
+static GensCount gens_count(int64_t Q, int32_t G, const int64_t* h_ends) {
+  GensCount c;
+  for (int g = 0; g < G; ++g) {
+    const int64_t n = Q * (h_ends[g] - (g ? h_ends[g - 1] : 0));
+    c.nblk += (n + KSM_CTS - 1) / KSM_CTS;
+    c.ndg += (n + 15) / 16;
+    c.rows += n;
+  }
+  return c;
+}
+// After the device check and before anything is queued: every named slot with
+// rows holds a key (FHE_E_STATE naming the slot), those keys share one gadget
+// (FHE_E_STATE), and the launch limits hold (FHE_E_ARG; the group form's over
+// all generations, the loop's per generation).
+static int gens_ready(fhe_ctx* ctx, int64_t Q, int32_t G, const int64_t* h_ends, const int32_t* h_slots) {
+  const GadgetKey* first = nullptr;
+  for (int g = 0; g < G; ++g) {
+    const int64_t n = h_ends[g] - (g ? h_ends[g - 1] : 0);
+    if (n == 0) continue;
+    int rc = need_bridge_slot(ctx, h_slots[g]);
+    if (rc) return rc;
+    const GadgetKey& k = ctx->bridge_keys[h_slots[g]];
+    if (!first) first = &k;
+    if (k.beta != first->beta || k.level != first->level)
+      return fail(ctx, FHE_E_STATE, "bridge gadgets differ: slot " + std::to_string(h_slots[g]) + " holds (" +
+                                        std::to_string(k.beta) + ", " + std::to_string(k.level) +
+                                        "), an earlier generation's slot (" + std::to_string(first->beta) + ", " +
+                                        std::to_string(first->level) + ")");
+    if (!FHEICP_GRP_BRIDGE && (Q * n + 15) / 16 > 65535)
+      return fail(ctx, FHE_E_ARG, "bridge batch too large: split the call");
+  }
+  const GensCount c = gens_count(Q, G, h_ends);
+  if (FHEICP_GRP_BRIDGE && (c.ndg > 65535 || 8 * c.nblk > 65535))
+    return fail(ctx, FHE_E_ARG, "bridge batch too large (more than 65535 digit groups of 16 rows, or 8191 blocks of "
+                                "128 rows, over all generations): split the call");
+  return FHE_OK;
+}
+// The bridge of every generation's rows of d_ct (Q x B big LWEs, in place),
+// after gens_args and gens_ready. Group form: the tables (one launch each for
+// the host's values and the block table), k_bridge_digits_grp, the group GEMM
+// and k_bridge_scatter_grp; bridge_ws holds
+//   starts | ends | the generation table | the key table | the block table |
+//   digits | bodies | the compact result.
+static int bridge_gens_impl(fhe_ctx* ctx, uint64_t* d_ct, int64_t Q, int64_t B, int32_t G, const int64_t* h_ends,
+                            const int32_t* h_slots, hipStream_t st) {
+  const fhe_params& p = ctx->p;
+  const GensCount c = gens_count(Q, G, h_ends);
+  if (c.rows == 0) return FHE_OK;
+  const int big = p.k * p.N;
+  if (!FHEICP_GRP_BRIDGE) {
+    for (int g = 0; g < G; ++g) {
+      const int64_t d0 = g ? h_ends[g - 1] : 0, n = h_ends[g] - d0;
+      if (n == 0) continue;
+      // the single bridge's row map on the rows from document d0 on: row q B + j there is row q B + d0 + j here
+      u64* base = d_ct + (size_t)d0 * (big + 1);
+      int rc = bridge_impl(ctx, ctx->bridge_keys[h_slots[g]], base, Q, B, n, base, st);
+      if (rc) return rc;
+    }
+    return FHE_OK;
+  }
+  BridgeGensArg a{};
+  const GadgetKey* key0 = nullptr;
+  int64_t start = 0;
+  for (int g = 0; g < G; ++g) {
+    const int64_t d0 = g ? h_ends[g - 1] : 0, n = h_ends[g] - d0;
+    a.start[g] = start;
+    a.n[g] = n;
+    a.doc0[g] = d0;
+    a.planes[g] = ctx->bridge_keys[h_slots[g]].planes;  // an empty generation's is never read
+    if (n && !key0) key0 = &ctx->bridge_keys[h_slots[g]];
+    start += Q * n;
+  }
+  const int levels = key0->level;
+  const int K = big * levels, KB = K / 64, n1 = big + 1, NB = (n1 + KSM_NB_COLS - 1) / KSM_NB_COLS;
+  const size_t tbytes = ((size_t)G * (16 + sizeof(BridgeGen) + 8) + 15) / 16 * 16;
+  const size_t kbytes = (sizeof(KsGrpBlock) * (size_t)c.nblk + 15) / 16 * 16;
+  const size_t dbytes = (size_t)c.ndg * 16 * K, bbytes = (8 * (size_t)c.rows + 15) / 16 * 16;
+  const size_t need = tbytes + kbytes + dbytes + bbytes + 8 * (size_t)c.rows * n1;
+  int rc = reserve(ctx, ctx->bridge_ws, need, FHE_E_DEVICE, "hipMalloc of the bridge workspace failed");
+  if (rc) return rc;
+  char* w = (char*)ctx->bridge_ws.p;
+  int64_t* se = (int64_t*)w;
+  BridgeGen* gen = (BridgeGen*)(se + 2 * G);
+  const void** keys = (const void**)(gen + G);
+  KsGrpBlock* blk = (KsGrpBlock*)(w + tbytes);
+  uint32_t* Dg = (uint32_t*)(w + tbytes + kbytes);
+  u64* body = (u64*)(w + tbytes + kbytes + dbytes);
+  u64* M = (u64*)(w + tbytes + kbytes + dbytes + bbytes);
+  // the single bridge's split rule on the launch's blocks x column blocks
+  const auto [S, kslice] = ksm_split(KB, c.nblk * NB, 512);
+  hipEvent_t e1;
+  prof_begin(ctx, ctx->prof_bridge, st, &e1);
+  hipLaunchKernelGGL(k_bridge_grp_setup, dim3(1), dim3(64), 0, st, a, (int)G, Q, se, gen, keys);
+  hipLaunchKernelGGL(k_ks_grp_tables, dim3((unsigned)((c.nblk + 255) / 256)), dim3(256), 0, st, (const int64_t*)se,
+                     (int)G, c.nblk, blk);
+  // the digits kernel also zeroes the compact rows the split's atomics add into
+  hipLaunchKernelGGL(k_bridge_digits_grp, dim3((unsigned)(big / 64), (unsigned)(8 * c.nblk)), dim3(256), 0, st, d_ct,
+                     (const KsGrpBlock*)blk, (const BridgeGen*)gen, B, big, key0->beta, levels, KB, Dg, body,
+                     S > 1 ? n1 : 0, M);
+  ctx->prof_bridge.kernel = "k_keyswitch_mfma_grp<8, 1>";
+  hipLaunchKernelGGL((k_keyswitch_mfma_grp<8, 1>), dim3((unsigned)(c.nblk * NB * S)), dim3(256), 0, st,
+                     (const v4i*)Dg, (const v4i* const*)keys, (const KsGrpBlock*)blk, (const u64*)body, n1, NB, KB, 0,
+                     S, kslice, M);
+  hipLaunchKernelGGL(k_bridge_scatter_grp, dim3((unsigned)(8 * c.nblk), (unsigned)((n1 + 255) / 256)), dim3(256), 0,
+                     st, (const u64*)M, (const KsGrpBlock*)blk, (const BridgeGen*)gen, B, n1, d_ct);
+  prof_end(ctx, ctx->prof_bridge, st, e1, c.rows);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+int fhe_bridge_gens_batch(fhe_ctx* ctx, uint64_t* d_ct, int64_t Q, int64_t B, int32_t G, const int64_t* h_ends,
+                          const int32_t* h_slots, void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  // argument errors first: a host-only context reports them too
+  if (Q < 1 || B < 1 || Q > 0x7fffffffLL || B > 0x7fffffffLL || Q * B > 0x7fffffffLL)
+    return fail(ctx, FHE_E_ARG, "bad bridge generations arguments (Q < 1, B < 1 or Q*B >= 2^31)");
+  int rc = gens_args(ctx, B, G, h_ends, h_slots);
+  if (rc) return rc;
+  if (!d_ct) return fail(ctx, FHE_E_ARG, "null bridge buffers");
+  if ((rc = need_device(ctx))) return rc;
+  if ((rc = gens_ready(ctx, Q, G, h_ends, h_slots))) return rc;
+  return bridge_gens_impl(ctx, d_ct, Q, B, G, h_ends, h_slots, (hipStream_t)stream);
 }
 
 // The leveled part of a private-query search, shared by the single-party
@@ -2875,7 +3123,37 @@ int fhe_search_seeded_queries_bridged_batch(fhe_ctx* ctx, const uint64_t* d_body
   int64_t* d_T;
   rc = seeded_queries_leveled(ctx, d_body, d_id0, B, D, h_mask_key, Q, d_W, cst, h_T, true, &w, &d_T, stream);
   if (rc) return rc;
-  if (B_old > 0 && (rc = bridge_impl(ctx, w.ctv, Q, B, B_old, w.ctv, (hipStream_t)stream))) return rc;
+  if (B_old > 0 && (rc = bridge_impl(ctx, ctx->bridge_keys[0], w.ctv, Q, B, B_old, w.ctv, (hipStream_t)stream)))
+    return rc;
+  return post_leveled_search(ctx, w, Q * B, levels_bit, d_glwe_acc, d_glwe_bit, stream);
+}
+
+// The same entry with several old generations resident:
+// the generation row map (G, h_ends, h_slots) in B_old's place; documents
+// b >= h_ends[G - 1] are under the current key. G = 0: no bridge, no bridge
+// key needed.
+int fhe_search_seeded_queries_gens_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t B,
+                                         int32_t D, const uint32_t h_mask_key[8], int64_t Q, const int64_t* d_W,
+                                         int64_t cst, const int64_t* h_T, int32_t levels_bit, int32_t G,
+                                         const int64_t* h_ends, const int32_t* h_slots, uint64_t* d_glwe_acc,
+                                         uint64_t* d_glwe_bit, void* stream) {
+  int rc = seeded_queries_args(ctx, Q, B, D);  // argument errors first: a host-only context reports them too
+  if (rc) return rc;
+  if (levels_bit < 0 || levels_bit > 8)
+    return fail(ctx, FHE_E_ARG, "bad search seeded queries arguments (levels_bit outside [0, 8])");
+  if (!d_body || !d_id0 || !h_mask_key || !d_W || !h_T || !d_glwe_acc || !d_glwe_bit)
+    return fail(ctx, FHE_E_ARG, "null search seeded queries arguments");
+  if ((rc = gens_args(ctx, B, G, h_ends, h_slots))) return rc;
+  if ((rc = need_eval_keys(ctx))) return rc;
+  if ((rc = need_pack_key(ctx))) return rc;
+  if ((rc = gens_ready(ctx, Q, G, h_ends, h_slots))) return rc;
+  if (levels_bit > ctx->pack_key.level)
+    return fail(ctx, FHE_E_ARG, "search seeded queries levels_bit exceeds the packing key's levels");
+  QueryWs w;
+  int64_t* d_T;
+  rc = seeded_queries_leveled(ctx, d_body, d_id0, B, D, h_mask_key, Q, d_W, cst, h_T, true, &w, &d_T, stream);
+  if (rc) return rc;
+  if ((rc = bridge_gens_impl(ctx, w.ctv, Q, B, G, h_ends, h_slots, (hipStream_t)stream))) return rc;
   return post_leveled_search(ctx, w, Q * B, levels_bit, d_glwe_acc, d_glwe_bit, stream);
 }
 
@@ -3449,9 +3727,9 @@ static KeyRows ksk_rows(const fhe_ctx* ctx) {
   const fhe_params& p = ctx->p;
   return {ctx->ksk, (int64_t)p.k * p.N * p.ks_level, p.n + 1, 1, TAG_KSK_MASK};
 }
-static KeyRows gadget_rows(const fhe_ctx* ctx, const GadgetDesc& d, int L) {
+static KeyRows gadget_rows(fhe_ctx* ctx, const GadgetDesc& d, int L) {
   const fhe_params& p = ctx->p;
-  return {(ctx->*d.key).key, (int64_t)p.k * p.N * L, d.n1(p), d.body(p), d.tag_mask};
+  return {d.key(ctx).key, (int64_t)p.k * p.N * L, d.n1(p), d.body(p), d.tag_mask};
 }
 static int sk_reserve(fhe_ctx* ctx, size_t words) {
   return reserve(ctx, ctx->sk_ws, 8 * words, FHE_E_DEVICE, "hipMalloc of the seeded keys' staging buffer failed");
@@ -3538,9 +3816,11 @@ int fhe_keygen_pack_key_seeded(fhe_ctx* ctx, int32_t base_log, int32_t level, co
   return FHE_OK;
 }
 
-int fhe_keygen_bridge_key_seeded(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level,
-                                 const uint32_t h_mask_key[8], const uint32_t h_noise_key[8], void* stream) {
-  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+// the seeded bridge keygen of a slot; the mask key reuse refusal covers every
+// slot of the context (used_masks is the context's)
+static int keygen_bridge_key_seeded_at(fhe_ctx* ctx, int32_t slot, const uint64_t* h_s_big_old, int32_t base_log,
+                                       int32_t level, const uint32_t h_mask_key[8], const uint32_t h_noise_key[8],
+                                       void* stream) {
   int rc = seeded_arg(ctx, gadget_args(ctx, BRIDGE_KEY, base_log, level));
   if (rc) return rc;
   ChaKey Km, Kn;
@@ -3548,11 +3828,24 @@ int fhe_keygen_bridge_key_seeded(fhe_ctx* ctx, const uint64_t* h_s_big_old, int3
   if ((rc = bridge_keygen_args(ctx, h_s_big_old, keys_ok, "seeded: "))) return rc;
   if ((rc = mask_reuse(ctx, BRIDGE_KEY, Km))) return rc;
   if ((rc = need_secret(ctx))) return rc;
-  if ((rc = keygen_bridge_impl(ctx, h_s_big_old, base_log, level, Km, Kn, (hipStream_t)stream))) return rc;
-  ctx->bridge_key.seeded = true;
-  ctx->bridge_key.mask = Km;
+  if ((rc = keygen_bridge_impl(ctx, slot, h_s_big_old, base_log, level, Km, Kn, (hipStream_t)stream))) return rc;
+  ctx->bridge_keys[slot].seeded = true;
+  ctx->bridge_keys[slot].mask = Km;
   note_mask(ctx, Km);
   return FHE_OK;
+}
+int fhe_keygen_bridge_key_seeded(fhe_ctx* ctx, const uint64_t* h_s_big_old, int32_t base_log, int32_t level,
+                                 const uint32_t h_mask_key[8], const uint32_t h_noise_key[8], void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  return keygen_bridge_key_seeded_at(ctx, 0, h_s_big_old, base_log, level, h_mask_key, h_noise_key, stream);
+}
+int fhe_keygen_bridge_key_slot_seeded(fhe_ctx* ctx, int32_t slot, const uint64_t* h_s_big_old, int32_t base_log,
+                                      int32_t level, const uint32_t h_mask_key[8], const uint32_t h_noise_key[8],
+                                      void* stream) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  int rc = slot_arg(ctx, slot);
+  if (rc) return rc;
+  return keygen_bridge_key_seeded_at(ctx, slot, h_s_big_old, base_log, level, h_mask_key, h_noise_key, stream);
 }
 
 int fhe_export_eval_keys_seeded(fhe_ctx* ctx, uint32_t h_mask_key_out[8], uint64_t* h_bsk_body, uint64_t* h_ksk_body,
@@ -3622,7 +3915,7 @@ static int gadget_key_export_seeded(fhe_ctx* ctx, const GadgetDesc& d, uint32_t*
     return fail(ctx, FHE_E_ARG, "seeded " + std::string(d.noun) + " key export: null buffer");
   int rc = need_gadget_key(ctx, d);
   if (rc) return rc;
-  const GadgetKey& k = ctx->*d.key;
+  const GadgetKey& k = d.key(ctx);
   if (!k.seeded)
     return fail(ctx, FHE_E_STATE, "the " + std::string(d.noun) + " key was not generated or imported seeded: no mask "
                                   "key (fhe_keygen_" + d.abi + "_key_seeded, fhe_import_" + d.abi + "_key_seeded)");
@@ -3643,7 +3936,7 @@ static int gadget_key_import_seeded(fhe_ctx* ctx, const GadgetDesc& d, int32_t b
   if ((rc = gadget_key_alloc(ctx, d, L))) return rc;
   if ((rc = import_bodies(ctx, Km, gadget_rows(ctx, d, L), h_body))) return rc;
   if ((rc = gadget_key_planes(ctx, d, beta, L, nullptr))) return rc;
-  GadgetKey& k = ctx->*d.key;
+  GadgetKey& k = d.key(ctx);
   k.seeded = true;
   k.mask = Km;
   return sk_release(ctx);
@@ -3653,6 +3946,19 @@ int fhe_export_pack_key_seeded(fhe_ctx* ctx, uint32_t h_mask_key_out[8], uint64_
 }
 int fhe_export_bridge_key_seeded(fhe_ctx* ctx, uint32_t h_mask_key_out[8], uint64_t* h_body) {
   return gadget_key_export_seeded(ctx, BRIDGE_KEY, h_mask_key_out, h_body);
+}
+int fhe_export_bridge_key_slot_seeded(fhe_ctx* ctx, int32_t slot, uint32_t h_mask_key_out[8], uint64_t* h_body) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  int rc = slot_arg(ctx, slot);
+  if (rc) return rc;
+  return gadget_key_export_seeded(ctx, bridge_slot(slot), h_mask_key_out, h_body);
+}
+int fhe_import_bridge_key_slot_seeded(fhe_ctx* ctx, int32_t slot, int32_t base_log, int32_t level,
+                                      const uint32_t h_mask_key[8], const uint64_t* h_body) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  int rc = slot_arg(ctx, slot);
+  if (rc) return rc;
+  return gadget_key_import_seeded(ctx, bridge_slot(slot), base_log, level, h_mask_key, h_body);
 }
 int fhe_import_pack_key_seeded(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint32_t h_mask_key[8],
                                const uint64_t* h_body) {
@@ -4442,7 +4748,7 @@ int fhe_search_seeded_queries_group_batch(fhe_group* g, const fhe_group_corpus* 
     if ((rc = store_scaled_csts(ctx, dcs, c.Q, nullptr, c.cst, c.h_T, st))) return rc;
     if ((rc = linear_seeded_queries_launch(ctx, c.d_body, c.d_id0, c.B, c.D, c.h_mask_key, c.Q, c.d_W, dcs, seg, st)))
       return rc;
-    if (c.B_old > 0 && (rc = bridge_impl(ctx, seg, c.Q, c.B, c.B_old, seg, st))) return rc;
+    if (c.B_old > 0 && (rc = bridge_impl(ctx, ctx->bridge_keys[0], seg, c.Q, c.B, c.B_old, seg, st))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(cpy + (size_t)starts[t] * Wb, seg, 8 * (size_t)counts[t] * Wb, hipMemcpyDeviceToDevice, st));
   }
   if ((rc = grp_sign(g, ctv, counts.data(), starts.data(), M, sgn, small, g->ws.p, st))) return rc;

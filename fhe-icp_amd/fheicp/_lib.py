@@ -17,6 +17,7 @@ LIB_PATH = Path(os.environ.get("FHEICP_LIB") or Path(__file__).resolve().parent 
 
 FHE_OK = 0
 ERRORS = {-1: "FHE_E_ARG", -2: "FHE_E_DEVICE", -3: "FHE_E_STATE", -4: "FHE_E_NOMEM"}
+BRIDGE_SLOTS = 8  # FHE_BRIDGE_SLOTS (include/fhe_icp.h): bridge keys a context holds
 
 PARAM_FIELDS = ("n", "k", "N", "pbs_base_log", "pbs_level", "ks_base_log", "ks_level",
                 "lwe_noise_bits", "glwe_noise_bits", "msg_bits", "sign_digit_bits",
@@ -181,6 +182,18 @@ SIGNATURES = [
     ("fhe_bridge_rows_batch", C.c_int, [_CTXP, _vp, _i64, _i64, _i64, _vp]),
     ("fhe_search_seeded_queries_bridged_batch", C.c_int, [_CTXP, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32,
                                                           _i64, _vp, _vp, _vp]),
+    # several old generations resident: bridge slots and the generation row map
+    ("fhe_keygen_bridge_key_slot_key", C.c_int, [_CTXP, _i32, _vp, _i32, _i32, _vp, _vp]),
+    ("fhe_keygen_bridge_key_slot", C.c_int, [_CTXP, _i32, _vp, _i32, _i32, _u64, _vp]),
+    ("fhe_export_bridge_key_slot", C.c_int, [_CTXP, _i32, _vp]),
+    ("fhe_import_bridge_key_slot", C.c_int, [_CTXP, _i32, _i32, _i32, _vp]),
+    ("fhe_drop_bridge_key_slot", C.c_int, [_CTXP, _i32]),
+    ("fhe_bridge_gens_batch", C.c_int, [_CTXP, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    ("fhe_search_seeded_queries_gens_batch", C.c_int, [_CTXP, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32,
+                                                       _i32, _vp, _vp, _vp, _vp, _vp]),
+    ("fhe_keygen_bridge_key_slot_seeded", C.c_int, [_CTXP, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
+    ("fhe_export_bridge_key_slot_seeded", C.c_int, [_CTXP, _i32, _vp, _vp]),
+    ("fhe_import_bridge_key_slot_seeded", C.c_int, [_CTXP, _i32, _i32, _i32, _vp, _vp]),
     ("fhe_glwe_docs_queries_bytes", C.c_size_t, [_P, _i64, _i32, _i32]),
     ("fhe_glwe_docs_queries_pack", C.c_int, [_CTXP, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     ("fhe_ggsws_ws_bytes", C.c_size_t, [_P, _i64, _i64, _i32, _i32]),

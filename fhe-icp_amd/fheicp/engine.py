@@ -47,6 +47,7 @@ class Engine:
         self.has_keys = False
         self.pack_gadget = None   # (base_log, level) of the packing key, once one is generated or imported
         self.bridge_gadget = None  # (base_log, level) of the bridge key (§8.12), once one is generated or imported
+        self.slot_gadgets = {}     # the same for bridge slots 1.. (§8.17); slot 0 is bridge_gadget
 
     def close(self) -> None:
         if getattr(self, "_ctx", None):
@@ -483,48 +484,82 @@ class Engine:
     def bridge_key_words(self, base_log: int, level: int) -> int:
         return int(self._L.fhe_bridge_key_words(C.byref(self._P), int(base_log), int(level)))
 
+    def bridge_gadget_of(self, slot: int = 0):
+        """(base_log, level) of the bridge key in `slot`, None for an empty slot."""
+        return self.bridge_gadget if int(slot) == 0 else self.slot_gadgets.get(int(slot))
+
+    def _set_bridge_gadget(self, slot: int, gadget) -> None:
+        if int(slot) == 0:
+            self.bridge_gadget = gadget
+        elif gadget is None:
+            self.slot_gadgets.pop(int(slot), None)
+        else:
+            self.slot_gadgets[int(slot)] = gadget
+
+    def bridge_slots(self) -> list:
+        """The bridge slots that hold a key, ascending."""
+        return ([0] if self.bridge_gadget else []) + sorted(self.slot_gadgets)
+
     def keygen_bridge_key(self, s_big_old, base_log: int, level: int, key=None, seed: int | None = None,
-                          mask_key=None) -> None:
+                          mask_key=None, slot: int = 0) -> None:
         """Generate the bridge key from the old big key s_big_old (kN words of
         0/1, export_keys()["s_big"] of the old context) to this context's
         secret (fhe_keygen_bridge_key[_key]); `key` is a 256-bit ChaCha20 key
         (os.urandom when neither is given), `seed` the 64-bit test form. With
         mask_key (this bridge key's own, or True for a fresh one) the key is
-        seeded (fhe_keygen_bridge_key_seeded, §8.16)."""
+        seeded (fhe_keygen_bridge_key_seeded, §8.16). slot > 0: into that
+        bridge slot (the *_slot entries, §8.17)."""
         s = np.ascontiguousarray(s_big_old, dtype=np.uint64).reshape(-1)
         if s.size != self.big:
             raise ValueError(f"the old big key holds {s.size} words, these parameters {self.big}")
         sp = C.c_void_p(s.ctypes.data)
+        slot = int(slot)
+        at = (slot,) if slot else ()
+        L = self._L
         if mask_key is not None and mask_key is not False:
             import os
             noise = self.key_from_seed(seed) if seed is not None else (key if key is not None else os.urandom(32))
-            rc = self._L.fhe_keygen_bridge_key_seeded(self._ctx, sp, int(base_log), int(level),
-                                                      self._key(self._fresh(mask_key)), self._key(noise),
-                                                      _stream(self.device))
+            fn = L.fhe_keygen_bridge_key_slot_seeded if slot else L.fhe_keygen_bridge_key_seeded
+            rc = fn(self._ctx, *at, sp, int(base_log), int(level), self._key(self._fresh(mask_key)), self._key(noise),
+                    _stream(self.device))
         elif seed is not None:
-            rc = self._L.fhe_keygen_bridge_key(self._ctx, sp, int(base_log), int(level), C.c_uint64(seed),
-                                               _stream(self.device))
+            fn = L.fhe_keygen_bridge_key_slot if slot else L.fhe_keygen_bridge_key
+            rc = fn(self._ctx, *at, sp, int(base_log), int(level), C.c_uint64(seed), _stream(self.device))
         else:
             import os
-            rc = self._L.fhe_keygen_bridge_key_key(self._ctx, sp, int(base_log), int(level),
-                                                   self._key(key if key is not None else os.urandom(32)),
-                                                   _stream(self.device))
+            fn = L.fhe_keygen_bridge_key_slot_key if slot else L.fhe_keygen_bridge_key_key
+            rc = fn(self._ctx, *at, sp, int(base_log), int(level),
+                    self._key(key if key is not None else os.urandom(32)), _stream(self.device))
         self._chk(rc)
-        self.bridge_gadget = (int(base_log), int(level))
+        self._set_bridge_gadget(slot, (int(base_log), int(level)))
 
-    def export_bridge_key(self) -> np.ndarray:
-        if not self.bridge_gadget:
-            raise _lib.FheError("FHE_E_STATE: no bridge key")
-        out = np.zeros(self.bridge_key_words(*self.bridge_gadget), np.uint64)
-        self._chk(self._L.fhe_export_bridge_key(self._ctx, C.c_void_p(out.ctypes.data)))
+    def export_bridge_key(self, slot: int = 0) -> np.ndarray:
+        slot = int(slot)
+        if not self.bridge_gadget_of(slot):
+            raise _lib.FheError("FHE_E_STATE: no bridge key" + (f" in slot {slot}" if slot else ""))
+        out = np.zeros(self.bridge_key_words(*self.bridge_gadget_of(slot)), np.uint64)
+        if slot:
+            self._chk(self._L.fhe_export_bridge_key_slot(self._ctx, slot, C.c_void_p(out.ctypes.data)))
+        else:
+            self._chk(self._L.fhe_export_bridge_key(self._ctx, C.c_void_p(out.ctypes.data)))
         return out
 
-    def import_bridge_key(self, base_log: int, level: int, key) -> None:
+    def import_bridge_key(self, base_log: int, level: int, key, slot: int = 0) -> None:
         a = np.ascontiguousarray(key, dtype=np.uint64)
         if a.size != self.bridge_key_words(base_log, level):
             raise ValueError("bridge key size does not match its gadget and these parameters")
-        self._chk(self._L.fhe_import_bridge_key(self._ctx, int(base_log), int(level), C.c_void_p(a.ctypes.data)))
-        self.bridge_gadget = (int(base_log), int(level))
+        slot = int(slot)
+        if slot:
+            self._chk(self._L.fhe_import_bridge_key_slot(self._ctx, slot, int(base_log), int(level),
+                                                         C.c_void_p(a.ctypes.data)))
+        else:
+            self._chk(self._L.fhe_import_bridge_key(self._ctx, int(base_log), int(level), C.c_void_p(a.ctypes.data)))
+        self._set_bridge_gadget(slot, (int(base_log), int(level)))
+
+    def drop_bridge_key(self, slot: int) -> None:
+        """fhe_drop_bridge_key_slot: frees the slot's key (an empty slot: nothing to do)."""
+        self._chk(self._L.fhe_drop_bridge_key_slot(self._ctx, int(slot)))
+        self._set_bridge_gadget(int(slot), None)
 
     def bridge(self, ct: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         """Big LWEs under the old key -> under this context's key
@@ -541,6 +576,26 @@ class Engine:
         if ct.numel() < int(Q) * int(B) * self.W:
             raise ValueError(f"{ct.numel() // self.W} ciphertexts for {Q} x {B} rows")
         self._chk(self._L.fhe_bridge_rows_batch(self._ctx, _ptr(ct), int(Q), int(B), int(b_old),
+                                                _stream(self.device)))
+        return ct
+
+    @staticmethod
+    def _gens(ends, slots):
+        """The generation row map as host tables: (G, int64[G], int32[G])."""
+        ends, slots = [int(e) for e in ends], [int(s) for s in slots]
+        if len(ends) != len(slots):
+            raise ValueError(f"{len(ends)} generation ends for {len(slots)} bridge slots")
+        G = len(ends)
+        return G, (C.c_int64 * max(G, 1))(*ends), (C.c_int32 * max(G, 1))(*slots)
+
+    def bridge_gens(self, ct: torch.Tensor, Q: int, B: int, ends, slots) -> torch.Tensor:
+        """fhe_bridge_gens_batch: in place on a query-major Q x B result whose
+        documents ends[g - 1] <= b < ends[g] are under old generation g,
+        bridged by slot slots[g] (§8.17)."""
+        if ct.numel() < int(Q) * int(B) * self.W:
+            raise ValueError(f"{ct.numel() // self.W} ciphertexts for {Q} x {B} rows")
+        G, he, hs = self._gens(ends, slots)
+        self._chk(self._L.fhe_bridge_gens_batch(self._ctx, _ptr(ct), int(Q), int(B), G, he, hs,
                                                 _stream(self.device)))
         return ct
 
@@ -561,23 +616,33 @@ class Engine:
                                                      C.c_void_p(a.ctypes.data)))
         self.pack_gadget = (int(base_log), int(level))
 
-    def export_bridge_key_seeded(self):
+    def export_bridge_key_seeded(self, slot: int = 0):
         """(mask key u32[8], bodies) of a seeded bridge key (fhe_export_bridge_key_seeded)."""
-        if not self.bridge_gadget:
-            raise _lib.FheError("FHE_E_STATE: no bridge key")
+        slot = int(slot)
+        if not self.bridge_gadget_of(slot):
+            raise _lib.FheError("FHE_E_STATE: no bridge key" + (f" in slot {slot}" if slot else ""))
         mk = np.zeros(8, np.uint32)
-        out = np.zeros(self._L.fhe_bridge_key_body_words(C.byref(self._P), *self.bridge_gadget), np.uint64)
-        self._chk(self._L.fhe_export_bridge_key_seeded(self._ctx, C.c_void_p(mk.ctypes.data),
-                                                       C.c_void_p(out.ctypes.data)))
+        out = np.zeros(self._L.fhe_bridge_key_body_words(C.byref(self._P), *self.bridge_gadget_of(slot)), np.uint64)
+        if slot:
+            self._chk(self._L.fhe_export_bridge_key_slot_seeded(self._ctx, slot, C.c_void_p(mk.ctypes.data),
+                                                                C.c_void_p(out.ctypes.data)))
+        else:
+            self._chk(self._L.fhe_export_bridge_key_seeded(self._ctx, C.c_void_p(mk.ctypes.data),
+                                                           C.c_void_p(out.ctypes.data)))
         return mk, out
 
-    def import_bridge_key_seeded(self, base_log: int, level: int, mask_key, body) -> None:
+    def import_bridge_key_seeded(self, base_log: int, level: int, mask_key, body, slot: int = 0) -> None:
         a = np.ascontiguousarray(body, dtype=np.uint64)
         if a.size != self._L.fhe_bridge_key_body_words(C.byref(self._P), int(base_log), int(level)):
             raise ValueError("bridge_key_body: size does not match its gadget and these parameters")
-        self._chk(self._L.fhe_import_bridge_key_seeded(self._ctx, int(base_log), int(level), self._key(mask_key),
-                                                       C.c_void_p(a.ctypes.data)))
-        self.bridge_gadget = (int(base_log), int(level))
+        slot = int(slot)
+        if slot:
+            self._chk(self._L.fhe_import_bridge_key_slot_seeded(self._ctx, slot, int(base_log), int(level),
+                                                                self._key(mask_key), C.c_void_p(a.ctypes.data)))
+        else:
+            self._chk(self._L.fhe_import_bridge_key_seeded(self._ctx, int(base_log), int(level), self._key(mask_key),
+                                                           C.c_void_p(a.ctypes.data)))
+        self._set_bridge_gadget(slot, (int(base_log), int(level)))
 
     def _export_eval_keys_seeded(self) -> dict:
         from .params import gadget_level
@@ -596,10 +661,56 @@ class Engine:
         if self.pack_gadget:
             out["pack_mask_key"], out["pack_key_body"] = self.export_pack_key_seeded()
             out["pack_gadget"] = np.array(self.pack_gadget, dtype=np.int64)
-        if self.bridge_gadget:
-            out["bridge_mask_key"], out["bridge_key_body"] = self.export_bridge_key_seeded()
-            out["bridge_gadget"] = np.array(self.bridge_gadget, dtype=np.int64)
+        self._export_bridges(out, True)
         return out
+
+    def _export_bridges(self, out: dict, seeded: bool) -> None:
+        """The bridge keys into an evaluation-key dict. Slot 0 alone: bridge_key
+        (bridge_mask_key / bridge_key_body), as ever. Further slots (§8.17):
+        bridge_keys [G, words] (bridge_mask_keys [G, 8] / bridge_key_bodies
+        [G, words]), the occupied slots in ascending order, and their one
+        bridge_gadget."""
+        slots = self.bridge_slots()
+        if not slots:
+            return
+        gadgets = {self.bridge_gadget_of(s) for s in slots}
+        if len(gadgets) != 1:
+            raise ValueError(f"the bridge slots hold different gadgets {sorted(gadgets)}: one dict carries one")
+        out["bridge_gadget"] = np.array(gadgets.pop(), dtype=np.int64)
+        if slots == [0]:
+            if seeded:
+                out["bridge_mask_key"], out["bridge_key_body"] = self.export_bridge_key_seeded()
+            else:
+                out["bridge_key"] = self.export_bridge_key()
+        elif seeded:
+            pairs = [self.export_bridge_key_seeded(s) for s in slots]
+            out["bridge_mask_keys"] = np.stack([mk for mk, _ in pairs])
+            out["bridge_key_bodies"] = np.stack([body for _, body in pairs])
+        else:
+            out["bridge_keys"] = np.stack([self.export_bridge_key(s) for s in slots])
+
+    def _import_bridges(self, d: dict) -> None:
+        """The multi-bridge entries of a dict (§8.17): row g into slot g;
+        every slot from G on is dropped."""
+        if "bridge_keys" not in d and "bridge_key_bodies" not in d:
+            return
+        b, L = (int(x) for x in np.asarray(d["bridge_gadget"]).reshape(2))
+        if "bridge_keys" in d:
+            rows = np.asarray(d["bridge_keys"])
+            rows = rows.reshape(-1, self.bridge_key_words(b, L))
+            if not 1 <= len(rows) <= _lib.BRIDGE_SLOTS:
+                raise ValueError(f"bridge_keys holds {len(rows)} keys, a context 1 to {_lib.BRIDGE_SLOTS}")
+            for g, row in enumerate(rows):
+                self.import_bridge_key(b, L, row, slot=g)
+        else:
+            masks = np.asarray(d["bridge_mask_keys"]).reshape(-1, 8)
+            rows = np.asarray(d["bridge_key_bodies"]).reshape(len(masks), -1)
+            if not 1 <= len(rows) <= _lib.BRIDGE_SLOTS:
+                raise ValueError(f"bridge_key_bodies holds {len(rows)} keys, a context 1 to {_lib.BRIDGE_SLOTS}")
+            for g, (mk, row) in enumerate(zip(masks, rows)):
+                self.import_bridge_key_seeded(b, L, mk, row, slot=g)
+        for s in [s for s in self.bridge_slots() if s >= len(rows)]:
+            self.drop_bridge_key(s)
 
     def export_eval_keys(self, seeded: bool = False) -> dict:
         """Everything a server needs and nothing more, as numpy arrays: bsk,
@@ -624,9 +735,7 @@ class Engine:
         if self.pack_gadget:
             out["pack_key"] = self.export_pack_key()
             out["pack_gadget"] = np.array(self.pack_gadget, dtype=np.int64)
-        if self.bridge_gadget:
-            out["bridge_key"] = self.export_bridge_key()
-            out["bridge_gadget"] = np.array(self.bridge_gadget, dtype=np.int64)
+        self._export_bridges(out, False)
         return out
 
     def _import_eval_keys_seeded(self, d: dict) -> None:
@@ -644,6 +753,7 @@ class Engine:
         if "bridge_key_body" in d:
             b, L = (int(x) for x in np.asarray(d["bridge_gadget"]).reshape(2))
             self.import_bridge_key_seeded(b, L, d["bridge_mask_key"], arr["bridge_key_body"])
+        self._import_bridges(d)
 
     def import_eval_keys(self, d: dict) -> None:
         """Install evaluation keys only (fhe_import_eval_keys; the packing key
@@ -671,6 +781,7 @@ class Engine:
         if "bridge_key" in d:
             b, L = (int(x) for x in np.asarray(d["bridge_gadget"]).reshape(2))
             self.import_bridge_key(b, L, d["bridge_key"])
+        self._import_bridges(d)
 
     def glwe_count(self, count: int) -> int:
         return -(-int(count) // self.params.N)
@@ -813,6 +924,26 @@ class Engine:
         self._chk(self._L.fhe_search_seeded_queries_batch(self._ctx, _ptr(body), _ptr(id0), int(B), int(D),
                                                           self._key(mask_key), Q, _ptr(W), int(cst), hT,
                                                           int(levels_bit), _ptr(ga), _ptr(gb), _stream(self.device)))
+        return ga, gb
+
+    def search_seeded_queries_gens(self, body: torch.Tensor, id0: torch.Tensor, mask_key, W: torch.Tensor, cst: int,
+                                   Ts, levels_bit: int = 0, gen_ends=(), gen_slots=()):
+        """fhe_search_seeded_queries_gens_batch: search_seeded_queries with
+        several old generations resident (§8.17): documents gen_ends[g - 1] <=
+        b < gen_ends[g] go through bridge slot gen_slots[g], the documents
+        after gen_ends[-1] are under the current key."""
+        B, D = body.shape
+        keep, hT = self._i64s(Ts)
+        Q = keep.size
+        if tuple(W.shape) != (Q, D):
+            raise ValueError(f"weights {tuple(W.shape)} for {Q} thresholds of {D} features")
+        G, he, hs = self._gens(gen_ends, gen_slots)
+        shape = (self.glwe_count(Q * B), (self.params.k + 1) * self.params.N)
+        ga = torch.empty(shape, dtype=torch.int64, device=self.device)
+        gb = torch.empty(shape, dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_search_seeded_queries_gens_batch(
+            self._ctx, _ptr(body), _ptr(id0), int(B), int(D), self._key(mask_key), Q, _ptr(W), int(cst), hT,
+            int(levels_bit), G, he, hs, _ptr(ga), _ptr(gb), _stream(self.device)))
         return ga, gb
 
     # ------------- both-private search: GGSW query x GLWE documents (§8.7) --
@@ -1093,7 +1224,8 @@ class Engine:
         return {"total_ms": ms.value, "launches": nl.value, "items": items.value}
 
 
-FULL_EVAL_KEYS = ("bsk", "ksk", "pack_key", "bridge_key") + tuple(f"gadget_bsk{g}" for g in (1, 2, 3, 4, 5))
+FULL_EVAL_KEYS = ("bsk", "ksk", "pack_key", "bridge_key", "bridge_keys") + \
+    tuple(f"gadget_bsk{g}" for g in (1, 2, 3, 4, 5))
 
 
 def eval_keys_seeded(d: dict) -> bool:
@@ -1108,7 +1240,7 @@ def eval_keys_seeded(d: dict) -> bool:
         for k in ("eval_mask_key", "ksk_body"):
             if k not in d:
                 raise ValueError(f"seeded evaluation keys without {k}")
-    elif any(k.endswith("_body") for k in d):
+    elif any(k.endswith("_body") or k == "bridge_key_bodies" for k in d):
         raise ValueError("evaluation keys mix the seeded and the full form: bodies without bsk_body")
     return seeded
 
@@ -1132,6 +1264,17 @@ def seeded_eval_key_sizes(params: SchemeParams, d: dict) -> dict:
             b, lv = (int(x) for x in np.asarray(d[f"{name}_gadget"]).reshape(2))
             want[f"{name}_key_body"] = fn(C.byref(P), b, lv)
             masks.append(f"{name}_mask_key")
+    if "bridge_key_bodies" in d:
+        if "bridge_gadget" not in d or "bridge_mask_keys" not in d:
+            raise ValueError("bridge_key_bodies without bridge_gadget or bridge_mask_keys")
+        b, lv = (int(x) for x in np.asarray(d["bridge_gadget"]).reshape(2))
+        per = L.fhe_bridge_key_body_words(C.byref(P), b, lv)
+        G = np.asarray(d["bridge_mask_keys"]).size // 8
+        if per == 0 or np.asarray(d["bridge_mask_keys"]).size != 8 * G or not 1 <= G <= _lib.BRIDGE_SLOTS or \
+                np.asarray(d["bridge_key_bodies"]).size != G * per:
+            raise ValueError(f"bridge_key_bodies: {np.asarray(d['bridge_key_bodies']).size} words and "
+                             f"{np.asarray(d['bridge_mask_keys']).size} mask key words do not match 1 to "
+                             f"{_lib.BRIDGE_SLOTS} keys of {per} words")
     for k, n in want.items():
         if k not in d:
             raise ValueError(f"seeded evaluation keys without {k} (these parameters have it)")

@@ -134,7 +134,7 @@ class CorpusClient:
             self._key_id = key_fingerprint(self.corpus.engine.export_key("ksk"))
         return self._key_id
 
-    def rotate(self, key_seed=None, count: int | None = None, bridge_from: "CorpusClient | None" = None,
+    def rotate(self, key_seed=None, count: int | None = None, bridge_from=None,
                device: int | None = None, pack_seed=None, bridge_seed=None, noise_seed=None) -> "CorpusClient":
         """Key rotation without re-encryption -> the next
         generation's client: a new EncryptedCorpus with the same CorpusQuant,
@@ -145,10 +145,29 @@ class CorpusClient:
         default stream ids continue after this client's. The *_seed arguments
         are the 64-bit test forms. When this client's keys are seeded (§8.16)
         so are the new generation's and its bridge key, under mask keys of
-        their own."""
+        their own.
+
+        bridge_from may also be a SEQUENCE of clients, oldest first: every
+        generation whose documents are still resident. The
+        new client then holds one DIRECT bridge key per client, each under its
+        own fresh keys (bridge_seed + i in the test form), one gadget for all,
+        and its eval_keys() carry bridge_from as an array of their
+        fingerprints and bridge_keys [G, words] (seeded: bridge_key_bodies and
+        bridge_mask_keys). A row still passes one bridge, so the packing plan
+        is the single bridge's."""
         from .params import bridge_plan, bridge_var
-        src = self if bridge_from is None else bridge_from
-        src.corpus._need()
+        many = bridge_from is not None and not isinstance(bridge_from, CorpusClient)
+        srcs = list(bridge_from) if many else [self if bridge_from is None else bridge_from]
+        if many:
+            from ._lib import BRIDGE_SLOTS
+            if not 1 <= len(srcs) <= BRIDGE_SLOTS:
+                raise ValueError(f"bridge_from names {len(srcs)} generations, a context holds 1 to {BRIDGE_SLOTS} "
+                                 "bridge keys")
+            if len({c.key_id for c in srcs}) != len(srcs):
+                raise ValueError("bridge_from names a generation twice")
+        for c in srcs:
+            c.corpus._need()
+        src = srcs[0]
         old = src.corpus.engine
         scheme = self.corpus.scheme.with_msg_bits(self.P0)
         new_corpus = EncryptedCorpus(self.cq, self.corpus.scheme)
@@ -160,13 +179,15 @@ class CorpusClient:
         b, L = bridge_plan(scheme, self.in_var)
         new = CorpusClient(new_corpus, count=self.count if count is None else count, in_var=self.in_var,
                            pack_seed=pack_seed, extra_var=bridge_var(scheme, b, L) / 2.0 ** 128,
-                           next_id=max(self.id_end, src.id_end))
-        s_old = old.export_key("s_big")
-        new_corpus.engine.keygen_bridge_key(s_old, b, L, seed=bridge_seed,
-                                            mask_key=new_corpus.next_key_mask() if new_corpus.seeded_keys else None)
-        s_old[:] = 0
+                           next_id=max([self.id_end] + [c.id_end for c in srcs]))
+        for i, c in enumerate(srcs):
+            s_old = c.corpus.engine.export_key("s_big")
+            new_corpus.engine.keygen_bridge_key(
+                s_old, b, L, seed=None if bridge_seed is None else (int(bridge_seed) + i) % 2 ** 64,
+                mask_key=new_corpus.next_key_mask() if new_corpus.seeded_keys else None, slot=i)
+            s_old[:] = 0
         new.bridge_gadget = (b, L)
-        new.bridge_from = src.key_id
+        new.bridge_from = [c.key_id for c in srcs] if many else src.key_id
         return new
 
     def payloads(self, bodies, ids):
@@ -183,7 +204,15 @@ class CorpusClient:
         d = self.corpus.engine.export_eval_keys(seeded=self.corpus.seeded_keys if seeded is None else seeded)
         d["pack_bit_levels"] = np.array([self.bit_levels], dtype=np.int64)
         d["key_id"] = np.array([self.key_id])
-        if self.bridge_from is not None:
+        if isinstance(self.bridge_from, list):
+            # the multi-bridge form (§8.17), for one named generation too
+            d["bridge_from"] = np.array(self.bridge_from)
+            if "bridge_key" in d:
+                d["bridge_keys"] = d.pop("bridge_key")[None]
+            if "bridge_key_body" in d:
+                d["bridge_key_bodies"] = d.pop("bridge_key_body")[None]
+                d["bridge_mask_keys"] = d.pop("bridge_mask_key")[None]
+        elif self.bridge_from is not None:
             d["bridge_from"] = np.array([self.bridge_from])
         return d
 
@@ -231,6 +260,35 @@ class CorpusServer:
         self.key_id = self._key_id_of(eval_keys)
         self.b_old = 0
         self.old_key_id = None
+        # several old generations resident (§8.17): their (fingerprint, end)
+        # pairs, oldest first, and the bridge slot of each; None with fewer
+        # than two, where b_old and old_key_id say it all
+        self._old_gens = None
+        self._gen_slots = None
+
+    @property
+    def old_generations(self) -> list:
+        """The resident old generations, oldest first, as (fingerprint, end)
+        pairs: documents end_{g-1} <= b < end_g are under generation g's key."""
+        if self._old_gens:
+            return list(self._old_gens)
+        return [(self.old_key_id, int(self.b_old))] if self.b_old else []
+
+    @property
+    def generations(self) -> list:
+        """old_generations and, when documents under the current key are
+        resident, (key_id, B) last."""
+        gens = self.old_generations
+        B = 0 if self.body is None else int(self.body.shape[0])
+        if B > (gens[-1][1] if gens else 0):
+            gens.append((self.key_id, B))
+        return gens
+
+    def _reset_generations(self) -> None:
+        if self._old_gens:  # the extra slots' keys serve nothing any more
+            for slot in [s for s in self.engine.bridge_slots() if s > 0]:
+                self.engine.drop_bridge_key(slot)
+        self._old_gens = self._gen_slots = None
 
     def _key_id_of(self, eval_keys: dict) -> str:
         """The generation's fingerprint: the dict's key_id, else that of the
@@ -256,6 +314,7 @@ class CorpusServer:
         if bodies.shape[1] != len(self.cq.model.q_w):
             raise ValueError(f"documents hold {bodies.shape[1]} features, the model {len(self.cq.model.q_w)}")
         self.body, self.ids = self.engine.to_dev(bodies), self.engine.to_dev(ids)
+        self._reset_generations()
         self.b_old, self.old_key_id = 0, None
         return int(ids.size)
 
@@ -285,10 +344,21 @@ class CorpusServer:
         document becomes old-generation. One old generation is resident at a
         time: with old-generation documents already resident, the bridge must
         come from THEIR generation (rotate(bridge_from=...)) and every
-        resident document must be of it."""
+        resident document must be of it.
+
+        A multi-bridge dict (rotate(bridge_from=[clients]), §8.17) lifts that:
+        it must hold a bridge for EVERY resident generation, the one that was
+        current until now included (ValueError naming the missing fingerprint,
+        before anything changes). Each bridge goes into a slot; slots whose
+        generation is not resident are dropped."""
         if "pack_key" not in eval_keys and "pack_key_body" not in eval_keys:
             raise ValueError("the evaluation keys hold no packing key")
         B = 0 if self.body is None else int(self.body.shape[0])
+        if "bridge_keys" in eval_keys or "bridge_key_bodies" in eval_keys:
+            return self._rekey_many(eval_keys, B)
+        if B and self._old_gens:
+            raise ValueError(f"documents of {len(self._old_gens)} old generations are resident and the evaluation "
+                             "keys hold one bridge key: rotate(bridge_from=[...]) makes one per generation")
         if B:
             if ("bridge_key" not in eval_keys and "bridge_key_body" not in eval_keys) or "bridge_from" not in eval_keys:
                 raise ValueError("documents are resident and the evaluation keys hold no bridge key")
@@ -310,6 +380,39 @@ class CorpusServer:
         self.b_old = B
         self.key_id = self._key_id_of(eval_keys)
 
+    def _rekey_many(self, eval_keys: dict, B: int) -> None:
+        """rekey with a multi-bridge dict: bridge_from[g]'s key is row g."""
+        if "bridge_from" not in eval_keys:
+            raise ValueError("the evaluation keys hold bridge keys and no bridge_from")
+        src = [str(f) for f in np.asarray(eval_keys["bridge_from"]).reshape(-1)]
+        resident = [(fp, end) for fp, end in self.generations] if B else []
+        for fp, _ in resident:
+            if fp not in src:
+                raise ValueError(f"documents under key {fp} are resident and the evaluation keys hold no bridge "
+                                 f"key from it (they bridge from {', '.join(src)})")
+        eng = self.engine
+        eng.import_eval_keys(eval_keys)  # row g into slot g, the slots after them dropped
+        self.bit_levels = int(np.asarray(eval_keys.get("pack_bit_levels", [0])).reshape(-1)[0])
+        slots = [src.index(fp) for fp, _ in resident]
+        if len(resident) == 1 and slots[0] != 0:
+            # one old generation runs the single bridge, which reads slot 0
+            g, (b, L) = slots[0], (int(x) for x in np.asarray(eval_keys["bridge_gadget"]).reshape(2))
+            if "bridge_keys" in eval_keys:
+                eng.import_bridge_key(b, L, np.asarray(eval_keys["bridge_keys"])[g], slot=0)
+            else:
+                eng.import_bridge_key_seeded(b, L, np.asarray(eval_keys["bridge_mask_keys"])[g],
+                                             np.asarray(eval_keys["bridge_key_bodies"])[g], slot=0)
+            slots = [0]
+        for s in [s for s in range(len(src)) if s not in slots]:
+            eng.drop_bridge_key(s)
+        if len(resident) >= 2:
+            self._old_gens, self._gen_slots = resident, slots
+            self.b_old, self.old_key_id = B, None
+        else:
+            self._old_gens = self._gen_slots = None
+            self.b_old, self.old_key_id = B, (resident[0][0] if resident else None)
+        self.key_id = self._key_id_of(eval_keys)
+
     def search_many(self, queries, min_similarity=None) -> list:
         """Q clear queries against the resident corpus -> a LIST of version-2
         replies, one per chunk of query_chunks(Q, B), each planned on its own
@@ -325,8 +428,13 @@ class CorpusServer:
         for ch in query_chunks(Q, B):
             Wr, cst, Ts, P = self._plan.plan_many(queries[ch.start:ch.stop], [ts[q] for q in ch])
             eng.set_msg_bits(P)
-            ga, gb = eng.search_seeded_queries(self.body, self.ids, self.mask_key, eng.to_dev(Wr), cst, Ts,
-                                               self.bit_levels, b_old=self.b_old)
+            if self._old_gens:  # several old generations: one grouped bridge over their rows (§8.17)
+                ga, gb = eng.search_seeded_queries_gens(self.body, self.ids, self.mask_key, eng.to_dev(Wr), cst, Ts,
+                                                        self.bit_levels, gen_ends=[e for _, e in self._old_gens],
+                                                        gen_slots=self._gen_slots)
+            else:
+                ga, gb = eng.search_seeded_queries(self.body, self.ids, self.mask_key, eng.to_dev(Wr), cst, Ts,
+                                                   self.bit_levels, b_old=self.b_old)
             out.append(pack_replies(ga.cpu().numpy().view(np.uint64), gb.cpu().numpy().view(np.uint64), B, P, Ts))
         return out
 
@@ -457,8 +565,12 @@ class CorpusHub:
         return self._tenant(name).append(bodies, ids)
 
     def rekey(self, name, eval_keys: dict) -> None:
-        """CorpusServer.rekey of the tenant (its one-old-generation rules);
-        the group re-reads the tenant's keys at the next call."""
+        """CorpusServer.rekey of the tenant (its one-old-generation rules: a
+        multi-bridge dict of §8.17 is refused, the group's bridge reads one
+        key per tenant); the group re-reads the tenant's keys at the next call."""
+        if "bridge_keys" in eval_keys or "bridge_key_bodies" in eval_keys:
+            raise ValueError(f"tenant {name!r}: the hub keeps one old generation per tenant; a multi-bridge "
+                             "dict needs a CorpusServer of its own")
         self._tenant(name).rekey(eval_keys)
 
     def group(self):

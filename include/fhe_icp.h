@@ -709,6 +709,61 @@ int fhe_search_seeded_queries_bridged_batch(fhe_ctx* ctx, const uint64_t* d_body
                                             int64_t cst, const int64_t* h_T, int32_t levels_bit, int64_t B_old,
                                             uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream);
 
+/* ---- key rotation with several old generations resident ----
+ * A rotation schedule leaves documents of several old generations resident.
+ * The key holder makes one DIRECT bridge key from every still-resident old
+ * generation to the current key (no chained bridges: a row carries the noise
+ * of one bridge); the context holds them in FHE_BRIDGE_SLOTS bridge slots.
+ * Slot 0 is the bridge key of the entries above, which keep working on it.
+ * The *_slot entries are their siblings on the named slot: the same
+ * arguments, outputs and check order, with "slot outside [0,
+ * FHE_BRIDGE_SLOTS)" (FHE_E_ARG) first of all. The seeded keygen's "mask key
+ * reuse" refusal covers every slot of the context (rows with equal masks under
+ * one secret differ only by their messages, old key bits here); the unseeded
+ * slot keygen refuses (FHE_E_ARG, "key reuse") a h_key another live slot of the
+ * context was generated with, a courtesy and not the defence: draw every
+ * slot's keys fresh. fhe_drop_bridge_key_slot frees a slot's words and planes
+ * (an empty slot: nothing to do). */
+#define FHE_BRIDGE_SLOTS 8
+int fhe_keygen_bridge_key_slot_key(fhe_ctx* ctx, int32_t slot, const uint64_t* h_s_big_old, int32_t base_log,
+                                   int32_t level, const uint32_t h_key[8], void* stream);
+int fhe_keygen_bridge_key_slot(fhe_ctx* ctx, int32_t slot, const uint64_t* h_s_big_old, int32_t base_log,
+                               int32_t level, uint64_t seed, void* stream);
+int fhe_export_bridge_key_slot(fhe_ctx* ctx, int32_t slot, uint64_t* h_out);
+int fhe_import_bridge_key_slot(fhe_ctx* ctx, int32_t slot, int32_t base_log, int32_t level, const uint64_t* h_in);
+int fhe_drop_bridge_key_slot(fhe_ctx* ctx, int32_t slot);
+/* Generation row map (G, h_ends, h_slots), host tables: documents are resident
+ * oldest generation first and the current generation last; h_ends[G] is
+ * non-decreasing with 0 <= h_ends[g] <= B, documents h_ends[g-1] <= b <
+ * h_ends[g] (h_ends[-1] = 0) belong to old generation g and bridge slot
+ * h_slots[g] bridges them; documents b >= h_ends[G-1] are under the current
+ * key. Empty generations are allowed. fhe_bridge_gens_batch works in place on
+ * a query-major Q x B result (Q >= 1, B >= 1, Q * B < 2^31); every row of a
+ * current-key document is left untouched. One digits launch, one GEMM on the
+ * i8 matrix cores with each 128-row block's own key planes, and one copy back
+ * serve all generations (a -DFHEICP_GRP_BRIDGE=0 build runs one single-key
+ * bridge per generation behind the same entries); bit-exact, equal word for
+ * word to the single bridge applied generation by generation. Timing goes to
+ * the "bridge" bucket.
+ * FHE_E_ARG first, on host-only contexts too: G outside [0,
+ * FHE_BRIDGE_SLOTS], null tables when G > 0, ends that decrease or exceed B, a
+ * slot out of range or named twice. Then the device. Then FHE_E_STATE: a
+ * named slot with rows but no key ("no bridge key in slot s"), named slots
+ * with rows whose gadgets differ ("bridge gadgets differ"). More than 65,535
+ * digit groups of 16 rows or 8,191 blocks of 128 rows over all generations is
+ * FHE_E_ARG ("split the call"), before anything is queued. */
+int fhe_bridge_gens_batch(fhe_ctx* ctx, uint64_t* d_ct, int64_t Q, int64_t B, int32_t G, const int64_t* h_ends,
+                          const int32_t* h_slots, void* stream);
+/* fhe_search_seeded_queries_bridged_batch with the generation row map in
+ * B_old's place. At G = 0 it is fhe_search_seeded_queries_batch word for word
+ * and needs no bridge key; at G = 1, h_slots = {0} it is the bridged entry
+ * word for word. */
+int fhe_search_seeded_queries_gens_batch(fhe_ctx* ctx, const uint64_t* d_body, const uint64_t* d_id0, int64_t B,
+                                         int32_t D, const uint32_t h_mask_key[8], int64_t Q, const int64_t* d_W,
+                                         int64_t cst, const int64_t* h_T, int32_t levels_bit, int32_t G,
+                                         const int64_t* h_ends, const int32_t* h_slots, uint64_t* d_glwe_acc,
+                                         uint64_t* d_glwe_bit, void* stream);
+
 /* ---- both-private search: several GGSW queries in one pass -
  * Q GGSW queries of one key holder (d_ggsw: Q x fhe_ggsw_words, one gadget)
  * against the same B GLWE-encrypted documents. The product is the one of
@@ -1035,6 +1090,14 @@ int fhe_import_pack_key_seeded(fhe_ctx* ctx, int32_t base_log, int32_t level, co
                                const uint64_t* h_body);
 int fhe_import_bridge_key_seeded(fhe_ctx* ctx, int32_t base_log, int32_t level, const uint32_t h_mask_key[8],
                                  const uint64_t* h_body);
+/* The seeded bridge entries on a named bridge slot: "slot
+ * outside [0, FHE_BRIDGE_SLOTS)" first, then their siblings' checks. */
+int fhe_keygen_bridge_key_slot_seeded(fhe_ctx* ctx, int32_t slot, const uint64_t* h_s_big_old, int32_t base_log,
+                                      int32_t level, const uint32_t h_mask_key[8], const uint32_t h_noise_key[8],
+                                      void* stream);
+int fhe_export_bridge_key_slot_seeded(fhe_ctx* ctx, int32_t slot, uint32_t h_mask_key_out[8], uint64_t* h_body);
+int fhe_import_bridge_key_slot_seeded(fhe_ctx* ctx, int32_t slot, int32_t base_log, int32_t level,
+                                      const uint32_t h_mask_key[8], const uint64_t* h_body);
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,15 @@ _PROTOS = {
     "fhe_bridge_batch": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "fhe_search_seeded_queries_bridged_batch": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32,
                                                           _i64, _vp, _vp, _vp]),
+    # several old generations resident: bridge slots and the generation row map
+    "fhe_keygen_bridge_key_slot_key": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "fhe_export_bridge_key_slot": (C.c_int, [_vp, _i32, _vp]),
+    "fhe_import_bridge_key_slot": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
+    "fhe_import_bridge_key_slot_seeded": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "fhe_drop_bridge_key_slot": (C.c_int, [_vp, _i32]),
+    "fhe_bridge_gens_batch": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "fhe_search_seeded_queries_gens_batch": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32,
+                                                       _i32, _vp, _vp, _vp, _vp, _vp]),
     # both sides encrypted: GGSW query x GLWE documents
     "fhe_encrypt_packed_batch_key": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _u64, _vp, _vp]),
     "fhe_encrypt_packed_batch": (C.c_int, [_vp, _vp, _i64, _i32, _u64, _u64, _vp, _vp]),

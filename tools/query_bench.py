@@ -73,6 +73,13 @@ generation's keys and bridge key, at 8 queries x 128 documents and 1 x 1024,
 with every, half and none of the documents old-generation, 24 steps after 4
 warm-up in rotating order, then the "bridge" and "pack" buckets of each leg
 and its parity with the restatement; it writes profiles/r15/rotated.json.
+With --generations G > 1 (docs/AB_LOG_r20.md) the server holds
+a direct bridge key from each of G old generations and the legs are "the G old
+generations in equal parts" (the generation row map, one grouped bridge), "all
+documents of one old generation" (the single bridge over the same rows) and
+"none old"; it reports the "bridge" bucket per leg (three rounds of five
+searches) and writes profiles/r20/rotated_gens.json. FHEICP_LIB selects the
+-DFHEICP_GRP_BRIDGE=0 build (tools/build_variant.sh) for the A/B.
 
 With --stored-tenants (docs/AB_LOG_r16.md) it measures
 several key holders' STORED documents in one batched call, two-party, at 16
@@ -927,6 +934,108 @@ def rotated(cq, oq, D: int, n_bits: int, steps: int, warmup: int, shapes=((8, 12
     return out
 
 
+def rotated_gens(cq, oq, D: int, n_bits: int, G: int, steps: int, warmup: int, shapes=((8, 128), (1, 1024))) -> dict:
+    """The stored-ciphertext search with G old generations resident (DESIGN.md
+    §8.17), one process, one evaluation-only server holding the newest
+    generation's keys and a direct bridge key from each of the G old ones. Per
+    shape three legs, interleaved in rotating order as rotated() does: the G
+    old generations in equal parts of the B documents (the generation row map:
+    fhe_search_seeded_queries_gens_batch), all B documents of ONE old
+    generation (the single bridge of §8.12 over the same row count), none old.
+    Host clock around each search_many with a device synchronise; then a short
+    profiled pass for the "bridge", "pack" and "linear_seeded" HIP-event
+    buckets; and the parity of every leg's decrypted replies with the
+    restatement."""
+    import numpy as np
+    import torch
+    from oracle import quant_ref as Q
+    from fheicp.corpus import EncryptedCorpus
+    from fheicp.stored import CorpusClient, CorpusServer
+    Bmax = max(B for _, B in shapes)
+    c0 = EncryptedCorpus(cq).compile(key_seed=5, device=0, noise_seed=6)
+    clients = [CorpusClient(c0, count=1024, pack_seed=17)]
+    for g in range(1, G):
+        clients.append(clients[-1].rotate(key_seed=5 + 2 * g, pack_seed=17 + g, bridge_seed=100 + g,
+                                          noise_seed=6 + 2 * g))
+    new = clients[-1].rotate(key_seed=5 + 2 * G, pack_seed=17 + G, bridge_seed=200, noise_seed=6 + 2 * G,
+                             bridge_from=clients)
+    server = CorpusServer(new.eval_keys(), cq, c0.P0, c0.mask_key)
+    eng = server.engine
+    _, docs = Q.make_corpus(D, Bmax, seed=21)
+    enc = [c.encrypt_docs(docs) for c in clients]
+    new_b, new_i = new.encrypt_docs(docs)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    out = {"generations": G, "bridge_gadget": list(new.bridge_gadget), "pack_gadget": [new.base_log, new.level],
+           "bridge_key_bytes_each": 8 * eng.bridge_key_words(*new.bridge_gadget), "steps": steps, "warmup": warmup,
+           "shapes": []}
+    for Qn, B in shapes:
+        qs = np.stack([Q.make_corpus(D, 1, seed=100 + i)[0] for i in range(Qn)])
+        ends = [B * (g + 1) // G for g in range(G)]
+        lo = [0] + ends[:-1]
+        legs = {
+            "gens_old": (eng.to_dev(np.concatenate([enc[g][0][lo[g]:ends[g]] for g in range(G)])),
+                         eng.to_dev(np.concatenate([enc[g][1][lo[g]:ends[g]] for g in range(G)])), B,
+                         [(clients[g].key_id, ends[g]) for g in range(G)], list(range(G))),
+            "one_old": (eng.to_dev(enc[0][0][:B]), eng.to_dev(enc[0][1][:B]), B, None, None),
+            "none_old": (eng.to_dev(new_b[:B]), eng.to_dev(new_i[:B]), 0, None, None)}
+
+        def run(name):
+            server.body, server.ids, server.b_old, server._old_gens, server._gen_slots = legs[name]
+            return server.search_many(qs, 0.5)
+
+        orders = ("abc", "cba", "bca", "acb", "cab", "bac")
+        names = {"a": "gens_old", "b": "one_old", "c": "none_old"}
+        t = {k: [] for k in legs}
+        last = {}
+        for i in range(warmup + steps):
+            for k in orders[i % len(orders)]:
+                sec, last[names[k]] = timed(lambda: run(names[k]))
+                if i >= warmup:
+                    t[names[k]].append(sec)
+        ref = np.stack([Q.corpus_accumulate(oq, cq.s_e, n_bits, q, docs[:B]) for q in qs])
+        scores = np.float64(Q.corpus_out_scale(oq, cq.s_e)) * ref.astype(np.float64)
+        exact = {}
+        for name in legs:
+            acc, below = new.decrypt_replies(last[name])
+            exact[name] = bool(np.array_equal(acc.cpu().numpy(), ref) and
+                               np.array_equal(below.cpu().numpy(), (scores < 0.5).astype(np.int64)))
+        # the HIP-event split, in passes of their own (the brackets are not in the timed runs):
+        # three rounds of five searches per leg, so the bucket has a spread of its own
+        eng.profile(True)
+        split, kernels = {name: [] for name in legs}, {}
+        for _ in range(3):
+            for name in legs:
+                for kern in ("bridge", "pack", "linear_seeded"):
+                    eng.profile_read(kern)
+                for _ in range(5):
+                    run(name)
+                torch.cuda.synchronize()
+                split[name].append({kern: eng.profile_read(kern)["total_ms"] / 5
+                                    for kern in ("bridge", "pack", "linear_seeded")})
+                kernels[name] = eng.kernel_name("bridge")
+        eng.profile(False)
+        med = {k: statistics.median(v) * 1e3 for k, v in t.items()}
+        out["shapes"].append({
+            "Q": Qn, "B": B, "ends": ends, "ms_per_search": med, "min_ms": {k: min(v) * 1e3 for k, v in t.items()},
+            "ratio_over_none_old": {k: med[k] / med["none_old"] for k in med},
+            "event_ms_per_search": {k: {kern: statistics.median(r[kern] for r in v) for kern in v[0]}
+                                    for k, v in split.items()},
+            "bridge_event_ms_rounds": {k: [r["bridge"] for r in v] for k, v in split.items()},
+            "bridge_kernel": kernels, "bit_exact": exact})
+    out["bit_exact"] = all(all(s["bit_exact"].values()) for s in out["shapes"])
+    eng.close()
+    for c in clients + [new]:
+        c.corpus.engine.close()
+    return out
+
+
 def private_leveled(eng, beta: int, L: int, D: int, steps: int, warmup: int, Qn: int = 8, sizes=(128, 1024)) -> dict:
     """The both-private leveled step for Qn GGSW queries, per document count:
     one fhe_linear_ggsws_batch (the "linear_ggsws" bucket, and HIP events
@@ -1391,6 +1500,10 @@ def main() -> int:
                          "§8.12): CorpusServer.search_many at 8 queries x 128 documents and 1 x 1024 with every, half "
                          "and none of the documents old-generation (bridged), 24 interleaved steps after 4 warm-up, "
                          "with the bridge bucket's HIP-event time; writes profiles/r15/rotated.json")
+    ap.add_argument("--generations", type=int, default=1, metavar="G",
+                    help="with --rotated: G old generations resident (DESIGN.md §8.17), legs \"G old generations in "
+                         "equal parts\", \"all one old generation\" and \"none old\" with the bridge bucket's "
+                         "HIP-event time; writes profiles/r20/rotated_gens.json. Default 1: --rotated as it was")
     ap.add_argument("--stored-tenants", action="store_true",
                     help="several key holders' stored documents in one batched call (16-dim, n_bits 6, two-party, "
                          "DESIGN.md §8.13): CorpusHub.search_many for 8 tenants x (Q = 1, B = 128) against the eight "
@@ -1428,6 +1541,7 @@ def main() -> int:
                                          "r18/seeded_private.json" if a.seeded_private else
                                          "r17/private_tenants.json" if a.private_tenants else
                                          "r16/stored_tenants.json" if a.stored_tenants else
+                                         "r20/rotated_gens.json" if a.rotated and a.generations > 1 else
                                          "r15/rotated.json" if a.rotated else
                                          "r14/tenants.json" if a.tenants else
                                          "r11/multi_query.json" if a.multi_query else
@@ -1460,6 +1574,20 @@ def main() -> int:
         res = {"bench": "query_bench --seeded-private", "device": torch.cuda.get_device_name(0), "D": 16, "n_bits": 6,
                "P0": cq.worst_msg_bits(), "build": _lib.lib().fhe_build_info().decode(), "seeded_private": sp,
                "bit_exact": bool(sp["bit_exact"] and sp["operands_equal"] and sp["replies_equal_word_for_word"])}
+        line = json.dumps(res)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(line + "\n")
+        print(line)
+        return 0
+    if a.rotated and a.generations > 1:
+        from fheicp import _lib
+        if a.generations > _lib.BRIDGE_SLOTS:
+            ap.error(f"--generations is at most {_lib.BRIDGE_SLOTS}")
+        cq, oq = corpus_quant(16, 6)
+        ro = rotated_gens(cq, oq, 16, 6, a.generations, steps=24, warmup=4)
+        res = {"bench": f"query_bench --rotated --generations {a.generations}", "device": torch.cuda.get_device_name(0),
+               "D": 16, "n_bits": 6, "P0": cq.worst_msg_bits(), "build": _lib.lib().fhe_build_info().decode(),
+               "lib": Path(_lib.LIB_PATH).name, "rotated_gens": ro, "bit_exact": ro["bit_exact"]}
         line = json.dumps(res)
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(line + "\n")
