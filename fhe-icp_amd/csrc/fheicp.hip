@@ -16,6 +16,8 @@
 //                     ciphertexts): key generation, mapped digits, scatter
 //   k_bridge_grp.h    its group form: several old generations' rows in one
 //                     digits launch, one group GEMM and one scatter
+//   k_bridge_hub.h    the same over (tenant, generation) segments of a group's
+//                     padded rows: every tenant's rotation schedule in one pass
 //   k_extprod.h       both-private search: GGSW query encryption, GLWE document
 //                     digits, Toeplitz byte planes, slot extraction
 //   k_extprod_q.h     both-private search, Q queries in one pass: reversed
@@ -48,6 +50,7 @@
 #include "k_pack.h"
 #include "k_bridge.h"
 #include "k_bridge_grp.h"
+#include "k_bridge_hub.h"
 #include "k_extprod.h"
 #include "k_extprod_q.h"
 #include "k_private_seeded.h"
@@ -4227,6 +4230,7 @@ struct fhe_group {
   std::vector<const c64*> h_keys;   // what d_keys holds
   DevBuf ws;                        // tables | small | (search: ct_v | sign | copy | expanded queries / constants)
   DevBuf ks_ws;                     // the group key switch's digit groups | bodies (M words)
+  DevBuf bridge_ws;                 // the group bridge's tables | block table | digits | bodies | compact result (§8.18)
   int ks_tiles = 512;               // the key switch's K-split target: two workgroups per CU of the device
 };
 
@@ -4340,11 +4344,12 @@ int fhe_group_create(fhe_ctx* const* ctxs, int32_t T, fhe_group** out) {
 
 void fhe_group_destroy(fhe_group* g) {
   if (!g) return;
-  if (g->device >= 0 && (g->d_keys || g->ws.p || g->ks_ws.p)) {
+  if (g->device >= 0 && (g->d_keys || g->ws.p || g->ks_ws.p || g->bridge_ws.p)) {
     (void)hipSetDevice(g->device);
     (void)hipFree((void*)g->d_keys);
     (void)hipFree(g->ws.p);
     (void)hipFree(g->ks_ws.p);
+    (void)hipFree(g->bridge_ws.p);
   }
   delete g;
 }
@@ -4765,6 +4770,270 @@ int fhe_search_seeded_queries_group_batch(fhe_group* g, const fhe_group_corpus* 
   return FHE_OK;
 }
 
+// ---- rotation schedules in a group: one bridge for all tenants (§8.18) -----
+static size_t up16(size_t x) { return (x + 15) / 16 * 16; }
+// One tenant's row map as the two entries below hand it over.
+struct GrpRowMap {
+  int64_t Q = 0, B = 0;  // Q = 0: the tenant sits this call out
+  int32_t G = 0;
+  const int64_t* h_ends = nullptr;
+  const int32_t* h_slots = nullptr;
+};
+// One GEMM depth: the segments of the tenants whose bridge gadget is (beta, level).
+struct GrpBridgePass {
+  int beta = 0, level = 0;
+  int64_t nblk = 0, ndg = 0, rows = 0;
+  std::vector<BridgeSeg> segs;
+  std::vector<const void*> planes;
+};
+// After the device and key checks and before anything is queued: every named
+// slot with rows holds a key (FHE_E_STATE naming tenant and slot), a tenant's
+// keys share one gadget (FHE_E_STATE), then the launch limits of every pass
+// (FHE_E_ARG). Fills the passes, one per distinct gadget in order of first
+// appearance; starts: fhe_group_rows' for counts[t] = Q_t B_t.
+static int grp_bridge_plan(const fhe_group* g, const std::vector<GrpRowMap>& maps, const int64_t* starts,
+                           std::vector<GrpBridgePass>* passes) {
+  passes->clear();
+  for (size_t t = 0; t < maps.size(); ++t) {
+    const GrpRowMap& m = maps[t];
+    if (!m.Q) continue;
+    fhe_ctx* ctx = g->ctxs[t];
+    const std::string who = "tenant " + std::to_string(t) + ": ";
+    const GadgetKey* first = nullptr;
+    int first_slot = 0;
+    for (int gi = 0; gi < m.G; ++gi) {
+      const int64_t d0 = gi ? m.h_ends[gi - 1] : 0, n = m.h_ends[gi] - d0;
+      if (n == 0) continue;
+      const int slot = m.h_slots[gi];
+      int rc = need_bridge_slot(ctx, slot);
+      if (rc) return gfail(rc, who + fhe_last_error(ctx));
+      const GadgetKey& k = ctx->bridge_keys[slot];
+      if (!first) first = &k, first_slot = slot;
+      if (k.beta != first->beta || k.level != first->level)
+        return gfail(FHE_E_STATE, who + "bridge gadgets differ: slot " + std::to_string(slot) + " holds (" +
+                                      std::to_string(k.beta) + ", " + std::to_string(k.level) + "), slot " +
+                                      std::to_string(first_slot) + " (" + std::to_string(first->beta) + ", " +
+                                      std::to_string(first->level) + ")");
+      GrpBridgePass* ps = nullptr;
+      for (GrpBridgePass& q : *passes)
+        if (q.beta == k.beta && q.level == k.level) ps = &q;
+      if (!ps) {
+        passes->emplace_back();
+        ps = &passes->back();
+        ps->beta = k.beta;
+        ps->level = k.level;
+      }
+      const int64_t rows = m.Q * n;
+      ps->segs.push_back(BridgeSeg{ps->rows, n, d0, m.B, starts[t]});
+      ps->planes.push_back(k.planes);
+      ps->rows += rows;
+      ps->nblk += (rows + KSM_CTS - 1) / KSM_CTS;
+      ps->ndg += (rows + 15) / 16;
+    }
+  }
+  for (const GrpBridgePass& ps : *passes)
+    if (ps.ndg > 65535 || 8 * ps.nblk > 65535)
+      return gfail(FHE_E_ARG, "bridge batch too large (more than 65535 digit groups of 16 rows, or 8191 blocks of "
+                              "128 rows, over all segments of a pass): split the call");
+  return FHE_OK;
+}
+// The passes of a plan on the group's padded rows d_ct, in place. Per pass:
+// the tables (store_words in stream order, then the block table), the digits,
+// the group GEMM and the copy back; the group's bridge workspace holds
+//   starts | ends | the segment records | the key table | the block table |
+//   digits | bodies | the compact result
+// of the largest pass. Timing goes to the "bridge" bucket of the group's first
+// context, one bracket per pass.
+static int grp_bridge_launch(fhe_group* g, u64* d_ct, const std::vector<GrpBridgePass>& passes, hipStream_t st) {
+  if (passes.empty()) return FHE_OK;
+  fhe_ctx* c0 = g->ctxs[0];
+  const fhe_params& p = c0->p;
+  const int big = p.k * p.N, n1 = big + 1, NB = (n1 + KSM_NB_COLS - 1) / KSM_NB_COLS;
+  auto layout = [&](const GrpBridgePass& ps, size_t off[5]) {
+    const size_t S = ps.segs.size();
+    off[0] = up16(8 * S * (3 + BRIDGE_SEG_WORDS));                      // the block table
+    off[1] = off[0] + up16(sizeof(KsGrpBlock) * (size_t)ps.nblk);       // digits
+    off[2] = off[1] + (size_t)ps.ndg * 16 * (size_t)(big * ps.level);   // bodies
+    off[3] = off[2] + up16(8 * (size_t)ps.rows);                        // the compact result
+    off[4] = off[3] + 8 * (size_t)ps.rows * n1;
+  };
+  size_t need = 0, off[5];
+  for (const GrpBridgePass& ps : passes) {
+    layout(ps, off);
+    need = std::max(need, off[4]);
+  }
+  int rc = reserve(nullptr, g->bridge_ws, need, FHE_E_NOMEM,
+                   "group: bridge workspace: out of device memory (fewer rows per call)");
+  if (rc) return rc;
+  char* w = (char*)g->bridge_ws.p;
+  for (const GrpBridgePass& ps : passes) {
+    const size_t S = ps.segs.size();
+    layout(ps, off);
+    std::vector<u64> words(S * (3 + BRIDGE_SEG_WORDS));
+    for (size_t s = 0; s < S; ++s) {
+      const BridgeSeg& sg = ps.segs[s];
+      words[s] = (u64)sg.start;
+      words[S + s] = (u64)(s + 1 < S ? ps.segs[s + 1].start : ps.rows);  // segments follow each other unpadded
+      memcpy(&words[2 * S + s * BRIDGE_SEG_WORDS], &sg, sizeof(BridgeSeg));
+      words[(2 + BRIDGE_SEG_WORDS) * S + s] = (u64)(uintptr_t)ps.planes[s];
+    }
+    int64_t* se = (int64_t*)w;
+    BridgeSeg* seg = (BridgeSeg*)(se + 2 * S);
+    const void** keys = (const void**)(se + (2 + BRIDGE_SEG_WORDS) * S);
+    KsGrpBlock* blk = (KsGrpBlock*)(w + off[0]);
+    uint32_t* Dg = (uint32_t*)(w + off[1]);
+    u64* body = (u64*)(w + off[2]);
+    u64* M = (u64*)(w + off[3]);
+    const int KB = big * ps.level / 64;
+    // the single bridge's split rule on the launch's blocks x column blocks
+    const auto [Sk, kslice] = ksm_split(KB, ps.nblk * NB, 512);
+    hipEvent_t e1;
+    prof_begin(c0, c0->prof_bridge, st, &e1);
+    if ((rc = store_words(c0, (u64*)w, words.data(), (int64_t)words.size(), st))) return rc;
+    hipLaunchKernelGGL(k_ks_grp_tables, dim3((unsigned)((ps.nblk + 255) / 256)), dim3(256), 0, st, (const int64_t*)se,
+                       (int)S, ps.nblk, blk);
+    // the digits kernel also zeroes the compact rows the split's atomics add into
+    hipLaunchKernelGGL(k_bridge_digits_hub, dim3((unsigned)(big / 64), (unsigned)(8 * ps.nblk)), dim3(256), 0, st,
+                       (const u64*)d_ct, (const KsGrpBlock*)blk, (const BridgeSeg*)seg, big, ps.beta, ps.level, KB, Dg,
+                       body, Sk > 1 ? n1 : 0, M);
+    c0->prof_bridge.kernel = "k_keyswitch_mfma_grp<8, 1>";
+    hipLaunchKernelGGL((k_keyswitch_mfma_grp<8, 1>), dim3((unsigned)(ps.nblk * NB * Sk)), dim3(256), 0, st,
+                       (const v4i*)Dg, (const v4i* const*)keys, (const KsGrpBlock*)blk, (const u64*)body, n1, NB, KB, 0,
+                       Sk, kslice, M);
+    hipLaunchKernelGGL(k_bridge_scatter_hub, dim3((unsigned)(8 * ps.nblk), (unsigned)((n1 + 255) / 256)), dim3(256),
+                       0, st, (const u64*)M, (const KsGrpBlock*)blk, (const BridgeSeg*)seg, n1, d_ct);
+    prof_end(c0, c0->prof_bridge, st, e1, ps.rows);
+    HIPCHK(c0, hipGetLastError());
+  }
+  return FHE_OK;
+}
+// the row-map rules of one participating tenant (FHE_E_ARG, "tenant t: ...")
+static int grp_rowmap_args(const fhe_group* g, int32_t t, const GrpRowMap& m) {
+  fhe_ctx* ctx = g->ctxs[t];
+  if (gens_args(ctx, m.B, m.G, m.h_ends, m.h_slots))
+    return gfail(FHE_E_ARG, "tenant " + std::to_string(t) + ": " + fhe_last_error(ctx));
+  return FHE_OK;
+}
+
+int fhe_bridge_group_gens_batch(fhe_group* g, uint64_t* d_ct, const fhe_group_rowmap* maps, int32_t T, void* stream) {
+  if (!g) return gfail(FHE_E_ARG, "null group");
+  if (!maps || T != (int32_t)g->ctxs.size()) return gfail(FHE_E_ARG, "one fhe_group_rowmap per tenant");
+  // argument errors first, before any device or key is looked at
+  std::vector<int64_t> counts((size_t)T), starts((size_t)T);
+  std::vector<GrpRowMap> rm((size_t)T);
+  int64_t total = 0;
+  int rc;
+  for (int32_t t = 0; t < T; ++t) {
+    const fhe_group_rowmap& m = maps[t];
+    const std::string who = "tenant " + std::to_string(t) + ": ";
+    if (m.struct_size != (int32_t)sizeof(fhe_group_rowmap))
+      return gfail(FHE_E_ARG, who + "fhe_group_rowmap.struct_size is not this library's");
+    if (m.Q < 0) return gfail(FHE_E_ARG, who + "Q < 0");
+    counts[t] = 0;
+    if (m.Q == 0) continue;  // sits this call out
+    if (m.B < 1 || m.Q > 0x7fffffffLL || m.B > 0x7fffffffLL || m.Q * m.B > 0x7fffffffLL)
+      return gfail(FHE_E_ARG, who + "bad bridge generations arguments (Q < 1, B < 1 or Q*B >= 2^31)");
+    rm[t].Q = m.Q, rm[t].B = m.B, rm[t].G = m.G, rm[t].h_ends = m.h_ends, rm[t].h_slots = m.h_slots;
+    if ((rc = grp_rowmap_args(g, t, rm[t]))) return rc;
+    if (!d_ct) return gfail(FHE_E_ARG, who + "null bridge buffers");
+    counts[t] = m.Q * m.B;
+    total += counts[t];
+    if (total >= ((int64_t)1 << 31)) return gfail(FHE_E_ARG, "2^31 results and more: split the call");
+  }
+  if ((rc = grp_enter(g))) return rc;
+  fhe_group_rows(counts.data(), T, starts.data());
+  std::vector<GrpBridgePass> passes;
+  if ((rc = grp_bridge_plan(g, rm, starts.data(), &passes))) return rc;
+  return grp_bridge_launch(g, d_ct, passes, (hipStream_t)stream);
+}
+
+// fhe_search_seeded_queries_group_batch with every tenant's generation row map
+// in B_old's place: the leveled steps, ONE grouped bridge over all tenants'
+// old generations, the copies, one sign extraction, the packings.
+int fhe_search_seeded_queries_group_gens_batch(fhe_group* g, const fhe_group_corpus_gens* items, int32_t T,
+                                               void* stream) {
+  if (!g) return gfail(FHE_E_ARG, "null group");
+  if (!items || T != (int32_t)g->ctxs.size()) return gfail(FHE_E_ARG, "one fhe_group_corpus_gens per tenant");
+  // argument errors first, before any device or key is looked at
+  std::vector<int64_t> counts((size_t)T), starts((size_t)T);
+  std::vector<GrpRowMap> rm((size_t)T);
+  int64_t total = 0, qmax = 0;
+  int rc;
+  for (int32_t t = 0; t < T; ++t) {
+    const fhe_group_corpus_gens& c = items[t];
+    const std::string who = "tenant " + std::to_string(t) + ": ";
+    if (c.struct_size != (int32_t)sizeof(fhe_group_corpus_gens))
+      return gfail(FHE_E_ARG, who + "fhe_group_corpus_gens.struct_size is not this library's");
+    if (c.Q < 0) return gfail(FHE_E_ARG, who + "Q < 0");
+    counts[t] = 0;
+    if (c.Q == 0) continue;  // sits this call out
+    if (seeded_queries_args(g->ctxs[t], c.Q, c.B, c.D))
+      return gfail(FHE_E_ARG, who + fhe_last_error(g->ctxs[t]));
+    if (c.levels_bit < 0 || c.levels_bit > 8) return gfail(FHE_E_ARG, who + "levels_bit outside [0, 8]");
+    rm[t].Q = c.Q, rm[t].B = c.B, rm[t].G = c.G, rm[t].h_ends = c.h_ends, rm[t].h_slots = c.h_slots;
+    if ((rc = grp_rowmap_args(g, t, rm[t]))) return rc;
+    if (!c.d_body || !c.d_id0 || !c.h_mask_key || !c.d_W || !c.h_T || !c.d_glwe_acc || !c.d_glwe_bit)
+      return gfail(FHE_E_ARG, who + "null search arguments");
+    counts[t] = c.Q * c.B;
+    total += counts[t];
+    qmax = std::max(qmax, c.Q);
+    if (total >= ((int64_t)1 << 31)) return gfail(FHE_E_ARG, "2^31 results and more: split the call");
+  }
+  if ((rc = grp_enter(g))) return rc;
+  for (int32_t t = 0; t < T; ++t) {
+    if (!items[t].Q) continue;
+    if ((rc = need_pack_key(g->ctxs[t])))
+      return gfail(rc, "tenant " + std::to_string(t) + ": " + fhe_last_error(g->ctxs[t]));
+  }
+  const int64_t M = fhe_group_rows(counts.data(), T, starts.data());
+  std::vector<GrpBridgePass> passes;
+  if ((rc = grp_bridge_plan(g, rm, starts.data(), &passes))) return rc;
+  for (int32_t t = 0; t < T; ++t)
+    if (items[t].Q && items[t].levels_bit > g->ctxs[t]->pack_key.level)
+      return gfail(FHE_E_ARG, "tenant " + std::to_string(t) + ": levels_bit exceeds the packing key's levels");
+  if (M == 0) return FHE_OK;
+  if ((rc = grp_ks_fits(g, counts.data()))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const fhe_params& p = g->ctxs[0]->p;
+  const size_t Wb = fhe_big_lwe_words(&p), Ws = fhe_small_lwe_words(&p), tb = grp_table_bytes((size_t)T, M);
+  if ((rc = grp_ensure_ws(g, tb + 8 * ((size_t)M * (3 * Wb + Ws) + (size_t)qmax)))) return rc;
+  u64* small = (u64*)((char*)g->ws.p + tb);
+  u64* ctv = small + (size_t)M * Ws;
+  u64* sgn = ctv + (size_t)M * Wb;
+  u64* cpy = sgn + (size_t)M * Wb;
+  u64* dcs = cpy + (size_t)M * Wb;  // one tenant's scaled constants at a time, in stream order
+  // per tenant the leveled step into its segment; the grouped bridge on every
+  // tenant's old documents' rows; then the copies of the leveled rows (the
+  // sign extraction consumes them)
+  for (int32_t t = 0; t < T; ++t) {
+    const fhe_group_corpus_gens& c = items[t];
+    if (!c.Q) continue;
+    fhe_ctx* ctx = g->ctxs[t];
+    if ((rc = store_scaled_csts(ctx, dcs, c.Q, nullptr, c.cst, c.h_T, st))) return rc;
+    if ((rc = linear_seeded_queries_launch(ctx, c.d_body, c.d_id0, c.B, c.D, c.h_mask_key, c.Q, c.d_W, dcs,
+                                           ctv + (size_t)starts[t] * Wb, st)))
+      return rc;
+  }
+  if ((rc = grp_bridge_launch(g, ctv, passes, st))) return rc;
+  for (int32_t t = 0; t < T; ++t) {
+    if (!items[t].Q) continue;
+    HIPCHK(g->ctxs[t], hipMemcpyAsync(cpy + (size_t)starts[t] * Wb, ctv + (size_t)starts[t] * Wb,
+                                      8 * (size_t)counts[t] * Wb, hipMemcpyDeviceToDevice, st));
+  }
+  if ((rc = grp_sign(g, ctv, counts.data(), starts.data(), M, sgn, small, g->ws.p, st))) return rc;
+  // tenant t's two packings with its own key, as fhe_search_seeded_queries_gens_batch
+  for (int32_t t = 0; t < T; ++t) {
+    const fhe_group_corpus_gens& c = items[t];
+    if (!c.Q) continue;
+    fhe_ctx* ctx = g->ctxs[t];
+    if ((rc = pack_impl(ctx, cpy + (size_t)starts[t] * Wb, counts[t], ctx->pack_key.level, c.d_glwe_acc, st))) return rc;
+    if ((rc = pack_impl(ctx, sgn + (size_t)starts[t] * Wb, counts[t], c.levels_bit ? c.levels_bit : ctx->pack_key.level,
+                        c.d_glwe_bit, st)))
+      return rc;
+  }
+  return FHE_OK;
+}
+
 // ---- both-private search for a group ---------------------
 // What one call's leveled step launches, from the participating tenants'
 // shapes: the records, the launch's RT, tile, row-tile and row counts, the K
@@ -4778,7 +5047,6 @@ struct XqGrpPlan {
   std::vector<int64_t> counts, starts;
   size_t off_tiles = 0, off_rt = 0, off_quad = 0, off_cst = 0, off_planes = 0, off_M = 0, bytes = 0;
 };
-static size_t up16(size_t x) { return (x + 15) / 16 * 16; }
 // The argument checks of both entries (FHE_E_ARG, "tenant t: ...", host-only
 // contexts report them too) and the plan. `search`: the thresholds, levels_bit
 // and the two outputs are arguments too.

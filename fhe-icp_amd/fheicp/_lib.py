@@ -53,6 +53,23 @@ class FheGroupCorpus(C.Structure):
                 ("B_old", C.c_int64), ("d_glwe_acc", C.c_void_p), ("d_glwe_bit", C.c_void_p)]
 
 
+class FheGroupRowmap(C.Structure):
+    # one tenant's part of fhe_bridge_group_gens_batch: struct_size first, then
+    # its Q x B result and the generation row map of fhe_bridge_gens_batch
+    _fields_ = [("struct_size", C.c_int32), ("G", C.c_int32), ("Q", C.c_int64), ("B", C.c_int64),
+                ("h_ends", C.c_void_p), ("h_slots", C.c_void_p)]
+
+
+class FheGroupCorpusGens(C.Structure):
+    # one tenant's part of fhe_search_seeded_queries_group_gens_batch:
+    # FheGroupCorpus with the generation row map in B_old's place
+    _fields_ = [("struct_size", C.c_int32), ("D", C.c_int32), ("d_body", C.c_void_p), ("d_id0", C.c_void_p),
+                ("B", C.c_int64), ("h_mask_key", C.c_void_p), ("Q", C.c_int64), ("d_W", C.c_void_p),
+                ("cst", C.c_int64), ("h_T", C.c_void_p), ("levels_bit", C.c_int32), ("G", C.c_int32),
+                ("h_ends", C.c_void_p), ("h_slots", C.c_void_p), ("d_glwe_acc", C.c_void_p),
+                ("d_glwe_bit", C.c_void_p)]
+
+
 class FheGroupGgsw(C.Structure):
     # one tenant's part of fhe_linear_ggsws_group_batch / fhe_search_ggsws_group_batch:
     # struct_size first, then the arguments of fhe_search_ggsws_batch
@@ -211,6 +228,9 @@ SIGNATURES = [
     ("fhe_group_form", C.c_int, [_P]),
     ("fhe_keyswitch_group_batch", C.c_int, [_vp, _vp, C.POINTER(_i64), _i32, _u64, _vp, _vp]),
     ("fhe_search_seeded_queries_group_batch", C.c_int, [_vp, _vp, _i32, _vp]),
+    # rotation schedules in a group: one bridge for all tenants
+    ("fhe_bridge_group_gens_batch", C.c_int, [_vp, _vp, _vp, _i32, _vp]),
+    ("fhe_search_seeded_queries_group_gens_batch", C.c_int, [_vp, _vp, _i32, _vp]),
     # a group's both-private search
     ("fhe_linear_ggsws_group_batch", C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
     ("fhe_search_ggsws_group_batch", C.c_int, [_vp, _vp, _i32, _vp]),

@@ -1425,6 +1425,70 @@ class EngineGroup:
         _lib.check(self._L.fhe_search_seeded_queries_group_batch(self._grp, arr, len(items), _stream(self.device)))
         return out
 
+    # ------------- rotation schedules: one bridge for all tenants (§8.18) --
+    def bridge_gens(self, ct: torch.Tensor, maps) -> torch.Tensor:
+        """fhe_bridge_group_gens_batch: in place on the padded rows of
+        rows([Q_t * B_t]). maps: one per engine, None (the tenant sits this
+        call out) or (Q, B, gen_ends, gen_slots) as Engine.bridge_gens."""
+        if len(maps) != len(self.engines):
+            raise ValueError(f"{len(maps)} row maps for {len(self.engines)} tenants")
+        arr = (_lib.FheGroupRowmap * max(len(maps), 1))()
+        keep, counts = [], []
+        for t, m in enumerate(maps):
+            arr[t].struct_size = C.sizeof(_lib.FheGroupRowmap)
+            if m is None:
+                counts.append(0)
+                continue
+            Q, B, ends, slots = m
+            G, he, hs = Engine._gens(ends, slots)
+            keep.append((he, hs))
+            arr[t].Q, arr[t].B, arr[t].G = int(Q), int(B), G
+            arr[t].h_ends, arr[t].h_slots = C.addressof(he), C.addressof(hs)
+            counts.append(int(Q) * int(B))
+        M, _ = group_rows(counts)
+        if ct.numel() < M * self.W:
+            raise ValueError(f"ct holds {ct.numel() // self.W} rows, the layout {M}")
+        _lib.check(self._L.fhe_bridge_group_gens_batch(self._grp, _ptr(ct), arr, len(maps), _stream(self.device)))
+        return ct
+
+    def search_seeded_queries_gens(self, items) -> list:
+        """fhe_search_seeded_queries_group_gens_batch. items: one per engine,
+        None (the tenant sits this call out) or search_seeded_queries' tuple
+        with (gen_ends, gen_slots) in b_old's place: (body, id0, mask_key, W,
+        cst, Ts, levels_bit, gen_ends, gen_slots). Returns, per tenant,
+        (glwe_acc, glwe_bit) or None."""
+        if len(items) != len(self.engines):
+            raise ValueError(f"{len(items)} items for {len(self.engines)} tenants")
+        arr = (_lib.FheGroupCorpusGens * max(len(items), 1))()
+        keep, out = [], []
+        for t, (eng, it) in enumerate(zip(self.engines, items)):
+            arr[t].struct_size = C.sizeof(_lib.FheGroupCorpusGens)
+            if it is None:
+                out.append(None)
+                continue
+            body, id0, mask_key, W, cst, Ts, levels_bit, ends, slots = it
+            hT, _ = Engine._i64s(Ts)
+            key = Engine._key(mask_key)
+            G, he, hs = Engine._gens(ends, slots)
+            Q = hT.size
+            B, D = body.shape
+            if tuple(W.shape) != (Q, D):
+                raise ValueError(f"tenant {t}: weights {tuple(W.shape)} for {Q} thresholds of {D} features")
+            shape = (eng.glwe_count(Q * int(B)), (eng.params.k + 1) * eng.params.N)
+            ga = torch.empty(shape, dtype=torch.int64, device=self.device)
+            gb = torch.empty(shape, dtype=torch.int64, device=self.device)
+            keep.append((hT, key, body, id0, W, he, hs))
+            c = arr[t]
+            c.D, c.Q, c.B, c.cst, c.levels_bit, c.G = int(D), Q, int(B), int(cst), int(levels_bit), G
+            c.d_body, c.d_id0, c.d_W = body.data_ptr(), id0.data_ptr(), W.data_ptr()
+            c.h_mask_key, c.h_T = C.addressof(key), hT.ctypes.data
+            c.h_ends, c.h_slots = C.addressof(he), C.addressof(hs)
+            c.d_glwe_acc, c.d_glwe_bit = ga.data_ptr(), gb.data_ptr()
+            out.append((ga, gb))
+        _lib.check(self._L.fhe_search_seeded_queries_group_gens_batch(self._grp, arr, len(items),
+                                                                      _stream(self.device)))
+        return out
+
     # ------------------------- both-private search for a group (§8.14) --
     def _ggsw_items(self, items):
         """The fhe_group_ggsw array of items (one per engine, None: the tenant

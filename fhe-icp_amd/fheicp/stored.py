@@ -508,8 +508,14 @@ class CorpusHub:
     behind one GPU. The host learns which tenant asked, the queries and the
     thresholds; each tenant's documents, scores and bits stay under its key."""
 
-    def __init__(self, device: int = 0):
+    def __init__(self, device: int = 0, rotation_schedules: bool = False):
+        """rotation_schedules: tenants may keep several old generations
+        resident (§8.18): rekey takes a multi-bridge dict and every group
+        round bridges all tenants' old generations in one grouped pass
+        (fhe_search_seeded_queries_group_gens_batch). The default keeps one
+        old generation per tenant and the per-tenant bridge of §8.13."""
         self.device = device
+        self.rotation_schedules = bool(rotation_schedules)
         self.tenants = {}  # name -> CorpusServer
         self._group = None
 
@@ -567,11 +573,30 @@ class CorpusHub:
     def rekey(self, name, eval_keys: dict) -> None:
         """CorpusServer.rekey of the tenant (its one-old-generation rules: a
         multi-bridge dict of §8.17 is refused, the group's bridge reads one
-        key per tenant); the group re-reads the tenant's keys at the next call."""
+        key per tenant); the group re-reads the tenant's keys at the next call.
+        With rotation_schedules any dict goes to the tenant's server, whose
+        rules and messages apply with the tenant's name in front."""
+        if self.rotation_schedules:
+            server = self._tenant(name)
+            try:
+                return server.rekey(eval_keys)
+            except ValueError as e:
+                raise ValueError(f"tenant {name!r}: {e}") from e
         if "bridge_keys" in eval_keys or "bridge_key_bodies" in eval_keys:
             raise ValueError(f"tenant {name!r}: the hub keeps one old generation per tenant; a multi-bridge "
                              "dict needs a CorpusServer of its own")
         self._tenant(name).rekey(eval_keys)
+
+    @staticmethod
+    def gen_map(server) -> tuple:
+        """(gen_ends, gen_slots) of a tenant's resident old generations: its
+        several generations' ends and slots, else its one old generation in
+        slot 0, else empty."""
+        if getattr(server, "_old_gens", None):
+            return [int(e) for _, e in server._old_gens], [int(s) for s in server._gen_slots]
+        if int(getattr(server, "b_old", 0)):
+            return [int(server.b_old)], [0]
+        return [], []
 
     def group(self):
         if self._group is None:
@@ -614,9 +639,13 @@ class CorpusHub:
             items = [None] * len(names)
             for p in rnd["parts"]:
                 s = self.tenants[p["name"]]
+                last = self.gen_map(s) if self.rotation_schedules else (s.b_old,)
                 items[names.index(p["name"])] = (s.body, s.ids, s.mask_key, s.engine.to_dev(p["W"]), p["cst"], p["Ts"],
-                                                 s.bit_levels, s.b_old)
-            res = self.group().search_seeded_queries(items)
+                                                 s.bit_levels) + last
+            if self.rotation_schedules:  # every tenant's old generations in one grouped bridge (§8.18)
+                res = self.group().search_seeded_queries_gens(items)
+            else:
+                res = self.group().search_seeded_queries(items)
             for p in rnd["parts"]:
                 ga, gb = res[names.index(p["name"])]
                 B = int(self.tenants[p["name"]].body.shape[0])

@@ -915,6 +915,68 @@ typedef struct fhe_group_corpus {
  * then FHE_E_STATE (no packing key, or no bridge key where B_old > 0). */
 int fhe_search_seeded_queries_group_batch(fhe_group* group, const fhe_group_corpus* items, int32_t T, void* stream);
 
+/* ---- rotation schedules in a group: one bridge for all tenants -
+ * One tenant's part of a group bridge: its query-major Q x B result and its
+ * generation row map (G, h_ends, h_slots) as fhe_bridge_gens_batch takes it. */
+typedef struct fhe_group_rowmap {
+  int32_t struct_size;        /* = sizeof(fhe_group_rowmap); else FHE_E_ARG */
+  int32_t G;                  /* G old generations, 0..FHE_BRIDGE_SLOTS */
+  int64_t Q;                  /* Q = 0: the tenant sits this call out */
+  int64_t B;
+  const int64_t* h_ends;      /* G, as fhe_bridge_gens_batch */
+  const int32_t* h_slots;     /* G */
+} fhe_group_rowmap;
+/* fhe_bridge_gens_batch for the T tenants of a group, in place on the padded
+ * layout of counts[t] = Q_t * B_t (fhe_group_rows): tenant t's segment is, word
+ * for word, what fhe_bridge_gens_batch on t's own context gives; padding rows,
+ * current-key rows and the rows of tenants that sit out are neither read nor
+ * written. Every non-empty old generation of every participating tenant is one
+ * segment of ONE pass: the tables, one digits launch, one GEMM on the i8 matrix
+ * cores whose 128-row blocks each take their segment's key planes, one copy
+ * back. Tenants whose bridge gadgets differ run one pass per distinct
+ * (base_log, level), in order of first appearance. Timing goes to the "bridge"
+ * bucket of the group's first context, one bracket per pass.
+ * FHE_E_ARG first ("tenant t: ...", before the device is looked at):
+ * struct_size, Q < 0, Q * B >= 2^31, fhe_bridge_gens_batch's row-map rules, a
+ * null d_ct, 2^31 results and more. Then the device and the evaluation keys.
+ * Then FHE_E_STATE: "tenant t: no bridge key in slot s" for a named slot with
+ * rows, "tenant t: bridge gadgets differ" within one tenant. More than 65,535
+ * digit groups of 16 rows or 8,191 blocks of 128 rows over all segments of a
+ * pass is FHE_E_ARG ("split the call"), before anything is queued. */
+int fhe_bridge_group_gens_batch(fhe_group* group, uint64_t* d_ct, const fhe_group_rowmap* maps, int32_t T,
+                                void* stream);
+/* One tenant's part of fhe_search_seeded_queries_group_gens_batch:
+ * fhe_group_corpus with the generation row map in B_old's place. Q = 0: the
+ * tenant sits this call out. */
+typedef struct fhe_group_corpus_gens {
+  int32_t struct_size;        /* = sizeof(fhe_group_corpus_gens); else FHE_E_ARG */
+  int32_t D;
+  const uint64_t* d_body;     /* B x D body words of the stored documents */
+  const uint64_t* d_id0;      /* B stream ids (device) */
+  int64_t B;
+  const uint32_t* h_mask_key; /* 8 words */
+  int64_t Q;
+  const int64_t* d_W;         /* Q x D weight rows */
+  int64_t cst;
+  const int64_t* h_T;         /* Q thresholds (host) */
+  int32_t levels_bit;
+  int32_t G;                  /* old generations, 0..FHE_BRIDGE_SLOTS */
+  const int64_t* h_ends;      /* G: documents h_ends[g-1] <= b < h_ends[g] are under old generation g */
+  const int32_t* h_slots;     /* G: the bridge slot of each */
+  uint64_t* d_glwe_acc;       /* ceil(Q B / N) x (k+1)N words */
+  uint64_t* d_glwe_bit;
+} fhe_group_corpus_gens;
+/* fhe_search_seeded_queries_group_batch with every tenant's rotation schedule:
+ * the leveled steps, the group bridge above over all tenants' old generations,
+ * one fhe_sign_group_batch, the packings. Tenant t's outputs are word for word
+ * those of fhe_search_seeded_queries_gens_batch on its own context; with every
+ * tenant at G <= 1 and slot 0 they are those of
+ * fhe_search_seeded_queries_group_batch. Checks: that entry's, with the row-map
+ * rules in B_old's place, then the group bridge's FHE_E_STATE checks after the
+ * packing key's, then its launch limit. */
+int fhe_search_seeded_queries_group_gens_batch(fhe_group* group, const fhe_group_corpus_gens* items, int32_t T,
+                                               void* stream);
+
 /* ---- both-private search for a group ---------------------
  * One tenant's part of the two entries below: the arguments of
  * fhe_search_ggsws_batch. Q = 0: the tenant sits this call out. */

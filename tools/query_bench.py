@@ -89,6 +89,13 @@ after another and one tenant's 1 x 1024 search, 24 steps after 4 warm-up in
 rotating order, with the HIP-event split of each (rotations, key switches,
 bridge, packings, leveled step), then a second pass with every tenant rotated
 (all documents old-generation); it writes profiles/r16/stored_tenants.json.
+With --generations G (docs/AB_LOG_r21.md) every tenant's
+documents lie in G old generations in equal parts and none current, 8 queries
+per tenant; CorpusHub(rotation_schedules=True) (one grouped bridge pass over
+all tenants' generations) is timed and, at G = 1, alternates with the default
+hub (one single-key bridge per tenant) in one process; it reports the search
+time and the "bridge" bucket per hub search and writes
+profiles/r21/stored_tenants_gens.json.
 
 With --private-tenants (docs/AB_LOG_r17.md) it measures
 several key holders' BOTH-PRIVATE searches in one batched call, two-party, at
@@ -719,6 +726,114 @@ def stored_tenants(cq, oq, D: int, n_bits: int, steps: int, warmup: int, Tn: int
         for c in corpora:
             c.engine.close()
     out["meets_bar"] = all(p["meets_bar"] for p in out["passes"].values())
+    return out
+
+
+def stored_tenants_gens(cq, oq, D: int, n_bits: int, G: int, steps: int, warmup: int, Tn: int = 8, B: int = 128,
+                        Qn: int = 8, plain_first: bool = False) -> dict:
+    """Rotation schedules in the stored-ciphertext hub, one
+    process: Tn tenants x (Qn queries, B documents), every tenant's documents
+    in G old generations in equal parts and none current (as --rotated
+    --generations splits them). Leg "sched": CorpusHub(rotation_schedules=True),
+    one grouped bridge pass over all tenants' generations. At G = 1 also leg
+    "plain": the default hub, one single-key bridge per tenant; the two hubs
+    alternate, their order swapping every step. Host clock around each
+    search_many with a device synchronise; per run the "bridge" bucket summed
+    over the hub's contexts; each leg's decrypted replies against the
+    restatement, and at G = 1 the two hubs' replies word for word."""
+    import numpy as np
+    import torch
+    from oracle import quant_ref as Q
+    from fheicp.corpus import EncryptedCorpus
+    from fheicp.stored import CorpusClient, CorpusHub
+    from fheicp import _lib
+    names = [f"tenant{t}" for t in range(Tn)]
+    _, docs = Q.make_corpus(D, Tn * B, seed=21)
+    qs = [np.stack([Q.make_corpus(D, 1, seed=100 + Qn * t + i)[0] for i in range(Qn)]) for t in range(Tn)]
+    ends = [B * (g + 1) // G for g in range(G)]
+    lo = [0] + ends[:-1]
+    hubs = {"sched": CorpusHub(0, rotation_schedules=True)}
+    if G == 1:
+        hubs["plain"] = CorpusHub(0)
+    if plain_first:  # the default hub's servers are built, and run, before the other's
+        hubs = dict(reversed(list(hubs.items())))
+    news, engines = [], []
+    for t, name in enumerate(names):
+        c0 = EncryptedCorpus(cq).compile(key_seed=5 + 16 * t, device=0, noise_seed=6 + 16 * t)
+        clients = [CorpusClient(c0, count=1024, pack_seed=17 + 16 * t)]
+        for g in range(1, G):
+            clients.append(clients[-1].rotate(key_seed=5 + 16 * t + 2 * g, pack_seed=17 + 16 * t + g,
+                                              bridge_seed=1000 + 16 * t + g, noise_seed=6 + 16 * t + 2 * g))
+        new = clients[-1].rotate(key_seed=5 + 16 * t + 2 * G, pack_seed=17 + 16 * t + G, bridge_seed=2000 + 16 * t,
+                                 noise_seed=6 + 16 * t + 2 * G, bridge_from=clients)
+        mine = docs[t * B:(t + 1) * B]
+        enc = [c.encrypt_docs(mine[lo[g]:ends[g]]) for g, c in enumerate(clients)]
+        keys = new.eval_keys()                                          # bridge g in slot g
+        for hub in hubs.values():
+            s = hub.add_tenant(name, keys, cq, c0.P0, c0.mask_key)
+            s.load(np.concatenate([e[0] for e in enc]), np.concatenate([e[1] for e in enc]))
+            s.b_old, s.old_key_id = B, clients[0].key_id
+            if G > 1:
+                s._old_gens, s._gen_slots = [(c.key_id, ends[g]) for g, c in enumerate(clients)], list(range(G))
+            engines.append(s.engine)
+        news.append(new)
+        for c in clients:
+            c.corpus.engine.close()
+    requests = {n: (qs[t], 0.5) for t, n in enumerate(names)}
+    for e in engines:
+        e.profile(True)
+
+    def timed(hub):
+        for s in hub.tenants.values():
+            s.engine.profile_read("bridge")
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = hub.search_many(requests)
+        torch.cuda.synchronize()
+        sec = time.perf_counter() - t0
+        br = [s.engine.profile_read("bridge") for s in hub.tenants.values()]
+        return sec, res, sum(r["total_ms"] for r in br), sum(r["launches"] for r in br)
+
+    legs = list(hubs)
+    t_, br_, last, brackets = {k: [] for k in legs}, {k: [] for k in legs}, {}, {}
+    for i in range(warmup + steps):
+        for k in (legs if i % 2 == 0 else legs[::-1]):
+            sec, last[k], ms, brackets[k] = timed(hubs[k])
+            if i >= warmup:
+                t_[k].append(sec)
+                br_[k].append(ms)
+    for e in engines:
+        e.profile(False)
+    exact = {}
+    for k in legs:
+        ok = True
+        for t, name in enumerate(names):
+            acc, below = news[t].decrypt_replies(last[k][name])
+            ref = np.stack([Q.corpus_accumulate(oq, cq.s_e, n_bits, q, docs[t * B:(t + 1) * B]) for q in qs[t]])
+            scores = np.float64(Q.corpus_out_scale(oq, cq.s_e)) * ref.astype(np.float64)
+            ok = ok and bool(np.array_equal(acc.cpu().numpy(), ref) and
+                             np.array_equal(below.cpu().numpy(), (scores < 0.5).astype(np.int64)))
+        exact[k] = ok
+    out = {"tenants": Tn, "Q": Qn, "B": B, "generations": G, "steps": steps, "warmup": warmup,
+           "build": _lib.lib().fhe_build_info().decode(), "bridge_gadget": list(news[0].bridge_gadget),
+           "hub_order": list(hubs), "rounds": [r["mode"] for r in hubs["sched"].rounds(requests)],
+           "rows_bridged": Tn * Qn * B, "blocks": Tn * sum(-(-Qn * (e - l) // 128) for l, e in zip(lo, ends)),
+           "bridge_kernel_sched": next(iter(hubs["sched"].tenants.values())).engine.kernel_name("bridge"),
+           "legs": {k: {"search_ms": statistics.median(t_[k]) * 1e3, "search_min_ms": min(t_[k]) * 1e3,
+                        "bridge_ms_per_search": statistics.median(br_[k]), "bridge_min_ms": min(br_[k]),
+                        "bridge_brackets_per_search": brackets[k], "bit_exact": exact[k]} for k in legs}}
+    if G == 1:
+        out["replies_equal_word_for_word"] = all(
+            len(last["sched"][n]) == len(last["plain"][n]) and
+            all(np.array_equal(a, b) for a, b in zip(last["sched"][n], last["plain"][n])) for n in names)
+        out["ratio_sched_over_plain_search"] = out["legs"]["sched"]["search_ms"] / out["legs"]["plain"]["search_ms"]
+        out["ratio_sched_over_plain_bridge"] = (out["legs"]["sched"]["bridge_ms_per_search"] /
+                                                out["legs"]["plain"]["bridge_ms_per_search"])
+    out["bit_exact"] = all(exact.values()) and out.get("replies_equal_word_for_word", True)
+    for hub in hubs.values():
+        hub.close()
+    for n in news:
+        n.corpus.engine.close()
     return out
 
 
@@ -1501,9 +1616,14 @@ def main() -> int:
                          "and none of the documents old-generation (bridged), 24 interleaved steps after 4 warm-up, "
                          "with the bridge bucket's HIP-event time; writes profiles/r15/rotated.json")
     ap.add_argument("--generations", type=int, default=1, metavar="G",
-                    help="with --rotated: G old generations resident (DESIGN.md §8.17), legs \"G old generations in "
+                    help="with --stored-tenants: every tenant's documents in G old generations, the hub with "
+                         "rotation_schedules (DESIGN.md §8.18; writes profiles/r21/stored_tenants_gens.json). "
+                         "With --rotated: G old generations resident (DESIGN.md §8.17), legs \"G old generations in "
                          "equal parts\", \"all one old generation\" and \"none old\" with the bridge bucket's "
                          "HIP-event time; writes profiles/r20/rotated_gens.json. Default 1: --rotated as it was")
+    ap.add_argument("--plain-first", action="store_true",
+                    help="with --stored-tenants --generations 1: build and run the default hub before the "
+                         "rotation_schedules hub (the order's own effect on the comparison)")
     ap.add_argument("--stored-tenants", action="store_true",
                     help="several key holders' stored documents in one batched call (16-dim, n_bits 6, two-party, "
                          "DESIGN.md §8.13): CorpusHub.search_many for 8 tenants x (Q = 1, B = 128) against the eight "
@@ -1536,11 +1656,13 @@ def main() -> int:
                                                 "--seeded-private: profiles/r18/seeded_private.json, "
                                                 "--seeded-keys: profiles/r19/seeded_keys.json)")
     a = ap.parse_args()
+    a.generations_given = any(x == "--generations" or x.startswith("--generations=") for x in sys.argv[1:])
     if a.out is None:
         a.out = str(REPO / "profiles" / ("r19/seeded_keys.json" if a.seeded_keys else
                                          "r18/seeded_private.json" if a.seeded_private else
                                          "r17/private_tenants.json" if a.private_tenants else
-                                         "r16/stored_tenants.json" if a.stored_tenants else
+                                         "r21/stored_tenants_gens.json" if a.stored_tenants and a.generations_given
+                                         else "r16/stored_tenants.json" if a.stored_tenants else
                                          "r20/rotated_gens.json" if a.rotated and a.generations > 1 else
                                          "r15/rotated.json" if a.rotated else
                                          "r14/tenants.json" if a.tenants else
@@ -1610,6 +1732,21 @@ def main() -> int:
         tn = private_tenants(cq, oq, 16, 6, steps=24, warmup=4, Tn=a.tenant_shape[0], B=a.tenant_shape[1])
         res = {"bench": "query_bench --private-tenants", "device": torch.cuda.get_device_name(0), "D": 16, "n_bits": 6,
                "P0": cq.worst_msg_bits(), "private_tenants": tn, "meets_bar": tn["meets_bar"]}
+        line = json.dumps(res)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(line + "\n")
+        print(line)
+        return 0
+    if a.stored_tenants and a.generations_given:
+        from fheicp import _lib
+        if not 1 <= a.generations <= _lib.BRIDGE_SLOTS:
+            ap.error(f"--generations is 1 to {_lib.BRIDGE_SLOTS}")
+        cq, oq = corpus_quant(16, 6)
+        tg = stored_tenants_gens(cq, oq, 16, 6, a.generations, steps=24, warmup=4, Tn=a.tenant_shape[0],
+                                 B=a.tenant_shape[1], plain_first=a.plain_first)
+        res = {"bench": f"query_bench --stored-tenants --generations {a.generations}",
+               "device": torch.cuda.get_device_name(0), "D": 16, "n_bits": 6, "P0": cq.worst_msg_bits(),
+               "stored_tenants_gens": tg, "bit_exact": tg["bit_exact"]}
         line = json.dumps(res)
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(line + "\n")
