@@ -57,6 +57,11 @@
 #include "k_seeded_keys.h"
 #include "k_blind_rotate.h"
 #include "k_extprod_grp.h"
+#ifndef FHEICP_GRP_XGENS
+#define FHEICP_GRP_XGENS 1  // 0: one fhe_linear_ggsws_batch per generation and a scatter behind the same entries
+                            // (A/B builds, tools/build_variant.sh NAME -DFHEICP_GRP_XGENS=0)
+#endif
+#include "k_extprod_gens.h"
 
 // ============================================================ host =========
 struct ProfAcc {
@@ -5229,3 +5234,205 @@ int fhe_search_ggsws_group_batch(fhe_group* g, const fhe_group_ggsw* items, int3
 }
 
 }  // extern "C"
+
+// ---- both-private key rotation: per-generation GGSW queries
+// What one call's leveled step launches, from the generations' shapes: the
+// segments (generations with documents), the launch's RT, tile and row-tile
+// counts, the K split, and the layout of xp_ws:
+//   planes | results | constants   (fhe_ggsws_gens_ws_bytes)
+//   | the records | the tile table | the row-tile table | the ends table.
+struct XqGensPlan {
+  int ns = 0, RT = 1, KB = 0, Sk = 1, kslice = 0;
+  int64_t B = 0, rtp = 0, ntiles = 0, nrt = 0, mwords = 0;
+  XqGensSegs seg;
+  int32_t gen[XQ_GENS_MAX];  // segment -> generation of the call
+  int64_t off[XQ_GENS_MAX];  // generation -> its first document of the call
+  int32_t n_old = 0;         // the bridge's row map: the generations before a slot -1 entry
+  int64_t ends[XQ_GENS_MAX];
+  int32_t slots[XQ_GENS_MAX];
+  size_t off_M = 0, off_cst = 0, off_ten = 0, off_tiles = 0, off_rt = 0, off_ends = 0, bytes = 0;
+};
+// The argument checks of both entries (FHE_E_ARG, host-only contexts report
+// them too) and the plan.
+static int xq_gens_plan(fhe_ctx* ctx, const fhe_ggsw_gen* gens, int32_t G, int32_t base_log, int32_t L, int64_t Q,
+                        int32_t D, XqGensPlan* pl) {
+  if (!ctx) return fail(nullptr, FHE_E_ARG, "null ctx");
+  if (G < 1 || G > XQ_GENS_MAX)
+    return fail(ctx, FHE_E_ARG, "bad ggsw generations arguments (G outside [1, " + std::to_string(XQ_GENS_MAX) + "])");
+  if (!gens) return fail(ctx, FHE_E_ARG, "null ggsw generations");
+  uint32_t seen = 0;
+  int64_t B = 0;
+  for (int g = 0; g < G; ++g) {
+    const fhe_ggsw_gen& it = gens[g];
+    const std::string who = "generation " + std::to_string(g) + ": ";
+    if (it.struct_size != (int32_t)sizeof(fhe_ggsw_gen))
+      return fail(ctx, FHE_E_ARG, who + "fhe_ggsw_gen.struct_size is not this library's");
+    if (it.slot == -1) {
+      if (g != G - 1)
+        return fail(ctx, FHE_E_ARG, who + "slot -1 (the current key) must be the last generation");
+    } else {
+      int rc = slot_arg(ctx, it.slot);
+      if (rc) return rc;
+      if (seen >> it.slot & 1)
+        return fail(ctx, FHE_E_ARG, who + "bridge slot " + std::to_string(it.slot) + " named twice");
+      seen |= 1u << it.slot;
+    }
+    if (it.B < 0 || it.B > 0x7fffffffLL) return fail(ctx, FHE_E_ARG, who + "B outside [0, 2^31)");
+    if (it.B > 0 && (!it.d_ggsw || !it.d_docs)) return fail(ctx, FHE_E_ARG, who + "null ggsw queries or documents");
+    pl->off[g] = B;
+    B += it.B;
+    if (it.slot != -1) {
+      pl->ends[pl->n_old] = B;
+      pl->slots[pl->n_old++] = it.slot;
+    }
+  }
+  if (B < 1) return fail(ctx, FHE_E_ARG, "bad ggsw generations arguments (no generation holds a document)");
+  int rc = ggsws_args(ctx, Q, B, D, base_log, L);
+  if (rc) return rc;
+  const fhe_params& p = ctx->p;
+  const int n1 = (p.k + 1) * p.N;
+  pl->B = B;
+  pl->KB = n1 * L / 64;
+  pl->rtp = ggsws_row_tiles(p, Q, &pl->RT);
+  for (int g = 0; g < G; ++g) {
+    const fhe_ggsw_gen& it = gens[g];
+    if (it.B == 0) continue;
+    const int64_t Gg = ggsw_glwes(p, it.B, D);
+    pl->seg.v[pl->ns] = {it.d_ggsw, (const uint8_t*)it.d_docs, pl->off[g], pl->mwords, (int32_t)Q, (int32_t)Gg,
+                         (int32_t)it.B, D, (int32_t)pl->nrt, 0};
+    pl->gen[pl->ns++] = g;
+    pl->ntiles += xq_grp_cgrid(p.N, (int)Gg) * (pl->rtp / pl->RT);
+    pl->nrt += pl->rtp;
+    pl->mwords += Q * Gg * n1;
+  }
+  // the tiles are the GEMM's grid x, (row tile, k-block) the planes'
+  if (pl->ntiles > 0x7fffffffLL || pl->nrt * pl->KB > 0x7fffffffLL)
+    return fail(ctx, FHE_E_ARG, "ggsw queries batch too large (2^31 tiles over all generations): split the call");
+  if (!FHEICP_GRP_XGENS)
+    for (int i = 0; i < pl->ns; ++i)
+      if (pl->seg.v[i].G > 65535 || pl->rtp / pl->RT > 65535)
+        return fail(ctx, FHE_E_ARG, "ggsw queries batch too large: split the call");
+  // linear_ggsws_impl's K split on the launch's total of tiles
+  pl->Sk = (int)std::max<int64_t>(1, std::min<int64_t>(pl->KB / 4, FHEICP_XQ_WGS / std::max<int64_t>(1, pl->ntiles)));
+  pl->kslice = (pl->KB + pl->Sk - 1) / pl->Sk;
+  pl->Sk = (pl->KB + pl->kslice - 1) / pl->kslice;
+  pl->off_M = (size_t)pl->nrt * 16 * n1 * L * 8;
+  pl->off_cst = pl->off_M + 8 * (size_t)pl->mwords;
+  pl->off_ten = up16(pl->off_cst + 8 * (size_t)Q);
+  pl->off_tiles = pl->off_ten + up16(sizeof(XqGrpTenant) * (size_t)pl->ns);
+  pl->off_rt = pl->off_tiles + sizeof(XqGrpTile) * (size_t)pl->ntiles;
+  pl->off_ends = pl->off_rt + up16(4 * (size_t)pl->nrt);
+  pl->bytes = pl->off_ends + 8 * (size_t)pl->ns;
+  return FHE_OK;
+}
+size_t fhe_ggsws_gens_ws_bytes(const fhe_params* p, int64_t Q, const int64_t* h_B, int32_t G, int32_t D,
+                               int32_t level) {
+  if (!p || !h_B || G < 1 || G > XQ_GENS_MAX || Q < 1 || D <= 0 || D > p->N || level < 1 || level > 8) return 0;
+  size_t sum = 0;
+  for (int g = 0; g < G; ++g) {
+    if (h_B[g] < 0) return 0;
+    // a generation's planes and result: the sibling's formula less the constants, which all generations share
+    if (h_B[g] > 0) sum += fhe_ggsws_ws_bytes(p, Q, h_B[g], D, level) - 8 * (size_t)Q;
+  }
+  return sum ? sum + 8 * (size_t)Q : 0;
+}
+// The leveled step of every generation into d_out (Q B x (kN+1), query-major,
+// generation g's documents from off_g on), h_cst[q] (or cst - h_T[q]) on query
+// q's bodies: the constants, then in one bracket the tables, the memset of a
+// split K, the planes, the GEMM and the extraction. The launch count does not
+// depend on G.
+static int linear_ggsws_gens_impl(fhe_ctx* ctx, const fhe_ggsw_gen* gens, const XqGensPlan& pl, int32_t L, int64_t Q,
+                                  int32_t D, const int64_t* h_cst, int64_t cst, const int64_t* h_T, uint64_t* d_out,
+                                  hipStream_t st) {
+  const fhe_params& p = ctx->p;
+  const int n1 = p.k * p.N + 1;
+  int rc;
+#if !FHEICP_GRP_XGENS
+  {
+    // the loop form: every generation through the single-key step into a compact buffer behind
+    // the largest generation's own workspace, then scattered to its rows
+    size_t need = 0, rows = 0;
+    for (int i = 0; i < pl.ns; ++i) {
+      need = std::max(need, up16(fhe_ggsws_ws_bytes(&p, Q, pl.seg.v[i].B, D, L)));
+      rows = std::max(rows, (size_t)Q * (size_t)pl.seg.v[i].B);
+    }
+    rc = reserve(ctx, ctx->xp_ws, need + 8 * rows * n1, FHE_E_DEVICE, "hipMalloc of the ggsw product workspace failed");
+    if (rc) return rc;
+    u64* compact = (u64*)((char*)ctx->xp_ws.p + need);
+    for (int i = 0; i < pl.ns; ++i) {
+      const XqGrpTenant& e = pl.seg.v[i];
+      if ((rc = linear_ggsws_impl(ctx, e.ggsw, L, e.F, Q, e.B, D, h_cst, cst, h_T, compact, st))) return rc;
+      hipLaunchKernelGGL(k_xq_gens_scatter, dim3((unsigned)(Q * e.B), (unsigned)((n1 + 255) / 256)), dim3(256), 0, st,
+                         (const u64*)compact, (int64_t)e.B, e.start, pl.B, n1, d_out);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return FHE_OK;
+  }
+#endif
+  rc = reserve(ctx, ctx->xp_ws, pl.bytes, FHE_E_DEVICE, "hipMalloc of the ggsw product workspace failed");
+  if (rc) return rc;
+  char* ws = (char*)ctx->xp_ws.p;
+  v4i* P8 = (v4i*)ws;
+  u64* Mall = (u64*)(ws + pl.off_M);
+  u64* d_cst = (u64*)(ws + pl.off_cst);
+  XqGrpTenant* ten = (XqGrpTenant*)(ws + pl.off_ten);
+  XqGrpTile* tiles = (XqGrpTile*)(ws + pl.off_tiles);
+  int32_t* rtt = (int32_t*)(ws + pl.off_rt);
+  int64_t* ends = (int64_t*)(ws + pl.off_ends);
+  if ((rc = store_scaled_csts(ctx, d_cst, Q, h_cst, cst, h_T, st))) return rc;
+  hipEvent_t e1;
+  prof_begin(ctx, ctx->prof_xq, st, &e1);
+  ctx->prof_xq.kernel = pl.RT == 2 ? "k_extprod_queries_mfma_grp<2>" : "k_extprod_queries_mfma_grp<1>";
+  const int64_t nth = std::max(std::max(pl.ntiles, pl.nrt), (int64_t)pl.ns);
+  hipLaunchKernelGGL(k_xq_gens_tables, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, st, pl.seg, pl.ns, p.N,
+                     pl.RT, pl.rtp, pl.ntiles, ten, tiles, rtt, ends);
+  if (pl.Sk > 1) HIPCHK(ctx, hipMemsetAsync(Mall, 0, 8 * (size_t)pl.mwords, st));
+  hipLaunchKernelGGL(k_ggsws_planes_grp, dim3((unsigned)(pl.nrt * pl.KB)), dim3(64), 0, st, (const XqGrpTenant*)ten,
+                     (const int32_t*)rtt, p.N, p.k, (int)L, pl.KB, P8);
+  const dim3 grid((unsigned)pl.ntiles, 1, (unsigned)pl.Sk);
+  if (pl.RT == 2)
+    hipLaunchKernelGGL(k_extprod_queries_mfma_grp<2>, grid, dim3(256), 0, st, (const XqGrpTile*)tiles,
+                       (const XqGrpTenant*)ten, (const v4i*)P8, p.N, p.k, (int)L, pl.KB, pl.kslice, Mall);
+  else
+    hipLaunchKernelGGL(k_extprod_queries_mfma_grp<1>, grid, dim3(256), 0, st, (const XqGrpTile*)tiles,
+                       (const XqGrpTenant*)ten, (const v4i*)P8, p.N, p.k, (int)L, pl.KB, pl.kslice, Mall);
+  hipLaunchKernelGGL(k_extprod_extract_gens, dim3((unsigned)(Q * pl.B), (unsigned)((p.k * p.N + 256) / 256)),
+                     dim3(256), 0, st, (const u64*)Mall, (const XqGrpTenant*)ten, (const int64_t*)ends, pl.ns, pl.B,
+                     p.N, p.k, (const u64*)d_cst, d_out);
+  prof_end(ctx, ctx->prof_xq, st, e1, Q * pl.B);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+
+int fhe_linear_ggsws_gens_batch(fhe_ctx* ctx, const fhe_ggsw_gen* gens, int32_t G, int32_t base_log, int32_t level,
+                                int64_t Q, int32_t D, const int64_t* h_cst, uint64_t* d_out, void* stream) {
+  XqGensPlan pl;
+  int rc = xq_gens_plan(ctx, gens, G, base_log, level, Q, D, &pl);  // argument errors first
+  if (rc) return rc;
+  if (!h_cst || !d_out) return fail(ctx, FHE_E_ARG, "null linear ggsw generations arguments");
+  if ((rc = need_device(ctx))) return rc;
+  return linear_ggsws_gens_impl(ctx, gens, pl, level, Q, D, h_cst, 0, nullptr, d_out, (hipStream_t)stream);
+}
+
+int fhe_search_ggsws_gens_batch(fhe_ctx* ctx, const fhe_ggsw_gen* gens, int32_t G, int32_t base_log, int32_t level,
+                                int64_t Q, int32_t D, int64_t cst, const int64_t* h_T, int32_t levels_bit,
+                                uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream) {
+  XqGensPlan pl;
+  int rc = xq_gens_plan(ctx, gens, G, base_log, level, Q, D, &pl);  // argument errors first
+  if (rc) return rc;
+  if (levels_bit < 0 || levels_bit > 8)
+    return fail(ctx, FHE_E_ARG, "bad search ggsw generations arguments (levels_bit outside [0, 8])");
+  if (!h_T || !d_glwe_acc || !d_glwe_bit) return fail(ctx, FHE_E_ARG, "null search ggsw generations arguments");
+  if ((rc = need_eval_keys(ctx))) return rc;
+  if ((rc = need_pack_key(ctx))) return rc;
+  if ((rc = gens_ready(ctx, Q, pl.n_old, pl.ends, pl.slots))) return rc;
+  if (levels_bit > ctx->pack_key.level)
+    return fail(ctx, FHE_E_ARG, "search ggsw generations levels_bit exceeds the packing key's levels");
+  hipStream_t st = (hipStream_t)stream;
+  QueryWs w;
+  if ((rc = leveled_ws(ctx, Q * pl.B, 0, true, &w, nullptr))) return rc;
+  if ((rc = linear_ggsws_gens_impl(ctx, gens, pl, level, Q, D, nullptr, cst, h_T, w.ctv, st))) return rc;
+  // the old generations' rows to the current key, in place; the packings' copy is taken after it
+  if ((rc = bridge_gens_impl(ctx, w.ctv, Q, pl.B, pl.n_old, pl.ends, pl.slots, st))) return rc;
+  return post_leveled_search(ctx, w, Q * pl.B, levels_bit, d_glwe_acc, d_glwe_bit, stream);
+}

@@ -79,6 +79,13 @@ class FheGroupGgsw(C.Structure):
                 ("d_glwe_bit", C.c_void_p)]
 
 
+class FheGgswGen(C.Structure):
+    # one key generation's part of fhe_linear_ggsws_gens_batch / fhe_search_ggsws_gens_batch
+    # (DESIGN.md §8.19): struct_size first; slot -1 is the context's current key
+    _fields_ = [("struct_size", C.c_int32), ("slot", C.c_int32), ("d_ggsw", C.c_void_p), ("d_docs", C.c_void_p),
+                ("B", C.c_int64)]
+
+
 # (name, restype, argtypes) for every symbol declared in include/fhe_icp.h
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -234,6 +241,11 @@ SIGNATURES = [
     # a group's both-private search
     ("fhe_linear_ggsws_group_batch", C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
     ("fhe_search_ggsws_group_batch", C.c_int, [_vp, _vp, _i32, _vp]),
+    # both-private key rotation: per-generation GGSW queries, one bridge
+    ("fhe_ggsws_gens_ws_bytes", C.c_size_t, [_P, _i64, _vp, _i32, _i32, _i32]),
+    ("fhe_linear_ggsws_gens_batch", C.c_int, [_CTXP, _vp, _i32, _i32, _i32, _i64, _i32, _vp, _vp, _vp]),
+    ("fhe_search_ggsws_gens_batch", C.c_int, [_CTXP, _vp, _i32, _i32, _i32, _i64, _i32, _i64, _vp, _i32, _vp, _vp,
+                                              _vp]),
     # both-private search on seeded documents and queries
     ("fhe_ggsw_body_words", C.c_size_t, [_P, _i32, _i32]),
     ("fhe_encrypt_packed_seeded_batch", C.c_int, [_CTXP, _vp, _i64, _i32, _vp, _vp, _u64, _vp, _vp]),

@@ -1099,6 +1099,63 @@ class Engine:
                                                  _stream(self.device)))
         return ga, gb
 
+    # ---- both-private key rotation: per-generation GGSW queries (§8.19) --
+    def ggsws_gens_ws_bytes(self, Q: int, Bs, D: int, level: int) -> int:
+        """Product workspace of a generations call (fhe_ggsws_gens_ws_bytes; host only)."""
+        keep, hB = self._i64s(Bs)
+        return self._L.fhe_ggsws_gens_ws_bytes(C.byref(self._P), int(Q), hB, keep.size, int(D), int(level))
+
+    def _ggsw_gens(self, gens, base_log: int, level: int):
+        """gens: (slot, ggsws, docs, B) per generation, oldest first; ggsws and
+        docs may be None where B == 0. -> (the fhe_ggsw_gen array, Q, B)."""
+        arr = (_lib.FheGgswGen * max(1, len(gens)))()
+        Q = None
+        for i, (slot, ggsws, docs, B) in enumerate(gens):
+            if int(B) > 0:
+                q = self._ggsws(ggsws, base_log, level)
+                if Q is not None and q != Q:
+                    raise ValueError(f"generation {i} holds {q} queries, an earlier one {Q}")
+                Q = q
+            a = arr[i]
+            a.struct_size, a.slot, a.B = C.sizeof(_lib.FheGgswGen), int(slot), int(B)
+            if int(B) > 0:
+                assert ggsws.is_contiguous() and docs.is_contiguous(), "buffers must be contiguous"
+                a.d_ggsw, a.d_docs = ggsws.data_ptr(), docs.data_ptr()
+        if Q is None:
+            raise ValueError("no generation holds a document")
+        return arr, Q, sum(int(g[3]) for g in gens)
+
+    def linear_ggsws_gens(self, gens, base_log: int, level: int, D: int, csts,
+                          out: torch.Tensor | None = None) -> torch.Tensor:
+        """fhe_linear_ggsws_gens_batch: gens (slot, ggsws, docs, B) per key
+        generation, oldest first; Q * B x (kN+1), query-major, generation g's
+        documents from off_g on, each row under its own generation's key."""
+        arr, Q, B = self._ggsw_gens(gens, base_log, level)
+        keep, hc = self._i64s(csts)
+        if keep.size != Q:
+            raise ValueError(f"{keep.size} constants for {Q} queries")
+        if out is None:
+            out = self.empty_big(Q * B)
+        self._chk(self._L.fhe_linear_ggsws_gens_batch(self._ctx, C.byref(arr), len(gens), int(base_log), int(level), Q,
+                                                      int(D), hc, _ptr(out), _stream(self.device)))
+        return out
+
+    def search_ggsws_gens(self, gens, base_log: int, level: int, D: int, cst: int, Ts, levels_bit: int = 0):
+        """fhe_search_ggsws_gens_batch: the evaluation-only form over several
+        key generations, the old ones' rows bridged to the current key;
+        (glwe_acc, glwe_bit), each ceil(Q B / N) x (k+1)N words, B = sum B_g."""
+        arr, Q, B = self._ggsw_gens(gens, base_log, level)
+        keep, hT = self._i64s(Ts)
+        if keep.size != Q:
+            raise ValueError(f"{keep.size} thresholds for {Q} queries")
+        shape = (self.glwe_count(Q * B), (self.params.k + 1) * self.params.N)
+        ga = torch.empty(shape, dtype=torch.int64, device=self.device)
+        gb = torch.empty(shape, dtype=torch.int64, device=self.device)
+        self._chk(self._L.fhe_search_ggsws_gens_batch(self._ctx, C.byref(arr), len(gens), int(base_log), int(level), Q,
+                                                      int(D), int(cst), hT, int(levels_bit), _ptr(ga), _ptr(gb),
+                                                      _stream(self.device)))
+        return ga, gb
+
     # ------- both-private search on seeded documents and queries (§8.15) --
     def ggsw_body_words(self, base_log: int, level: int) -> int:
         return self._L.fhe_ggsw_body_words(C.byref(self._P), int(base_log), int(level))

@@ -535,6 +535,28 @@ def extprod_plan(p: SchemeParams, w_norm2: float):
     return None
 
 
+def private_rotation_plan(p: SchemeParams, w_norm2: float):
+    """The plan of a both-private store that rotates its keys (DESIGN.md
+    §8.19): (ggsw_gadget, bridge_gadget, in_var_for_pack). An old generation's
+    row carries the external product's variance and, ADDED to it, one bridge's:
+    extprod_plan's gadget, bridge_plan on the product's variance, and when
+    2^(63 - msg_bits) / sqrt(extprod_var + bridge_var) falls below 9.2 the next
+    gadget of extprod_plan's order (fewest levels, then the largest base_log)
+    until one passes. in_var_for_pack = (extprod_var + bridge_var) / 2^128 is
+    what the packing key is planned with. ValueError when no gadget passes."""
+    first = extprod_plan(p, w_norm2)
+    gadgets = [(b, L) for L in range(1, 9) for b in range(7, 0, -1) if pack_gadget_ok(b, L)]
+    for b, L in (gadgets[gadgets.index(first):] if first is not None else ()):
+        ev = extprod_var(p, w_norm2, b, L)
+        bg = bridge_plan(p, ev / 2.0 ** 128)
+        total = ev + bridge_var(p, *bg)
+        if 2.0 ** (63 - p.msg_bits) / math.sqrt(total) >= SIGMA_BAR:
+            return (b, L), bg, total / 2.0 ** 128
+    raise ValueError(f"both-private search has no GGSW gadget at P0 = {p.msg_bits}: the int8 digits stop at "
+                     "base_log * level = 49 bits, whose rounding exceeds the 9.2-sigma margin of this width "
+                     "(DESIGN.md §8.7); use fewer embedding bits or dimensions")
+
+
 def _variances(p: SchemeParams, group: int = 1):
     """(bootstrap, key switch, modulus switch) output variances, relative to
     the 2^64 torus, for the main gadget of p on the classic

@@ -22,6 +22,16 @@ Several queries of one key holder go in one pass:
 ``search_many`` answers with fheicp.query's version-2 replies
 (fhe_search_ggsws_batch: the product transposed, no Toeplitz operand).
 
+Key rotation without re-encryption: ``PrivateClient.rotate``
+makes the next generation's client with one direct bridge key per resident
+old generation; ``encrypt_queries_gens`` encrypts each query once per resident
+generation, under that generation's own key; the host keeps every
+generation's documents resident (``PrivateServer.load`` / ``append`` /
+``rekey``) and ``search_resident`` multiplies generation g's documents by
+generation g's GGSWs, then moves the old generations' accumulator rows to the
+current key with the grouped bridge (fhe_search_ggsws_gens_batch). The bridge's
+noise is added to the product's, never multiplied by the query's norm.
+
 The expected values are the bilinear restatement of fheicp.corpus
 (oracle/quant_ref.py, ``corpus_*``); reply format and packing plan are
 fheicp.query's.
@@ -65,7 +75,8 @@ def pack_ggsw_query(ggsw, D: int, P0: int, base_log: int, level: int, N: int, k:
     return np.concatenate([head, g])
 
 
-def unpack_ggsw_query(arr) -> dict:
+def unpack_ggsw_query(arr, copy: bool = True) -> dict:
+    """copy=False: "ggsw" is a view of the payload (a reader that uploads it at once)."""
     a = np.asarray(arr)
     if a.dtype != np.uint64 or a.ndim != 1 or a.size < HEADER_WORDS or int(a[0]) != QUERY_MAGIC:
         raise ValueError("not an fheicp GGSW query payload")
@@ -76,7 +87,7 @@ def unpack_ggsw_query(arr) -> dict:
     if a.size != HEADER_WORDS + (k + 1) * level * (k + 1) * N:
         raise ValueError("GGSW query payload size does not match its gadget and parameters")
     return {"D": int(a[2]), "P0": int(a[3]), "base_log": base_log, "level": level, "N": N, "k": k,
-            "ggsw": a[HEADER_WORDS:].copy()}
+            "ggsw": a[HEADER_WORDS:].copy() if copy else a[HEADER_WORDS:]}
 
 
 # ------------------------------------------------------ batches of queries --
@@ -162,7 +173,7 @@ def _seeded_head(arr, magic: int, what: str) -> np.ndarray:
     return a
 
 
-def unpack_ggsw_query_seeded(arr) -> dict:
+def unpack_ggsw_query_seeded(arr, copy: bool = True) -> dict:
     a = _seeded_head(arr, SEEDED_QUERY_MAGIC, "GGSW query payload")
     base_log, level = int(a[4]) & 0xFFFFFFFF, int(a[4]) >> 32
     N, k = int(a[5]) & 0xFFFFFFFF, int(a[5]) >> 32
@@ -172,7 +183,8 @@ def unpack_ggsw_query_seeded(arr) -> dict:
     if a.size != SEEDED_HEADER_WORDS + (k + 1) * level * N:
         raise ValueError("seeded GGSW query payload size does not match its gadget and parameters")
     return {"seeded": True, "D": D, "P0": int(a[3]), "base_log": base_log, "level": level, "N": N, "k": k,
-            "id0": int(a[6]), "mask_key": a[7:11].copy().view(np.uint32), "body": a[SEEDED_HEADER_WORDS:].copy()}
+            "id0": int(a[6]), "mask_key": a[7:11].copy().view(np.uint32),
+            "body": a[SEEDED_HEADER_WORDS:].copy() if copy else a[SEEDED_HEADER_WORDS:]}
 
 
 def pack_doc_block_seeded(body, id0: int, mask_key, B: int, D: int, P0: int, N: int, k: int) -> np.ndarray:
@@ -198,11 +210,11 @@ def _is_seeded(arr, magic: int) -> bool:
     return a.dtype == np.uint64 and a.ndim == 1 and a.size > 0 and int(a[0]) == magic
 
 
-def unpack_any_query(arr) -> dict:
+def unpack_any_query(arr, copy: bool = True) -> dict:
     """A query payload of either form, dispatched on the magic; "seeded" says which."""
     if _is_seeded(arr, SEEDED_QUERY_MAGIC):
-        return unpack_ggsw_query_seeded(arr)
-    return dict(unpack_ggsw_query(arr), seeded=False)
+        return unpack_ggsw_query_seeded(arr, copy)
+    return dict(unpack_ggsw_query(arr, copy), seeded=False)
 
 
 def unpack_any_docs(arr) -> dict:
@@ -271,8 +283,11 @@ class PrivateClient(QueryClient):
     of a compiled EncryptedCorpus."""
 
     def __init__(self, corpus: EncryptedCorpus, count: int = 1024, pack_seed=None, enc_seed: int | None = None,
-                 seeded: bool = False, mask_seed: int | None = None):
+                 seeded: bool = False, mask_seed: int | None = None, in_var: float | None = None):
         """enc_seed: the 64-bit test form of the session's encryption key.
+        in_var: the variance (torus units) the packing key is planned for, in
+        place of the leveled step's worst case: rotate() passes the product's
+        plus the bridge's (params.private_rotation_plan).
         seeded: encrypt_docs / encrypt_query / encrypt_queries emit the seeded
         payloads of DESIGN.md §8.15: masks from the client's own fresh PUBLIC
         mask key (mask_seed: its 64-bit test form), which travels in every
@@ -282,8 +297,16 @@ class PrivateClient(QueryClient):
         scheme = corpus.scheme.with_msg_bits(corpus.P0)
         self.base_log, self.level = self.gadget = plan_gadget(scheme, corpus.cq)
         # the packing plan sees the leveled step's worst-case variance
-        in_var = extprod_var(scheme, worst_norm2(corpus.cq), *self.gadget) / 2.0 ** 128
+        if in_var is None:
+            in_var = extprod_var(scheme, worst_norm2(corpus.cq), *self.gadget) / 2.0 ** 128
         super().__init__(corpus, count, in_var, pack_seed)
+        self.count = int(count)
+        # key rotation (§8.19): the clients of the generations this one bridges from,
+        # oldest first, their fingerprints and the bridge gadget, once rotate() made this client
+        self._sources = []
+        self.bridge_gadget = None
+        self.bridge_from = None
+        self._key_id = None
         self.pack_base_log, self.pack_level = corpus.engine.pack_gadget
         self.base_log, self.level = self.gadget
         self._enc_key = (np.frombuffer(os.urandom(32), np.uint32).copy() if enc_seed is None
@@ -354,6 +377,100 @@ class PrivateClient(QueryClient):
         eng.set_msg_bits(self.P0)
         return [self._encrypt_w(self.cq.weights(q), i) for q, i in zip(qq, ids)]
 
+    # ------------------------------------------------ key rotation (§8.19) --
+    @property
+    def key_id(self) -> str:
+        """This generation's fingerprint (stored.key_fingerprint of its KSK)."""
+        if self._key_id is None:
+            from .stored import key_fingerprint
+            self._key_id = key_fingerprint(self.corpus.engine.export_key("ksk"))
+        return self._key_id
+
+    @property
+    def generations(self) -> list:
+        """(key_id, client) of every generation this client encrypts queries
+        for, oldest first: the clients rotate() bridged from, then itself."""
+        return [(c.key_id, c) for c in self._sources] + [(self.key_id, self)]
+
+    def rotate(self, key_seed=None, count: int | None = None, bridge_from=None, device: int | None = None,
+               pack_seed=None, bridge_seed=None, noise_seed=None, enc_seed=None, mask_seed=None) -> "PrivateClient":
+        """Key rotation without re-encryption -> the next
+        generation's client: a new EncryptedCorpus with the same CorpusQuant
+        and scheme and fresh keys, one DIRECT bridge key per client of
+        bridge_from (oldest first; default [self]; each must still hold its
+        secret) in bridge slots 0.., one gadget for all, and a packing key
+        planned with the product's and the bridge's variance
+        (params.private_rotation_plan). The new client keeps the source
+        clients: a query is encrypted once per resident generation, under
+        that generation's own key (encrypt_queries_gens). Its eval_keys()
+        carry bridge_from (the sources' fingerprints), bridge_gadget and
+        bridge_keys (seeded: bridge_key_bodies and bridge_mask_keys). The
+        *_seed arguments are the 64-bit test forms; seeded keys and seeded
+        payloads carry over."""
+        from ._lib import BRIDGE_SLOTS
+        from .params import private_rotation_plan
+        srcs = [self] if bridge_from is None else list(bridge_from)
+        if not 1 <= len(srcs) <= BRIDGE_SLOTS:
+            raise ValueError(f"bridge_from names {len(srcs)} generations, a context holds 1 to {BRIDGE_SLOTS} "
+                             "bridge keys")
+        if len({c.key_id for c in srcs}) != len(srcs):
+            raise ValueError("bridge_from names a generation twice")
+        for c in srcs:
+            c.corpus._need()
+        scheme = self.corpus.scheme.with_msg_bits(self.P0)
+        gadget, (b, L), in_var = private_rotation_plan(scheme, worst_norm2(self.cq))
+        if gadget != self.gadget:
+            raise ValueError(f"with a bridge behind it the GGSW gadget becomes {gadget}; the resident documents were "
+                             f"packed for {self.gadget}: re-encrypt them (DESIGN.md §8.19)")
+        new_corpus = EncryptedCorpus(self.cq, self.corpus.scheme)
+        kms = self.corpus.key_mask_seed
+        new_corpus.compile(key_seed=key_seed, device=self.corpus.engine.device.index if device is None else device,
+                           noise_seed=noise_seed, seeded_keys=self.corpus.seeded_keys,
+                           key_mask_seed=None if kms is None else (int(kms) + 16) % 2 ** 64)
+        new = PrivateClient(new_corpus, count=self.count if count is None else count, pack_seed=pack_seed,
+                            enc_seed=enc_seed, seeded=self.seeded, mask_seed=mask_seed, in_var=in_var)
+        for i, c in enumerate(srcs):
+            s_old = c.corpus.engine.export_key("s_big")
+            new_corpus.engine.keygen_bridge_key(
+                s_old, b, L, seed=None if bridge_seed is None else (int(bridge_seed) + i) % 2 ** 64,
+                mask_key=new_corpus.next_key_mask() if new_corpus.seeded_keys else None, slot=i)
+            s_old[:] = 0
+        new._sources = srcs
+        new.bridge_gadget = (b, L)
+        new.bridge_from = [c.key_id for c in srcs]
+        return new
+
+    def eval_keys(self, seeded: bool | None = None) -> dict:
+        """QueryClient.eval_keys; after rotate() also key_id, bridge_from (the
+        fingerprints of the generations the bridge keys come from, row g of
+        bridge_keys from bridge_from[g]), bridge_gadget and bridge_keys
+        (seeded: bridge_key_bodies and bridge_mask_keys), for one source too."""
+        d = super().eval_keys(seeded)
+        if self.bridge_from is None:
+            return d
+        d["key_id"] = np.array([self.key_id])
+        d["bridge_from"] = np.array(self.bridge_from)
+        if "bridge_key" in d:
+            d["bridge_keys"] = d.pop("bridge_key")[None]
+        if "bridge_key_body" in d:
+            d["bridge_key_bodies"] = d.pop("bridge_key_body")[None]
+            d["bridge_mask_keys"] = d.pop("bridge_mask_key")[None]
+        return d
+
+    def encrypt_queries_gens(self, vectors, key_ids=None, id0: int | None = None) -> dict:
+        """Q reduced query vectors -> {key_id: Q payloads}: the same quantized
+        weights encrypted by each listed generation's own client, under its
+        own encryption key (and its own mask key when seeded). key_ids: the
+        fingerprints of the generations resident at the host (default: every
+        generation of self.generations). Payload formats are encrypt_queries'."""
+        gens = dict(self.generations)
+        out = {}
+        for kid in (list(gens) if key_ids is None else [str(k) for k in key_ids]):
+            if kid not in gens:
+                raise ValueError(f"no client of generation {kid} is kept (this client holds {', '.join(gens)})")
+            out[kid] = gens[kid].encrypt_queries(vectors, id0)
+        return out
+
 
 class PrivateServer(QueryServer):
     """The untrusted host: evaluation keys, the CorpusQuant and P0 only."""
@@ -362,6 +479,178 @@ class PrivateServer(QueryServer):
         super().__init__(eval_keys, cq, P0, device, scheme)
         self.base_log, self.level = plan_gadget(self.scheme, cq)
         self._seeded_docs = {}      # mask key bytes -> [(id0, GLWEs, end words)] of the seeded blocks packed so far
+        self._init_store(eval_keys)
+
+    # ----------------------- the resident store and key rotation (§8.19) --
+    def _init_store(self, eval_keys: dict) -> None:
+        # the resident generations, oldest first: {"key_id", "docs" (the operand of search_many), "B"};
+        # the current generation, when it holds documents, is last
+        self._gens = []
+        self._slots = {}            # old generation's fingerprint -> the bridge slot of its key
+        self._note_key_id(eval_keys)
+
+    def _note_key_id(self, eval_keys: dict) -> None:
+        """Keeps what the current generation's fingerprint comes from and
+        nothing else of the dict: its key_id entry, else its ksk words (a few
+        MB), else nothing (a seeded dict: the context exports the ksk it
+        expanded). The fingerprint itself is worked out on first use."""
+        from .stored import _fp
+        self._key_id = _fp(eval_keys["key_id"]) if "key_id" in eval_keys else None
+        self._ksk = eval_keys.get("ksk") if self._key_id is None else None
+
+    @property
+    def key_id(self) -> str:
+        """The current generation's fingerprint: the dict's key_id, else that
+        of the full-form ksk (a seeded dict's: the key this context expanded)."""
+        if self._key_id is None:
+            from .stored import key_fingerprint
+            self._key_id = key_fingerprint(self._ksk if self._ksk is not None else self.engine.export_key("ksk"))
+            self._ksk = None
+        return self._key_id
+
+    @property
+    def generations(self) -> list:
+        """The resident generations, oldest first, as (fingerprint, end)
+        pairs: documents end_{g-1} <= b < end_g are under generation g's key."""
+        out, end = [], 0
+        for g in self._gens:
+            end += g["B"]
+            out.append((g["key_id"], end))
+        return out
+
+    @property
+    def old_generations(self) -> list:
+        """generations without the current key's."""
+        return [(fp, end) for fp, end in self.generations if fp != self.key_id]
+
+    def load(self, block) -> int:
+        """Make a document block (under the CURRENT key) the resident store,
+        in place of whatever was resident; -> the resident count."""
+        docs, B = self.pack_docs_many(block)
+        if B < 1:
+            raise ValueError("an empty document store")
+        for s in self.engine.bridge_slots():  # the old generations' keys serve nothing any more
+            self.engine.drop_bridge_key(s)
+        self._gens, self._slots = [{"key_id": self.key_id, "docs": docs, "B": int(B)}], {}
+        return int(B)
+
+    def append(self, block) -> int:
+        """Add a block encrypted under the CURRENT key after the resident
+        documents; -> the resident count. The block becomes whole GLWEs of the
+        current generation's operand, so it continues a generation only at a
+        GLWE boundary: after B documents with B % (N // D) == 0 (ValueError
+        otherwise; a rotation starts a new operand)."""
+        import torch
+        if not self._gens:
+            return self.load(block)
+        cur = self._gens[-1] if self._gens[-1]["key_id"] == self.key_id else None
+        S = self.scheme.N // len(self.cq.model.q_w)
+        if cur is not None and cur["B"] % S:
+            raise ValueError(f"the current generation holds {cur['B']} documents, its last GLWE is partly filled "
+                             f"({S} documents per GLWE): a block continues a generation only at a GLWE boundary")
+        docs, B = self.pack_docs_many(block)
+        if B < 1:
+            raise ValueError("an empty document block")
+        if cur is None:
+            self._gens.append({"key_id": self.key_id, "docs": docs, "B": int(B)})
+        else:
+            cur["docs"], cur["B"] = torch.cat([cur["docs"], docs]).contiguous(), cur["B"] + int(B)
+        return self.generations[-1][1]
+
+    def rekey(self, eval_keys: dict) -> None:
+        """Key rotation: install the next generation's evaluation keys and
+        bridge keys (PrivateClient.rotate(...).eval_keys()). Every resident
+        document becomes old-generation. The dict must hold a bridge key from
+        EVERY resident generation, the one that was current until now
+        included: ValueError naming the missing fingerprint, before anything
+        changes. Row g of bridge_keys goes into slot g; slots whose generation
+        is not resident are dropped. The single-bridge dict (bridge_key,
+        bridge_from one fingerprint) is accepted too."""
+        if "pack_key" not in eval_keys and "pack_key_body" not in eval_keys:
+            raise ValueError("the evaluation keys hold no packing key")
+        many = "bridge_keys" in eval_keys or "bridge_key_bodies" in eval_keys
+        single = "bridge_key" in eval_keys or "bridge_key_body" in eval_keys
+        if (many or single) and "bridge_from" not in eval_keys:
+            raise ValueError("the evaluation keys hold bridge keys and no bridge_from")
+        src = [str(f) for f in np.asarray(eval_keys["bridge_from"]).reshape(-1)] if many or single else []
+        for g in self._gens:
+            if g["key_id"] not in src:
+                raise ValueError(f"documents under key {g['key_id']} are resident and the evaluation keys hold no "
+                                 f"bridge key from it (they bridge from {', '.join(src) or 'no generation'})")
+        eng = self.engine
+        eng.import_eval_keys(eval_keys)  # row g into slot g (the single form: slot 0)
+        self.bit_levels = int(np.asarray(eval_keys.get("pack_bit_levels", [0])).reshape(-1)[0])
+        self._slots = {g["key_id"]: src.index(g["key_id"]) for g in self._gens}
+        for s in [s for s in eng.bridge_slots() if s not in self._slots.values()]:
+            eng.drop_bridge_key(s)
+        self._note_key_id(eval_keys)
+
+    def _upload_words(self, parts):
+        """uint64 host vectors -> one device tensor, each part copied straight
+        into its place (no concatenated host copy)."""
+        import torch
+        parts = [np.ascontiguousarray(a, dtype=np.uint64) for a in parts]
+        out = torch.empty(sum(a.size for a in parts), dtype=torch.int64, device=self.engine.device)
+        at = 0
+        for a in parts:
+            out[at:at + a.size].copy_(torch.from_numpy(a.view(np.int64)))
+            at += a.size
+        return out
+
+    def search_resident(self, bundle: dict, min_similarity=None) -> list:
+        """bundle: {key_id: Q payloads}, what PrivateClient.encrypt_queries_gens
+        returns: every query once per resident generation, under that
+        generation's key. Generation g's documents meet generation g's GGSWs
+        and the old generations' rows are bridged to the current key, one
+        fhe_search_ggsws_gens_batch per chunk of query_chunks(Q, B) -> a LIST
+        of version-2 replies over all resident documents, oldest generation
+        first, for the CURRENT client's decrypt_replies. A bundle that lacks a
+        resident generation is refused by its fingerprint; each generation's
+        payloads pass check_query_batch on their own (one form per generation)."""
+        from .query import pack_replies, query_chunks, thresholds_for
+        if not self._gens:
+            raise RuntimeError("no resident documents: call load() first")
+        eng = self.engine
+        gens = []
+        for g in self._gens:
+            fp = g["key_id"]
+            if fp not in bundle:
+                raise ValueError(f"documents under key {fp} are resident and the bundle holds no queries for it "
+                                 f"(it holds {', '.join(str(k) for k in bundle) or 'none'})")
+            try:
+                # views, not copies: a bundle carries G times a batch's GGSW words and each is uploaded once
+                pls = [unpack_any_query(p, copy=False) for p in bundle[fp]]
+                seeded = check_query_batch(pls)
+                self._check(pls[0], "query 0")
+                if (pls[0]["base_log"], pls[0]["level"]) != (self.base_log, self.level):
+                    raise ValueError("query 0: gadget differs from the one the documents were packed for")
+            except ValueError as e:
+                raise ValueError(f"generation {fp}: {e}") from None
+            if gens and len(pls) != len(gens[0][1]):
+                raise ValueError(f"generation {fp}: {len(pls)} queries, generation {gens[0][0]['key_id']} "
+                                 f"{len(gens[0][1])}")
+            gens.append((g, pls, seeded))
+        Q, D = len(gens[0][1]), gens[0][1][0]["D"]
+        B = self.generations[-1][1]
+        _, cst, _ = self.plan(None)
+        Ts = [self.plan(t)[2] for t in thresholds_for(min_similarity, Q)]
+        out = []
+        for ch in query_chunks(Q, B):
+            Tc = [Ts[q] for q in ch]
+            items = []
+            for g, pls, seeded in gens:
+                if seeded:   # expanded on this context; the generations entry takes full forms
+                    b = self._upload_words(pls[q]["body"] for q in ch)
+                    w = eng.expand_ggsws_seeded(b, [pls[q]["id0"] for q in ch], self.base_log, self.level,
+                                                pls[0]["mask_key"])
+                else:
+                    w = self._upload_words(pls[q]["ggsw"] for q in ch)
+                slot = -1 if g["key_id"] == self.key_id else self._slots[g["key_id"]]
+                items.append((slot, w, g["docs"], g["B"]))
+            ga, gb = eng.search_ggsws_gens(items, self.base_log, self.level, D, cst, Tc, self.bit_levels)
+            out.append(pack_replies(ga.cpu().numpy().view(np.uint64), gb.cpu().numpy().view(np.uint64), B, self.P0,
+                                    Tc))
+        return out
 
     def _note_seeded_docs(self, bl: dict) -> None:
         """An id must not repeat under one mask key: a seeded block whose ids

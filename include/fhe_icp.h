@@ -1160,6 +1160,60 @@ int fhe_keygen_bridge_key_slot_seeded(fhe_ctx* ctx, int32_t slot, const uint64_t
 int fhe_export_bridge_key_slot_seeded(fhe_ctx* ctx, int32_t slot, uint32_t h_mask_key_out[8], uint64_t* h_body);
 int fhe_import_bridge_key_slot_seeded(fhe_ctx* ctx, int32_t slot, int32_t base_log, int32_t level,
                                       const uint32_t h_mask_key[8], const uint64_t* h_body);
+
+/* ---- both-private key rotation: per-generation GGSW queries
+ * After a key rotation the documents of several generations are resident,
+ * each generation's GLWEs under its own big key. The client sends every query
+ * once per resident generation, as a GGSW under THAT generation's key; the
+ * host multiplies generation g's documents by generation g's GGSWs (the exact
+ * product of fhe_linear_ggsws_batch, nothing switched before it), extracts big
+ * LWEs under the old keys and moves those rows to the current key with the
+ * grouped bridge of fhe_bridge_gens_batch. The bridge's noise is added to the
+ * product's, not multiplied by the query's norm.
+ *
+ * One generation's part of a call. Generations come oldest first,
+ * 1 <= G <= FHE_BRIDGE_SLOTS + 1; at most one entry has slot -1 and it is the
+ * last; no slot is named twice; B = sum B_g >= 1. Document b of generation g
+ * is document off_g + b of the call, off_g = sum_{h<g} B_h (a generation's
+ * documents start a new GLWE of its own operand). */
+typedef struct fhe_ggsw_gen {
+  int32_t struct_size;     /* = sizeof(fhe_ggsw_gen); else FHE_E_ARG */
+  int32_t slot;            /* bridge slot of this generation's key; -1: the context's current key */
+  const uint64_t* d_ggsw;  /* Q GGSWs under THIS generation's big key, gadget (base_log, level) */
+  const void* d_docs;      /* fhe_glwe_docs_queries_pack of this generation's B documents */
+  int64_t B;               /* 0: an empty generation, pointers ignored */
+} fhe_ggsw_gen;
+/* Bytes of product workspace a call takes for its byte planes, results and
+ * constants: fhe_ggsws_ws_bytes summed over the generations with documents,
+ * the Q constants counted once (G = 1: fhe_ggsws_ws_bytes itself). The
+ * launch's tables (56 bytes per generation, 16 per workgroup tile, 4 per row
+ * tile) follow them and are not counted. Host only; 0 for bad arguments. */
+size_t fhe_ggsws_gens_ws_bytes(const fhe_params* params, int64_t Q, const int64_t* h_B, int32_t G, int32_t D,
+                               int32_t level);
+/* The leveled step alone; needs no key and bridges nothing. d_out:
+ * Q*B x (kN+1); row q B + off_g + b is generation g's document b under
+ * generation g's query q with trivial(h_cst[q] Delta) added, under generation
+ * g's key: word for word row q B_g + b of fhe_linear_ggsws_batch on that
+ * generation's operands. The launch count does not depend on G (one tables
+ * kernel, one plane launch, one grouped transposed product, one extraction,
+ * one memset when K is split). Timing goes to the "linear_ggsws" bucket.
+ * FHE_E_ARG first, on host-only contexts too (struct_size, G, slots, nulls,
+ * fhe_linear_ggsws_batch's bounds, a launch beyond 2^31 tiles: "split the
+ * call"), then the device. */
+int fhe_linear_ggsws_gens_batch(fhe_ctx* ctx, const fhe_ggsw_gen* gens, int32_t G, int32_t base_log, int32_t level,
+                                int64_t Q, int32_t D, const int64_t* h_cst, uint64_t* d_out, void* stream);
+/* The evaluation-only server: the leveled step with cst - h_T[q], the grouped
+ * bridge over the rows of the generations with slot >= 0 (timing: "bridge"),
+ * the sign extraction and the two packings of fhe_search_ggsws_batch, the
+ * packings' copy taken after the bridge. Outputs as fhe_search_ggsws_batch
+ * with B = sum B_g. G = 1 with slot -1 equals fhe_search_ggsws_batch word for
+ * word; old generations only (no slot -1 entry) is allowed. FHE_E_ARG first
+ * (as above, and levels_bit), then the device, then FHE_E_STATE: no keys, no
+ * packing key, "no bridge key in slot s" for a named slot with rows, "bridge
+ * gadgets differ". */
+int fhe_search_ggsws_gens_batch(fhe_ctx* ctx, const fhe_ggsw_gen* gens, int32_t G, int32_t base_log, int32_t level,
+                                int64_t Q, int32_t D, int64_t cst, const int64_t* h_T, int32_t levels_bit,
+                                uint64_t* d_glwe_acc, uint64_t* d_glwe_bit, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,12 @@ class fhe_params(C.Structure):
     _fields_ = [("struct_size", C.c_int32)] + [(f, C.c_int32) for f in FIELDS]
 
 
+class fhe_ggsw_gen(C.Structure):
+    # one key generation's part of the *_ggsws_gens_batch entries: slot -1 is the current key
+    _fields_ = [("struct_size", C.c_int32), ("slot", C.c_int32), ("d_ggsw", C.c_void_p), ("d_docs", C.c_void_p),
+                ("B", C.c_int64)]
+
+
 _vp, _i32, _i64, _u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
 _PROTOS = {
     "fhe_ctx_create": (C.c_int, [C.POINTER(fhe_params), C.c_int, C.POINTER(_vp)]),
@@ -119,6 +125,10 @@ _PROTOS = {
     "fhe_compare_ggsws_batch": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
     "fhe_search_ggsws_batch": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _i64, _i32, _i64, _vp, _i32, _vp, _vp,
                                          _vp]),
+    # both sides encrypted, after a key rotation: per-generation queries, one bridge
+    "fhe_ggsws_gens_ws_bytes": (C.c_size_t, [C.POINTER(fhe_params), _i64, _vp, _i32, _i32, _i32]),
+    "fhe_linear_ggsws_gens_batch": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _vp, _vp, _vp]),
+    "fhe_search_ggsws_gens_batch": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp]),
     # both sides encrypted, seeded documents and queries
     "fhe_ggsw_body_words": (C.c_size_t, [C.POINTER(fhe_params), _i32, _i32]),
     "fhe_encrypt_packed_seeded_batch": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _u64, _vp, _vp]),

@@ -1300,6 +1300,164 @@ def private_queries(cq, oq, D: int, n_bits: int, steps: int, warmup: int, Qn: in
     return out
 
 
+def private_rotated(cq, oq, D: int, n_bits: int, gens, steps: int, warmup: int, shapes=((8, 128), (1, 1024)),
+                    leveled_only: bool = False) -> dict:
+    """The both-private search after key rotations, one
+    process. For every G of `gens`: an evaluation-only PrivateServer holding
+    the newest generation's keys and a direct bridge key from each of G old
+    generations, ALL documents old, in equal parts across the G generations
+    (PrivateServer.search_resident, fhe_search_ggsws_gens_batch), against the
+    unrotated PrivateServer.search_many of generation 0 over the same
+    documents. The legs are interleaved in rotating order as rotated_gens
+    does, host clock around each with a device synchronise (payload parse and
+    upload, reply copies included); then a profiled pass for the
+    "linear_ggsws" and "bridge" HIP-event buckets and one for the leveled step
+    alone (Engine.linear_ggsws_gens between stream events, constants' upload
+    included: the A/B of library builds reads it); and
+    the parity of every leg's decrypted replies with the restatement.
+    leveled_only (--no-end-to-end): the leveled step's pass alone, for the
+    alternating-process A/B of library builds."""
+    import numpy as np
+    import torch
+    from oracle import quant_ref as Q
+    from fheicp.corpus import EncryptedCorpus
+    from fheicp.private import PrivateClient, PrivateServer, unpack_any_query
+    search_steps, search_warmup = (0, 0) if leveled_only else (steps, warmup)
+    Gmax, Bmax = max(gens), max(B for _, B in shapes)
+    c0 = EncryptedCorpus(cq).compile(key_seed=5, device=0, noise_seed=6)
+    clients = [PrivateClient(c0, count=1024, pack_seed=17, enc_seed=18)]
+    for g in range(1, Gmax):     # generation g bridges from every generation before it: a store lives through them all
+        clients.append(clients[-1].rotate(key_seed=5 + 2 * g, pack_seed=17 + g, bridge_seed=100 + 10 * g,
+                                          noise_seed=6 + 2 * g, enc_seed=18 + g, bridge_from=list(clients)))
+    keys = [c.eval_keys() for c in clients]
+    plain = PrivateServer(keys[0], cq, c0.P0, scheme=c0.scheme)
+    newest, newest_keys, servers = {}, {}, {}
+    for G in gens:
+        newest[G] = clients[G - 1].rotate(key_seed=50 + 2 * G, pack_seed=60 + G, bridge_seed=200 + 10 * G,
+                                          noise_seed=70 + 2 * G, enc_seed=80 + G, bridge_from=clients[:G])
+        newest_keys[G] = newest[G].eval_keys()
+        servers[G] = PrivateServer(keys[0], cq, c0.P0, scheme=c0.scheme)
+    _, docs = Q.make_corpus(D, Bmax, seed=21)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    first = newest[gens[0]]
+    eng0 = servers[gens[0]].engine
+    out = {"generations": list(gens), "ggsw_gadget": list(first.gadget), "bridge_gadget": list(first.bridge_gadget),
+           "pack_gadget": [first.pack_base_log, first.pack_level], "pack_margin_sigmas": first.margin,
+           "unrotated_pack_gadget": [clients[0].pack_base_log, clients[0].pack_level],
+           "bridge_key_bytes_each": 8 * eng0.bridge_key_words(*first.bridge_gadget), "steps": steps, "warmup": warmup,
+           "shapes": []}
+    for Qn, B in shapes:
+        qs = np.stack([Q.make_corpus(D, 1, seed=100 + i)[0] for i in range(Qn)])
+        plain_docs, _ = plain.pack_docs_many(clients[0].encrypt_docs(docs[:B]))
+        plain_payloads = clients[0].encrypt_queries(qs)
+        runs = {"unrotated": lambda: plain.search_many(plain_payloads, plain_docs, B, 0.5)}
+        bundles, ends_of, blocks = {}, {}, {}
+        for G in gens:
+            if servers[G].generations:       # the shape before: a new host, again under generation 0's keys
+                servers[G].engine.close()
+                servers[G] = PrivateServer(keys[0], cq, c0.P0, scheme=c0.scheme)
+            srv = servers[G]
+            ends = [B * (g + 1) // G for g in range(G)]
+            lo = [0] + ends[:-1]
+            # the store's life: generation 0 loads its part; every later generation rekeys and appends its own;
+            # the newest rekeys last, so ALL documents are old
+            blocks[G] = [clients[g].encrypt_docs(docs[lo[g]:ends[g]]) for g in range(G)]
+            srv.load(blocks[G][0])
+            for g in range(1, G):
+                srv.rekey(keys[g])
+                srv.append(blocks[G][g])
+            srv.rekey(newest_keys[G])
+            assert srv.old_generations == srv.generations == [(clients[g].key_id, ends[g]) for g in range(G)]
+            bundles[G] = newest[G].encrypt_queries_gens(qs, key_ids=[c.key_id for c in clients[:G]])
+            ends_of[G] = ends
+            runs[f"resident_g{G}"] = (lambda srv=srv, G=G: srv.search_resident(bundles[G], 0.5))
+        names = list(runs)
+        t = {k: [] for k in runs}
+        last = {}
+        for i in range(search_warmup + search_steps):
+            for j in range(len(names)):                      # a rotating order: every leg in every position
+                k = names[(i + j) % len(names)] if i % 2 == 0 else names[(i - j) % len(names)]
+                sec, last[k] = timed(runs[k])
+                if i >= search_warmup:
+                    t[k].append(sec)
+        ref = np.stack([Q.corpus_accumulate(oq, cq.s_e, n_bits, q, docs[:B]) for q in qs])
+        scores = np.float64(Q.corpus_out_scale(oq, cq.s_e)) * ref.astype(np.float64)
+        exact = {}
+        for k in (() if leveled_only else runs):
+            who = clients[0] if k == "unrotated" else newest[int(k.rsplit("g", 1)[1])]
+            acc, below = who.decrypt_replies(last[k])
+            exact[k] = bool(np.array_equal(acc.cpu().numpy(), ref) and
+                            np.array_equal(below.cpu().numpy(), (scores < 0.5).astype(np.int64)))
+        # the HIP-event split, in passes of their own: three rounds of five searches per leg
+        kerns = ("linear_ggsws", "bridge", "pack")
+        split, kernels = {k: [] for k in runs}, {}
+        for _ in range(0 if leveled_only else 3):
+            for k in runs:
+                eng = plain.engine if k == "unrotated" else servers[int(k.rsplit("g", 1)[1])].engine
+                eng.profile(True)
+                for kern in kerns:
+                    eng.profile_read(kern)
+                for _ in range(5):
+                    runs[k]()
+                torch.cuda.synchronize()
+                split[k].append({kern: eng.profile_read(kern)["total_ms"] / 5 for kern in kerns})
+                kernels[k] = eng.kernel_name("linear_ggsws")
+                eng.profile(False)
+        # the leveled step alone on each rotated server's operands: the "linear_ggsws" bucket per call
+        leveled = {}
+        for G in gens:
+            srv = servers[G]
+            eng = srv.engine
+            items = []
+            for g, block in enumerate(blocks[G]):      # rekey puts the bridge from generation g into slot g
+                pls = [unpack_any_query(p) for p in bundles[G][clients[g].key_id]]
+                operand, Bg = srv.pack_docs_many(block)
+                items.append((g, eng.to_dev(np.concatenate([pl["ggsw"] for pl in pls])), operand, Bg))
+            buf = eng.empty_big(Qn * B)
+            per = []
+            # stream events around the whole call: the loop build's scatters lie outside its buckets
+            for i in range(warmup + steps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                eng.linear_ggsws_gens(items, *first.gadget, D, [0] * Qn, out=buf)
+                e1.record()
+                torch.cuda.synchronize()
+                if i >= warmup:
+                    per.append(e0.elapsed_time(e1))
+            leveled[f"g{G}"] = {"median_ms": statistics.median(per), "min_ms": min(per), "max_ms": max(per),
+                                "kernel": eng.kernel_name("linear_ggsws")}
+        if leveled_only:
+            out["shapes"].append({"Q": Qn, "B": B, "ends": {f"g{G}": ends_of[G] for G in gens},
+                                  "leveled_step_ms": leveled, "bit_exact": {}, "meets_bar": {}})
+            continue
+        med = {k: statistics.median(v) * 1e3 for k, v in t.items()}
+        out["shapes"].append({
+            "Q": Qn, "B": B, "ends": {f"g{G}": ends_of[G] for G in gens}, "ms_per_search": med,
+            "min_ms": {k: min(v) * 1e3 for k, v in t.items()},
+            "ratio_over_unrotated": {k: med[k] / med["unrotated"] for k in med},
+            "meets_bar": {k: med[k] <= 1.10 * med["unrotated"] for k in med if k != "unrotated"},
+            "event_ms_per_search": {k: {kern: statistics.median(r[kern] for r in v) for kern in kerns}
+                                    for k, v in split.items()},
+            "linear_ggsws_kernel": kernels, "leveled_step_ms": leveled,
+            "query_bytes": {k: int(sum(p.nbytes for v in bundles[int(k.rsplit("g", 1)[1])].values() for p in v))
+                            if k != "unrotated" else int(sum(p.nbytes for p in plain_payloads)) for k in runs},
+            "bit_exact": exact})
+    out["bit_exact"] = all(all(s["bit_exact"].values()) for s in out["shapes"])
+    out["meets_bar"] = all(all(s["meets_bar"].values()) for s in out["shapes"])
+    for srv in [plain] + list(servers.values()):
+        srv.engine.close()
+    for c in clients + list(newest.values()):
+        c.corpus.engine.close()
+    return out
+
+
 def seeded_private(cq, oq, D: int, n_bits: int, steps: int, warmup: int, Qn: int = 8, B: int = 128,
                    load_sizes=(1024, 65536)) -> dict:
     """The both-private search on seeded payloads against the
@@ -1621,6 +1779,13 @@ def main() -> int:
                          "With --rotated: G old generations resident (DESIGN.md §8.17), legs \"G old generations in "
                          "equal parts\", \"all one old generation\" and \"none old\" with the bridge bucket's "
                          "HIP-event time; writes profiles/r20/rotated_gens.json. Default 1: --rotated as it was")
+    ap.add_argument("--private-rotated", action="store_true",
+                    help="the both-private search after key rotations (16-dim, n_bits 6, two-party, DESIGN.md §8.19): "
+                         "PrivateServer.search_resident with all documents old, in equal parts across G old "
+                         "generations, for G in {1, 3} (or the one G of --generations), against the unrotated "
+                         "search_many of the same process, at 8 queries x 128 documents and 1 x 1024, 24 interleaved "
+                         "steps after 4 warm-up, with the \"linear_ggsws\" and \"bridge\" buckets' HIP-event times "
+                         "and the leveled step alone; writes profiles/r22/private_rotated.json")
     ap.add_argument("--plain-first", action="store_true",
                     help="with --stored-tenants --generations 1: build and run the default hub before the "
                          "rotation_schedules hub (the order's own effect on the comparison)")
@@ -1658,7 +1823,8 @@ def main() -> int:
     a = ap.parse_args()
     a.generations_given = any(x == "--generations" or x.startswith("--generations=") for x in sys.argv[1:])
     if a.out is None:
-        a.out = str(REPO / "profiles" / ("r19/seeded_keys.json" if a.seeded_keys else
+        a.out = str(REPO / "profiles" / ("r22/private_rotated.json" if a.private_rotated else
+                                         "r19/seeded_keys.json" if a.seeded_keys else
                                          "r18/seeded_private.json" if a.seeded_private else
                                          "r17/private_tenants.json" if a.private_tenants else
                                          "r21/stored_tenants_gens.json" if a.stored_tenants and a.generations_given
@@ -1677,6 +1843,23 @@ def main() -> int:
         return 2
     from fheicp.engine import Engine
     from fheicp.params import params_for_bits
+    if a.private_rotated:
+        from fheicp import _lib
+        if not 1 <= a.generations <= _lib.BRIDGE_SLOTS:
+            ap.error(f"--generations is 1 to {_lib.BRIDGE_SLOTS}")
+        cq, oq = corpus_quant(16, 6)
+        gens = (a.generations,) if a.generations_given else (1, 3)
+        pr = private_rotated(cq, oq, 16, 6, gens, steps=24, warmup=4, leveled_only=a.no_end_to_end)
+        res = {"bench": "query_bench --private-rotated" + (f" --generations {a.generations}" if a.generations_given
+                                                            else ""),
+               "device": torch.cuda.get_device_name(0), "D": 16, "n_bits": 6, "P0": cq.worst_msg_bits(),
+               "build": _lib.lib().fhe_build_info().decode(), "lib": Path(_lib.LIB_PATH).name, "private_rotated": pr,
+               "bit_exact": pr["bit_exact"], "meets_bar": pr["meets_bar"]}
+        line = json.dumps(res)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(line + "\n")
+        print(line)
+        return 0
     if a.seeded_keys:
         cq, oq = corpus_quant(16, 6)
         sk = seeded_keys(cq, oq, 16, 6, steps=8, warmup=2)
