@@ -13,11 +13,9 @@
 //   k_pack.h          LWE -> GLWE packing key switch (two-party replies): wide
 //                     digits, key generation, rotation, packed decryption
 //   k_bridge.h        LWE -> LWE bridge key switch (key rotation of stored
-//                     ciphertexts): key generation, mapped digits, scatter
-//   k_bridge_grp.h    its group form: several old generations' rows in one
-//                     digits launch, one group GEMM and one scatter
-//   k_bridge_hub.h    the same over (tenant, generation) segments of a group's
-//                     padded rows: every tenant's rotation schedule in one pass
+//                     ciphertexts): key generation, mapped digits and scatter
+//                     for one key's rows and for segments with a key each
+//                     (several old generations, every tenant of a group)
 //   k_extprod.h       both-private search: GGSW query encryption, GLWE document
 //                     digits, Toeplitz byte planes, slot extraction
 //   k_extprod_q.h     both-private search, Q queries in one pass: reversed
@@ -49,8 +47,6 @@
 #include "k_query.h"
 #include "k_pack.h"
 #include "k_bridge.h"
-#include "k_bridge_grp.h"
-#include "k_bridge_hub.h"
 #include "k_extprod.h"
 #include "k_extprod_q.h"
 #include "k_private_seeded.h"
@@ -145,7 +141,7 @@ struct fhe_ctx {
   // slot 0 is the bridge key of §8.12, the others serve further old
   // generations (§8.17)
   GadgetKey bridge_keys[FHE_BRIDGE_SLOTS];
-  DevBuf bridge_ws;         // (the group form's tables |) digits | bodies | the GEMM's count x (kN+1) compact result
+  DevBuf bridge_ws;         // (a segmented pass's tables |) digits | bodies | the GEMM's count x (kN+1) compact result
   ProfAcc prof_bridge;      // fhe_bridge_batch: k_bridge_digits + the GEMM + k_bridge_scatter
   // both-private search (k_extprod.h): the query's Toeplitz byte planes |
   // zero bodies | the GEMM's G x (k+1)N result, allocated on first use
@@ -2708,118 +2704,167 @@ static int gens_args(fhe_ctx* ctx, int64_t B, int32_t G, const int64_t* h_ends, 
   }
   return FHE_OK;
 }
-// blocks of 128 rows and digit groups of 16 rows over the generations' segments
-struct GensCount {
-  int64_t nblk = 0, ndg = 0, rows = 0;
-};
-static GensCount gens_count(int64_t Q, int32_t G, const int64_t* h_ends) {
-  GensCount c;
+extern "C++" {
+// The generations with documents of a row map, oldest first: f(slot, d0, n)
+// for the n documents from d0 on; stops at the first nonzero return.
+template <typename F>
+static int for_gens(int32_t G, const int64_t* h_ends, const int32_t* h_slots, F&& f) {
   for (int g = 0; g < G; ++g) {
-    const int64_t n = Q * (h_ends[g] - (g ? h_ends[g - 1] : 0));
-    c.nblk += (n + KSM_CTS - 1) / KSM_CTS;
-    c.ndg += (n + 15) / 16;
-    c.rows += n;
+    const int64_t d0 = g ? h_ends[g - 1] : 0, n = h_ends[g] - d0;
+    if (n == 0) continue;
+    if (int rc = f((int)h_slots[g], d0, n)) return rc;
   }
-  return c;
+  return FHE_OK;
+}
+// The same walk after the device check, with the key checks of a generation
+// before f(slot, key, d0, n) sees it: its slot holds a key (need_bridge_slot's
+// code and message) and that key has the gadget of the first such generation's
+// (FHE_E_STATE; the first is named by its slot when name_first). err(code,
+// message) words the context and returns the code.
+template <typename Err, typename F>
+static int for_gen_keys(fhe_ctx* ctx, int32_t G, const int64_t* h_ends, const int32_t* h_slots, bool name_first,
+                        Err&& err, F&& f) {
+  const GadgetKey* first = nullptr;
+  int first_slot = 0;
+  return for_gens(G, h_ends, h_slots, [&](int slot, int64_t d0, int64_t n) {
+    int rc = need_bridge_slot(ctx, slot);
+    if (rc) return err(rc, std::string(fhe_last_error(ctx)));
+    const GadgetKey& k = ctx->bridge_keys[slot];
+    if (!first) first = &k, first_slot = slot;
+    if (k.beta != first->beta || k.level != first->level)
+      return err(FHE_E_STATE,
+                 "bridge gadgets differ: slot " + std::to_string(slot) + " holds (" + std::to_string(k.beta) + ", " +
+                     std::to_string(k.level) + "), " +
+                     (name_first ? "slot " + std::to_string(first_slot) : std::string("an earlier generation's slot")) +
+                     " (" + std::to_string(first->beta) + ", " + std::to_string(first->level) + ")");
+    return f(slot, k, d0, n);
+  });
+}
+}  // extern "C++"
+static size_t up16(size_t x) { return (x + 15) / 16 * 16; }
+// One segmented pass (k_bridge.h): the segments whose keys share the gadget
+// (beta, level), a key's byte planes each, and what they add up to in blocks
+// of 128 rows, digit groups of 16 rows and compact rows.
+struct BridgePass {
+  int beta = 0, level = 0;
+  int64_t nblk = 0, ndg = 0, rows = 0;
+  std::vector<BridgeSeg> segs;
+  std::vector<const void*> planes;
+  // the n > 0 documents from doc0 on of a Q x B result at buffer row row0
+  void add(int64_t Q, int64_t n, int64_t doc0, int64_t B, int64_t row0, const void* key_planes) {
+    segs.push_back(BridgeSeg{rows, n, doc0, B, row0});
+    planes.push_back(key_planes);
+    rows += Q * n;
+    nblk += (Q * n + KSM_CTS - 1) / KSM_CTS;
+    ndg += (Q * n + 15) / 16;
+  }
+  bool fits() const { return ndg <= 65535 && 8 * nblk <= 65535; }  // the launches' grid limits
+  // the workspace: starts | ends | the segment records | the key table | the
+  // block table | digits | bodies | the compact result
+  void layout(int big, size_t off[5]) const {
+    off[0] = up16(8 * segs.size() * (3 + BRIDGE_SEG_WORDS));        // the block table
+    off[1] = off[0] + up16(sizeof(KsGrpBlock) * (size_t)nblk);      // digits
+    off[2] = off[1] + (size_t)ndg * 16 * (size_t)(big * level);     // bodies
+    off[3] = off[2] + up16(8 * (size_t)rows);                       // the compact result
+    off[4] = off[3] + 8 * (size_t)rows * (size_t)(big + 1);
+  }
+};
+// One pass on the rows of d_ct, in place, in the workspace w of layout()'s
+// off[4] bytes: the tables (store_words in stream order, then the block
+// table), the digits, the group GEMM and the copy back. One bracket in ctx's
+// "bridge" bucket, items = the pass's rows.
+static int bridge_pass_launch(fhe_ctx* ctx, char* w, u64* d_ct, const BridgePass& ps, hipStream_t st) {
+  const int big = ctx->p.k * ctx->p.N, n1 = big + 1, NB = (n1 + KSM_NB_COLS - 1) / KSM_NB_COLS;
+  const size_t S = ps.segs.size();
+  size_t off[5];
+  ps.layout(big, off);
+  std::vector<u64> words(S * (3 + BRIDGE_SEG_WORDS));
+  for (size_t s = 0; s < S; ++s) {
+    const BridgeSeg& sg = ps.segs[s];
+    words[s] = (u64)sg.start;
+    words[S + s] = (u64)(s + 1 < S ? ps.segs[s + 1].start : ps.rows);  // segments follow each other unpadded
+    memcpy(&words[2 * S + s * BRIDGE_SEG_WORDS], &sg, sizeof(BridgeSeg));
+    words[(2 + BRIDGE_SEG_WORDS) * S + s] = (u64)(uintptr_t)ps.planes[s];
+  }
+  int64_t* se = (int64_t*)w;
+  BridgeSeg* seg = (BridgeSeg*)(se + 2 * S);
+  const void** keys = (const void**)(se + (2 + BRIDGE_SEG_WORDS) * S);
+  KsGrpBlock* blk = (KsGrpBlock*)(w + off[0]);
+  uint32_t* Dg = (uint32_t*)(w + off[1]);
+  u64* body = (u64*)(w + off[2]);
+  u64* M = (u64*)(w + off[3]);
+  const int KB = big * ps.level / 64;
+  // the single bridge's split rule on the launch's blocks x column blocks
+  const auto [Sk, kslice] = ksm_split(KB, ps.nblk * NB, 512);
+  hipEvent_t e1;
+  prof_begin(ctx, ctx->prof_bridge, st, &e1);
+  int rc = store_words(ctx, (u64*)w, words.data(), (int64_t)words.size(), st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_ks_grp_tables, dim3((unsigned)((ps.nblk + 255) / 256)), dim3(256), 0, st, (const int64_t*)se,
+                     (int)S, ps.nblk, blk);
+  // the digits kernel also zeroes the compact rows the split's atomics add into
+  hipLaunchKernelGGL(k_bridge_digits_seg, dim3((unsigned)(big / 64), (unsigned)(8 * ps.nblk)), dim3(256), 0, st,
+                     (const u64*)d_ct, (const KsGrpBlock*)blk, (const BridgeSeg*)seg, big, ps.beta, ps.level, KB, Dg,
+                     body, Sk > 1 ? n1 : 0, M);
+  ctx->prof_bridge.kernel = "k_keyswitch_mfma_grp<8, 1>";
+  hipLaunchKernelGGL((k_keyswitch_mfma_grp<8, 1>), dim3((unsigned)(ps.nblk * NB * Sk)), dim3(256), 0, st,
+                     (const v4i*)Dg, (const v4i* const*)keys, (const KsGrpBlock*)blk, (const u64*)body, n1, NB, KB, 0,
+                     Sk, kslice, M);
+  hipLaunchKernelGGL(k_bridge_scatter_seg, dim3((unsigned)(8 * ps.nblk), (unsigned)((n1 + 255) / 256)), dim3(256), 0,
+                     st, (const u64*)M, (const KsGrpBlock*)blk, (const BridgeSeg*)seg, n1, d_ct);
+  prof_end(ctx, ctx->prof_bridge, st, e1, ps.rows);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+// a context's row map as one pass: a segment per generation with documents,
+// row0 = 0 (the keys are in place: after gens_ready's checks)
+static BridgePass gens_pass(fhe_ctx* ctx, int64_t Q, int64_t B, int32_t G, const int64_t* h_ends,
+                            const int32_t* h_slots) {
+  BridgePass ps;
+  for_gens(G, h_ends, h_slots, [&](int slot, int64_t d0, int64_t n) {
+    const GadgetKey& k = ctx->bridge_keys[slot];
+    ps.beta = k.beta, ps.level = k.level;
+    ps.add(Q, n, d0, B, 0, k.planes);
+    return (int)FHE_OK;
+  });
+  return ps;
 }
 // After the device check and before anything is queued: every named slot with
 // rows holds a key (FHE_E_STATE naming the slot), those keys share one gadget
-// (FHE_E_STATE), and the launch limits hold (FHE_E_ARG; the group form's over
-// all generations, the loop's per generation).
-static int gens_ready(fhe_ctx* ctx, int64_t Q, int32_t G, const int64_t* h_ends, const int32_t* h_slots) {
-  const GadgetKey* first = nullptr;
-  for (int g = 0; g < G; ++g) {
-    const int64_t n = h_ends[g] - (g ? h_ends[g - 1] : 0);
-    if (n == 0) continue;
-    int rc = need_bridge_slot(ctx, h_slots[g]);
-    if (rc) return rc;
-    const GadgetKey& k = ctx->bridge_keys[h_slots[g]];
-    if (!first) first = &k;
-    if (k.beta != first->beta || k.level != first->level)
-      return fail(ctx, FHE_E_STATE, "bridge gadgets differ: slot " + std::to_string(h_slots[g]) + " holds (" +
-                                        std::to_string(k.beta) + ", " + std::to_string(k.level) +
-                                        "), an earlier generation's slot (" + std::to_string(first->beta) + ", " +
-                                        std::to_string(first->level) + ")");
-    if (!FHEICP_GRP_BRIDGE && (Q * n + 15) / 16 > 65535)
-      return fail(ctx, FHE_E_ARG, "bridge batch too large: split the call");
-  }
-  const GensCount c = gens_count(Q, G, h_ends);
-  if (FHEICP_GRP_BRIDGE && (c.ndg > 65535 || 8 * c.nblk > 65535))
+// (FHE_E_STATE), and the launch limits hold (FHE_E_ARG; the segmented pass's
+// over all generations, the loop's per generation).
+static int gens_ready(fhe_ctx* ctx, int64_t Q, int64_t B, int32_t G, const int64_t* h_ends, const int32_t* h_slots) {
+  int rc = for_gen_keys(
+      ctx, G, h_ends, h_slots, false, [&](int code, const std::string& msg) { return fail(ctx, code, msg); },
+      [&](int, const GadgetKey&, int64_t, int64_t n) {
+        if (!FHEICP_GRP_BRIDGE && (Q * n + 15) / 16 > 65535)
+          return fail(ctx, FHE_E_ARG, "bridge batch too large: split the call");
+        return (int)FHE_OK;
+      });
+  if (rc) return rc;
+  if (FHEICP_GRP_BRIDGE && !gens_pass(ctx, Q, B, G, h_ends, h_slots).fits())
     return fail(ctx, FHE_E_ARG, "bridge batch too large (more than 65535 digit groups of 16 rows, or 8191 blocks of "
                                 "128 rows, over all generations): split the call");
   return FHE_OK;
 }
 // The bridge of every generation's rows of d_ct (Q x B big LWEs, in place),
-// after gens_args and gens_ready. Group form: the tables (one launch each for
-// the host's values and the block table), k_bridge_digits_grp, the group GEMM
-// and k_bridge_scatter_grp; bridge_ws holds
-//   starts | ends | the generation table | the key table | the block table |
-//   digits | bodies | the compact result.
+// after gens_args and gens_ready: one segmented pass in ctx->bridge_ws.
 static int bridge_gens_impl(fhe_ctx* ctx, uint64_t* d_ct, int64_t Q, int64_t B, int32_t G, const int64_t* h_ends,
                             const int32_t* h_slots, hipStream_t st) {
-  const fhe_params& p = ctx->p;
-  const GensCount c = gens_count(Q, G, h_ends);
-  if (c.rows == 0) return FHE_OK;
-  const int big = p.k * p.N;
-  if (!FHEICP_GRP_BRIDGE) {
-    for (int g = 0; g < G; ++g) {
-      const int64_t d0 = g ? h_ends[g - 1] : 0, n = h_ends[g] - d0;
-      if (n == 0) continue;
+  const int big = ctx->p.k * ctx->p.N;
+  if (!FHEICP_GRP_BRIDGE)
+    return for_gens(G, h_ends, h_slots, [&](int slot, int64_t d0, int64_t n) {
       // the single bridge's row map on the rows from document d0 on: row q B + j there is row q B + d0 + j here
       u64* base = d_ct + (size_t)d0 * (big + 1);
-      int rc = bridge_impl(ctx, ctx->bridge_keys[h_slots[g]], base, Q, B, n, base, st);
-      if (rc) return rc;
-    }
-    return FHE_OK;
-  }
-  BridgeGensArg a{};
-  const GadgetKey* key0 = nullptr;
-  int64_t start = 0;
-  for (int g = 0; g < G; ++g) {
-    const int64_t d0 = g ? h_ends[g - 1] : 0, n = h_ends[g] - d0;
-    a.start[g] = start;
-    a.n[g] = n;
-    a.doc0[g] = d0;
-    a.planes[g] = ctx->bridge_keys[h_slots[g]].planes;  // an empty generation's is never read
-    if (n && !key0) key0 = &ctx->bridge_keys[h_slots[g]];
-    start += Q * n;
-  }
-  const int levels = key0->level;
-  const int K = big * levels, KB = K / 64, n1 = big + 1, NB = (n1 + KSM_NB_COLS - 1) / KSM_NB_COLS;
-  const size_t tbytes = ((size_t)G * (16 + sizeof(BridgeGen) + 8) + 15) / 16 * 16;
-  const size_t kbytes = (sizeof(KsGrpBlock) * (size_t)c.nblk + 15) / 16 * 16;
-  const size_t dbytes = (size_t)c.ndg * 16 * K, bbytes = (8 * (size_t)c.rows + 15) / 16 * 16;
-  const size_t need = tbytes + kbytes + dbytes + bbytes + 8 * (size_t)c.rows * n1;
-  int rc = reserve(ctx, ctx->bridge_ws, need, FHE_E_DEVICE, "hipMalloc of the bridge workspace failed");
+      return bridge_impl(ctx, ctx->bridge_keys[slot], base, Q, B, n, base, st);
+    });
+  const BridgePass ps = gens_pass(ctx, Q, B, G, h_ends, h_slots);
+  if (ps.rows == 0) return FHE_OK;
+  size_t off[5];
+  ps.layout(big, off);
+  int rc = reserve(ctx, ctx->bridge_ws, off[4], FHE_E_DEVICE, "hipMalloc of the bridge workspace failed");
   if (rc) return rc;
-  char* w = (char*)ctx->bridge_ws.p;
-  int64_t* se = (int64_t*)w;
-  BridgeGen* gen = (BridgeGen*)(se + 2 * G);
-  const void** keys = (const void**)(gen + G);
-  KsGrpBlock* blk = (KsGrpBlock*)(w + tbytes);
-  uint32_t* Dg = (uint32_t*)(w + tbytes + kbytes);
-  u64* body = (u64*)(w + tbytes + kbytes + dbytes);
-  u64* M = (u64*)(w + tbytes + kbytes + dbytes + bbytes);
-  // the single bridge's split rule on the launch's blocks x column blocks
-  const auto [S, kslice] = ksm_split(KB, c.nblk * NB, 512);
-  hipEvent_t e1;
-  prof_begin(ctx, ctx->prof_bridge, st, &e1);
-  hipLaunchKernelGGL(k_bridge_grp_setup, dim3(1), dim3(64), 0, st, a, (int)G, Q, se, gen, keys);
-  hipLaunchKernelGGL(k_ks_grp_tables, dim3((unsigned)((c.nblk + 255) / 256)), dim3(256), 0, st, (const int64_t*)se,
-                     (int)G, c.nblk, blk);
-  // the digits kernel also zeroes the compact rows the split's atomics add into
-  hipLaunchKernelGGL(k_bridge_digits_grp, dim3((unsigned)(big / 64), (unsigned)(8 * c.nblk)), dim3(256), 0, st, d_ct,
-                     (const KsGrpBlock*)blk, (const BridgeGen*)gen, B, big, key0->beta, levels, KB, Dg, body,
-                     S > 1 ? n1 : 0, M);
-  ctx->prof_bridge.kernel = "k_keyswitch_mfma_grp<8, 1>";
-  hipLaunchKernelGGL((k_keyswitch_mfma_grp<8, 1>), dim3((unsigned)(c.nblk * NB * S)), dim3(256), 0, st,
-                     (const v4i*)Dg, (const v4i* const*)keys, (const KsGrpBlock*)blk, (const u64*)body, n1, NB, KB, 0,
-                     S, kslice, M);
-  hipLaunchKernelGGL(k_bridge_scatter_grp, dim3((unsigned)(8 * c.nblk), (unsigned)((n1 + 255) / 256)), dim3(256), 0,
-                     st, (const u64*)M, (const KsGrpBlock*)blk, (const BridgeGen*)gen, B, n1, d_ct);
-  prof_end(ctx, ctx->prof_bridge, st, e1, c.rows);
-  HIPCHK(ctx, hipGetLastError());
-  return FHE_OK;
+  return bridge_pass_launch(ctx, (char*)ctx->bridge_ws.p, d_ct, ps, st);
 }
 
 int fhe_bridge_gens_batch(fhe_ctx* ctx, uint64_t* d_ct, int64_t Q, int64_t B, int32_t G, const int64_t* h_ends,
@@ -2832,7 +2877,7 @@ int fhe_bridge_gens_batch(fhe_ctx* ctx, uint64_t* d_ct, int64_t Q, int64_t B, in
   if (rc) return rc;
   if (!d_ct) return fail(ctx, FHE_E_ARG, "null bridge buffers");
   if ((rc = need_device(ctx))) return rc;
-  if ((rc = gens_ready(ctx, Q, G, h_ends, h_slots))) return rc;
+  if ((rc = gens_ready(ctx, Q, B, G, h_ends, h_slots))) return rc;
   return bridge_gens_impl(ctx, d_ct, Q, B, G, h_ends, h_slots, (hipStream_t)stream);
 }
 
@@ -3154,7 +3199,7 @@ int fhe_search_seeded_queries_gens_batch(fhe_ctx* ctx, const uint64_t* d_body, c
   if ((rc = gens_args(ctx, B, G, h_ends, h_slots))) return rc;
   if ((rc = need_eval_keys(ctx))) return rc;
   if ((rc = need_pack_key(ctx))) return rc;
-  if ((rc = gens_ready(ctx, Q, G, h_ends, h_slots))) return rc;
+  if ((rc = gens_ready(ctx, Q, B, G, h_ends, h_slots))) return rc;
   if (levels_bit > ctx->pack_key.level)
     return fail(ctx, FHE_E_ARG, "search seeded queries levels_bit exceeds the packing key's levels");
   QueryWs w;
@@ -4776,7 +4821,6 @@ int fhe_search_seeded_queries_group_batch(fhe_group* g, const fhe_group_corpus* 
 }
 
 // ---- rotation schedules in a group: one bridge for all tenants (§8.18) -----
-static size_t up16(size_t x) { return (x + 15) / 16 * 16; }
 // One tenant's row map as the two entries below hand it over.
 struct GrpRowMap {
   int64_t Q = 0, B = 0;  // Q = 0: the tenant sits this call out
@@ -4784,132 +4828,57 @@ struct GrpRowMap {
   const int64_t* h_ends = nullptr;
   const int32_t* h_slots = nullptr;
 };
-// One GEMM depth: the segments of the tenants whose bridge gadget is (beta, level).
-struct GrpBridgePass {
-  int beta = 0, level = 0;
-  int64_t nblk = 0, ndg = 0, rows = 0;
-  std::vector<BridgeSeg> segs;
-  std::vector<const void*> planes;
-};
 // After the device and key checks and before anything is queued: every named
 // slot with rows holds a key (FHE_E_STATE naming tenant and slot), a tenant's
 // keys share one gadget (FHE_E_STATE), then the launch limits of every pass
 // (FHE_E_ARG). Fills the passes, one per distinct gadget in order of first
 // appearance; starts: fhe_group_rows' for counts[t] = Q_t B_t.
 static int grp_bridge_plan(const fhe_group* g, const std::vector<GrpRowMap>& maps, const int64_t* starts,
-                           std::vector<GrpBridgePass>* passes) {
+                           std::vector<BridgePass>* passes) {
   passes->clear();
   for (size_t t = 0; t < maps.size(); ++t) {
     const GrpRowMap& m = maps[t];
     if (!m.Q) continue;
-    fhe_ctx* ctx = g->ctxs[t];
-    const std::string who = "tenant " + std::to_string(t) + ": ";
-    const GadgetKey* first = nullptr;
-    int first_slot = 0;
-    for (int gi = 0; gi < m.G; ++gi) {
-      const int64_t d0 = gi ? m.h_ends[gi - 1] : 0, n = m.h_ends[gi] - d0;
-      if (n == 0) continue;
-      const int slot = m.h_slots[gi];
-      int rc = need_bridge_slot(ctx, slot);
-      if (rc) return gfail(rc, who + fhe_last_error(ctx));
-      const GadgetKey& k = ctx->bridge_keys[slot];
-      if (!first) first = &k, first_slot = slot;
-      if (k.beta != first->beta || k.level != first->level)
-        return gfail(FHE_E_STATE, who + "bridge gadgets differ: slot " + std::to_string(slot) + " holds (" +
-                                      std::to_string(k.beta) + ", " + std::to_string(k.level) + "), slot " +
-                                      std::to_string(first_slot) + " (" + std::to_string(first->beta) + ", " +
-                                      std::to_string(first->level) + ")");
-      GrpBridgePass* ps = nullptr;
-      for (GrpBridgePass& q : *passes)
-        if (q.beta == k.beta && q.level == k.level) ps = &q;
-      if (!ps) {
-        passes->emplace_back();
-        ps = &passes->back();
-        ps->beta = k.beta;
-        ps->level = k.level;
-      }
-      const int64_t rows = m.Q * n;
-      ps->segs.push_back(BridgeSeg{ps->rows, n, d0, m.B, starts[t]});
-      ps->planes.push_back(k.planes);
-      ps->rows += rows;
-      ps->nblk += (rows + KSM_CTS - 1) / KSM_CTS;
-      ps->ndg += (rows + 15) / 16;
-    }
+    int rc = for_gen_keys(
+        g->ctxs[t], m.G, m.h_ends, m.h_slots, true,
+        [&](int code, const std::string& msg) { return gfail(code, "tenant " + std::to_string(t) + ": " + msg); },
+        [&](int, const GadgetKey& k, int64_t d0, int64_t n) {
+          BridgePass* ps = nullptr;
+          for (BridgePass& q : *passes)
+            if (q.beta == k.beta && q.level == k.level) ps = &q;
+          if (!ps) {
+            passes->emplace_back();
+            ps = &passes->back();
+            ps->beta = k.beta;
+            ps->level = k.level;
+          }
+          ps->add(m.Q, n, d0, m.B, starts[t], k.planes);
+          return (int)FHE_OK;
+        });
+    if (rc) return rc;
   }
-  for (const GrpBridgePass& ps : *passes)
-    if (ps.ndg > 65535 || 8 * ps.nblk > 65535)
+  for (const BridgePass& ps : *passes)
+    if (!ps.fits())
       return gfail(FHE_E_ARG, "bridge batch too large (more than 65535 digit groups of 16 rows, or 8191 blocks of "
                               "128 rows, over all segments of a pass): split the call");
   return FHE_OK;
 }
-// The passes of a plan on the group's padded rows d_ct, in place. Per pass:
-// the tables (store_words in stream order, then the block table), the digits,
-// the group GEMM and the copy back; the group's bridge workspace holds
-//   starts | ends | the segment records | the key table | the block table |
-//   digits | bodies | the compact result
-// of the largest pass. Timing goes to the "bridge" bucket of the group's first
-// context, one bracket per pass.
-static int grp_bridge_launch(fhe_group* g, u64* d_ct, const std::vector<GrpBridgePass>& passes, hipStream_t st) {
-  if (passes.empty()) return FHE_OK;
+// The passes of a plan on the group's padded rows d_ct, in place, one after
+// the other in the group's bridge workspace (the largest pass's). Timing goes
+// to the "bridge" bucket of the group's first context, one bracket per pass.
+static int grp_bridge_launch(fhe_group* g, u64* d_ct, const std::vector<BridgePass>& passes, hipStream_t st) {
   fhe_ctx* c0 = g->ctxs[0];
-  const fhe_params& p = c0->p;
-  const int big = p.k * p.N, n1 = big + 1, NB = (n1 + KSM_NB_COLS - 1) / KSM_NB_COLS;
-  auto layout = [&](const GrpBridgePass& ps, size_t off[5]) {
-    const size_t S = ps.segs.size();
-    off[0] = up16(8 * S * (3 + BRIDGE_SEG_WORDS));                      // the block table
-    off[1] = off[0] + up16(sizeof(KsGrpBlock) * (size_t)ps.nblk);       // digits
-    off[2] = off[1] + (size_t)ps.ndg * 16 * (size_t)(big * ps.level);   // bodies
-    off[3] = off[2] + up16(8 * (size_t)ps.rows);                        // the compact result
-    off[4] = off[3] + 8 * (size_t)ps.rows * n1;
-  };
+  const int big = c0->p.k * c0->p.N;
   size_t need = 0, off[5];
-  for (const GrpBridgePass& ps : passes) {
-    layout(ps, off);
+  for (const BridgePass& ps : passes) {
+    ps.layout(big, off);
     need = std::max(need, off[4]);
   }
   int rc = reserve(nullptr, g->bridge_ws, need, FHE_E_NOMEM,
                    "group: bridge workspace: out of device memory (fewer rows per call)");
   if (rc) return rc;
-  char* w = (char*)g->bridge_ws.p;
-  for (const GrpBridgePass& ps : passes) {
-    const size_t S = ps.segs.size();
-    layout(ps, off);
-    std::vector<u64> words(S * (3 + BRIDGE_SEG_WORDS));
-    for (size_t s = 0; s < S; ++s) {
-      const BridgeSeg& sg = ps.segs[s];
-      words[s] = (u64)sg.start;
-      words[S + s] = (u64)(s + 1 < S ? ps.segs[s + 1].start : ps.rows);  // segments follow each other unpadded
-      memcpy(&words[2 * S + s * BRIDGE_SEG_WORDS], &sg, sizeof(BridgeSeg));
-      words[(2 + BRIDGE_SEG_WORDS) * S + s] = (u64)(uintptr_t)ps.planes[s];
-    }
-    int64_t* se = (int64_t*)w;
-    BridgeSeg* seg = (BridgeSeg*)(se + 2 * S);
-    const void** keys = (const void**)(se + (2 + BRIDGE_SEG_WORDS) * S);
-    KsGrpBlock* blk = (KsGrpBlock*)(w + off[0]);
-    uint32_t* Dg = (uint32_t*)(w + off[1]);
-    u64* body = (u64*)(w + off[2]);
-    u64* M = (u64*)(w + off[3]);
-    const int KB = big * ps.level / 64;
-    // the single bridge's split rule on the launch's blocks x column blocks
-    const auto [Sk, kslice] = ksm_split(KB, ps.nblk * NB, 512);
-    hipEvent_t e1;
-    prof_begin(c0, c0->prof_bridge, st, &e1);
-    if ((rc = store_words(c0, (u64*)w, words.data(), (int64_t)words.size(), st))) return rc;
-    hipLaunchKernelGGL(k_ks_grp_tables, dim3((unsigned)((ps.nblk + 255) / 256)), dim3(256), 0, st, (const int64_t*)se,
-                       (int)S, ps.nblk, blk);
-    // the digits kernel also zeroes the compact rows the split's atomics add into
-    hipLaunchKernelGGL(k_bridge_digits_hub, dim3((unsigned)(big / 64), (unsigned)(8 * ps.nblk)), dim3(256), 0, st,
-                       (const u64*)d_ct, (const KsGrpBlock*)blk, (const BridgeSeg*)seg, big, ps.beta, ps.level, KB, Dg,
-                       body, Sk > 1 ? n1 : 0, M);
-    c0->prof_bridge.kernel = "k_keyswitch_mfma_grp<8, 1>";
-    hipLaunchKernelGGL((k_keyswitch_mfma_grp<8, 1>), dim3((unsigned)(ps.nblk * NB * Sk)), dim3(256), 0, st,
-                       (const v4i*)Dg, (const v4i* const*)keys, (const KsGrpBlock*)blk, (const u64*)body, n1, NB, KB, 0,
-                       Sk, kslice, M);
-    hipLaunchKernelGGL(k_bridge_scatter_hub, dim3((unsigned)(8 * ps.nblk), (unsigned)((n1 + 255) / 256)), dim3(256),
-                       0, st, (const u64*)M, (const KsGrpBlock*)blk, (const BridgeSeg*)seg, n1, d_ct);
-    prof_end(c0, c0->prof_bridge, st, e1, ps.rows);
-    HIPCHK(c0, hipGetLastError());
-  }
+  for (const BridgePass& ps : passes)
+    if ((rc = bridge_pass_launch(c0, (char*)g->bridge_ws.p, d_ct, ps, st))) return rc;
   return FHE_OK;
 }
 // the row-map rules of one participating tenant (FHE_E_ARG, "tenant t: ...")
@@ -4947,7 +4916,7 @@ int fhe_bridge_group_gens_batch(fhe_group* g, uint64_t* d_ct, const fhe_group_ro
   }
   if ((rc = grp_enter(g))) return rc;
   fhe_group_rows(counts.data(), T, starts.data());
-  std::vector<GrpBridgePass> passes;
+  std::vector<BridgePass> passes;
   if ((rc = grp_bridge_plan(g, rm, starts.data(), &passes))) return rc;
   return grp_bridge_launch(g, d_ct, passes, (hipStream_t)stream);
 }
@@ -4991,7 +4960,7 @@ int fhe_search_seeded_queries_group_gens_batch(fhe_group* g, const fhe_group_cor
       return gfail(rc, "tenant " + std::to_string(t) + ": " + fhe_last_error(g->ctxs[t]));
   }
   const int64_t M = fhe_group_rows(counts.data(), T, starts.data());
-  std::vector<GrpBridgePass> passes;
+  std::vector<BridgePass> passes;
   if ((rc = grp_bridge_plan(g, rm, starts.data(), &passes))) return rc;
   for (int32_t t = 0; t < T; ++t)
     if (items[t].Q && items[t].levels_bit > g->ctxs[t]->pack_key.level)
@@ -5425,7 +5394,7 @@ int fhe_search_ggsws_gens_batch(fhe_ctx* ctx, const fhe_ggsw_gen* gens, int32_t 
   if (!h_T || !d_glwe_acc || !d_glwe_bit) return fail(ctx, FHE_E_ARG, "null search ggsw generations arguments");
   if ((rc = need_eval_keys(ctx))) return rc;
   if ((rc = need_pack_key(ctx))) return rc;
-  if ((rc = gens_ready(ctx, Q, pl.n_old, pl.ends, pl.slots))) return rc;
+  if ((rc = gens_ready(ctx, Q, pl.B, pl.n_old, pl.ends, pl.slots))) return rc;
   if (levels_bit > ctx->pack_key.level)
     return fail(ctx, FHE_E_ARG, "search ggsw generations levels_bit exceeds the packing key's levels");
   hipStream_t st = (hipStream_t)stream;

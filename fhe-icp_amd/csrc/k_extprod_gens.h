@@ -9,7 +9,7 @@
 // and the MFMA kernels of the group form run as they are; what differs is the
 // output: not the group's padded per-tenant segments but ONE query-major
 // Q x B matrix (row q B + off_g + b, off_g the documents before generation g),
-// the layout the grouped bridge (k_bridge_grp.h) takes its row map over.
+// the layout the segmented bridge (k_bridge.h) takes its row map over.
 //
 // A segment is a generation with documents; XqGrpTenant.start holds off_g.
 #pragma once

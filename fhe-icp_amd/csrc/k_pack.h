@@ -5,8 +5,9 @@
 // The inner sums are the i8 MFMA GEMM of the key switch (k_keyswitch_mfma<8, 1>
 // on the packing key's byte planes, k_ksk_to_i8 with R = 0: the key layout
 // [i][l][(k+1)N] is the KSK's with n + 1 = (k+1)N columns); this file holds
-// what differs: digits past 32 bits, the key generation, the negacyclic
-// rotation-and-sum and the packed decryption.
+// what differs: digits past 32 bits (wide_digits_group, the bridge's too),
+// the key generation, the negacyclic rotation-and-sum and the packed
+// decryption.
 // Part of libfheicp (one translation unit: fheicp.hip includes it).
 #pragma once
 
@@ -61,28 +62,34 @@ __global__ void __launch_bounds__(256) k_keygen_pack(ChaKey Km, ChaKey Kn, int N
 
 // k_ks_digits for gadgets up to beta * levels = 48 (the rounded value in 64
 // bits; k_ks_digits keeps it in 32): zero-mean digits of the mask words in
-// A-fragment order [cb][kb][lane][16 B], K level-major. No shift and no body:
-// the rotation adds b_j where X^j puts it, so body[] (the GEMM's last-column
-// term) is zeroed here. The tie coin of digit s (LSB first) is input bit
-// 62 - prec - s, an input bit for every s < levels when prec + levels <= 62.
-// Grid (big / 64, ceil(count / 16)), 256 threads; zero_n1 as in k_ks_digits.
-__global__ void __launch_bounds__(256) k_pack_digits(const u64* __restrict__ in, int64_t count, int big, int beta,
-                                                     int levels, int KB, uint32_t* __restrict__ D,
-                                                     u64* __restrict__ body, int zero_n1, u64* __restrict__ zero_out) {
+// A-fragment order [dg][kb][lane][16 B], K level-major. No shift. The tie coin
+// of digit s (LSB first) is input bit 62 - prec - s, an input bit for every
+// s < levels when prec + levels <= 62.
+// wide_digits_group is one workgroup's work (256 threads, 64 mask words of 16
+// rows; blockIdx.x the word block of big / 64) on one digit group: the compact
+// rows c0 .. min(c0 + 16, end) - 1, digit group dg of D. row(c) is the source
+// row of compact row c (big + 1 words); body[c] (the GEMM's last-column term)
+// takes that row's body when keep_body, else 0. With zero_n1 > 0 the group's
+// rows of zero_out are zeroed as in k_ks_digits, for the split-K atomics.
+// Shared by k_pack_digits and the bridge's digit kernels (k_bridge.h).
+template <typename Row>
+__device__ __forceinline__ void wide_digits_group(int64_t c0, int64_t end, size_t dg, Row&& row, bool keep_body,
+                                                  int big, int beta, int levels, int KB, uint32_t* __restrict__ D,
+                                                  u64* __restrict__ body, int zero_n1, u64* __restrict__ zero_out) {
   const int t = threadIdx.x, cl = t >> 4, iq = t & 15;
-  const int64_t cb = blockIdx.y, c = cb * 16 + cl;
+  const int64_t c = c0 + cl;
   const int i0 = blockIdx.x * 64 + iq * 4;
   if (zero_n1 > 0) {
     const int per = (zero_n1 + (int)gridDim.x - 1) / (int)gridDim.x;
     for (int e = t; e < 16 * per; e += 256) {
       const int q = e / per, col = (int)blockIdx.x * per + (e - q * per);
-      const int64_t cz = cb * 16 + q;
-      if (cz < count && col < zero_n1) zero_out[(size_t)cz * zero_n1 + col] = 0;
+      const int64_t cz = c0 + q;
+      if (cz < end && col < zero_n1) zero_out[(size_t)cz * zero_n1 + col] = 0;
     }
   }
-  if (c >= count) return;
-  const u64* src = in + (size_t)c * (big + 1);
-  if (blockIdx.x == 0 && iq == 0) body[c] = 0;
+  if (c >= end) return;
+  const u64* src = row(c);
+  if (blockIdx.x == 0 && iq == 0) body[c] = keep_body ? src[big] : 0;
   const int prec = levels * beta;
   const u64 half = 1ull << (beta - 1), mask = (1ull << beta) - 1;
   uint32_t packed[8];
@@ -108,8 +115,17 @@ __global__ void __launch_bounds__(256) k_pack_digits(const u64* __restrict__ in,
   for (int s = 0; s < 8; ++s) {
     if (s >= levels) break;
     const int kb = (levels - 1 - s) * kbl + kbi;
-    D[(((size_t)cb * KB + kb) * 64 + lane) * 4 + ((i0 & 15) >> 2)] = packed[s];
+    D[((dg * KB + kb) * 64 + lane) * 4 + ((i0 & 15) >> 2)] = packed[s];
   }
+}
+// The packing's digits: row c of `in` as it stands and no body (the rotation
+// adds b_j where X^j puts it). Grid (big / 64, ceil(count / 16)), 256 threads.
+__global__ void __launch_bounds__(256) k_pack_digits(const u64* __restrict__ in, int64_t count, int big, int beta,
+                                                     int levels, int KB, uint32_t* __restrict__ D,
+                                                     u64* __restrict__ body, int zero_n1, u64* __restrict__ zero_out) {
+  wide_digits_group((int64_t)blockIdx.y * 16, count, blockIdx.y,
+                    [&](int64_t c) { return in + (size_t)c * (big + 1); }, false, big, beta, levels, KB, D, body,
+                    zero_n1, zero_out);
 }
 
 // out[g][c][t] += sum_j +-M[gN + j][c][(t - j) mod N] (minus when t < j: X^N =

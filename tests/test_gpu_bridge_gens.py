@@ -186,6 +186,35 @@ def test_one_generation_in_slot_0_is_the_row_map_bridge(need_gpu, Qn, B, B_old):
     eng.close()
 
 
+def test_context_entry_is_the_group_entry_of_one_tenant(toy8):
+    """fhe_bridge_gens_batch on a context and fhe_bridge_group_gens_batch on a
+    group of that one context (its rows start at row 0 of the padded buffer):
+    the same eight keys, (Q, B, ends) = (2, 300, [129, 150, 290]); equal words
+    on all Q B rows, the row after them untouched. The context has evaluation
+    keys of its own: a group admits no other."""
+    from fheicp.engine import EngineGroup
+    _, keys = toy8
+    eng = Engine(TOY, 0)
+    eng.keygen(311)
+    for g, bk in enumerate(keys):
+        eng.import_bridge_key(BETA, LV, bk, slot=PERM8[g])
+    grp = EngineGroup([eng])
+    try:
+        Qn, B, ends = 2, 300, [129, 150, 290]
+        ct = canaried(np.random.default_rng(23), eng, Qn, B, ends)
+        a, b = dev_u64(eng, ct), dev_u64(eng, ct)
+        eng.bridge_gens(a, Qn, B, ends, PERM8[:3])
+        grp.bridge_gens(b, [(Qn, B, ends, PERM8[:3])])
+        ga, gb = host_u64(a), host_u64(b)
+        np.testing.assert_array_equal(ga[:Qn * B], gb[:Qn * B])
+        bridged = np.concatenate(segment_rows(Qn, B, ends))
+        assert not np.array_equal(ga[bridged], ct[bridged])             # and the bridge did something
+        assert (ga[Qn * B] == U(CANARY)).all() and (gb[Qn * B] == U(CANARY)).all()
+    finally:
+        grp.close()
+        eng.close()
+
+
 # ------------------------------------------------------------- slot keys --
 def test_slot_keygen_export_import_drop(need_gpu):
     eng = Engine(TOY, 0)
