@@ -20,6 +20,8 @@
 //                     digits, Toeplitz byte planes, slot extraction
 //   k_extprod_q.h     both-private search, Q queries in one pass: reversed
 //                     document digits, GGSW byte planes, the transposed i8 GEMM
+//   k_extprod_grp.h   the same over the segments of a call (the tenants of a
+//                     group, the key generations of a context): one table kernel
 //   k_private_seeded.h  both-private search on seeded documents and queries
 //   k_seeded_keys.h   seeded evaluation keys: LWE-row expansion, body gather
 //   k_blind_rotate.h  blind rotation (external products over an f64 wave FFT):
@@ -52,12 +54,11 @@
 #include "k_private_seeded.h"
 #include "k_seeded_keys.h"
 #include "k_blind_rotate.h"
-#include "k_extprod_grp.h"
 #ifndef FHEICP_GRP_XGENS
 #define FHEICP_GRP_XGENS 1  // 0: one fhe_linear_ggsws_batch per generation and a scatter behind the same entries
                             // (A/B builds, tools/build_variant.sh NAME -DFHEICP_GRP_XGENS=0)
 #endif
-#include "k_extprod_gens.h"
+#include "k_extprod_grp.h"
 
 // ============================================================ host =========
 struct ProfAcc {
@@ -531,6 +532,25 @@ static bool ksm_dispatch(int planes, int CB, F&& f) {
 // rocprofv3's name of an instantiation, for a profile bucket: "base<Q, C>"
 static std::string ksm_name(const char* base, int Q, int C) {
   return std::string(base) + "<" + std::to_string(Q) + ", " + std::to_string(C) + ">";
+}
+// The transposed external product's K split (k_extprod_q.h, k_extprod_grp.h)
+// over workgroups, towards ~XQ_WGS of them on the launch's `tiles` (column
+// workgroups x row-tile groups), slices of 4 k-blocks at least.
+#ifndef FHEICP_XQ_WGS
+#define FHEICP_XQ_WGS 512  // A/B builds (tools/build_variant.sh): other targets
+#endif
+static KsmSplit xq_ksplit(int KB, int64_t tiles) {
+  const int S = (int)std::max<int64_t>(1, std::min<int64_t>(KB / 4, FHEICP_XQ_WGS / std::max<int64_t>(1, tiles)));
+  const int kslice = (KB + S - 1) / S;
+  return {(KB + kslice - 1) / kslice, kslice};
+}
+// Its GEMMs' row tiles per workgroup, RT = 1 or 2: f(RT) with RT as a compile-time constant.
+template <class F>
+static void xq_dispatch(int RT, F&& f) {
+  if (RT == 2)
+    f(std::integral_constant<int, 2>{});
+  else
+    f(std::integral_constant<int, 1>{});
 }
 
 extern "C" {
@@ -3465,14 +3485,7 @@ static int linear_ggsws_impl(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t L, co
   u64* M = (u64*)((char*)ctx->xp_ws.p + pbytes);
   u64* d_cst = M + (size_t)Q * G * n1;
   if ((rc = store_scaled_csts(ctx, d_cst, Q, h_cst, cst, h_T, st))) return rc;
-  // K split over workgroups towards ~XQ_WGS of them, slices of 4 k-blocks at least
-#ifndef FHEICP_XQ_WGS
-#define FHEICP_XQ_WGS 512  // A/B builds (tools/build_variant.sh): other targets
-#endif
-  int Sk = (int)std::max<int64_t>(
-      1, std::min<int64_t>(KB / 4, FHEICP_XQ_WGS / std::max<int64_t>(1, cgrid * rgrid)));
-  const int kslice = (KB + Sk - 1) / Sk;
-  Sk = (KB + kslice - 1) / kslice;
+  const auto [Sk, kslice] = xq_ksplit(KB, cgrid * rgrid);
   hipEvent_t e1;
   prof_begin(ctx, ctx->prof_xq, st, &e1);
   ctx->prof_xq.kernel = RT == 2 ? "k_extprod_queries_mfma<2>" : "k_extprod_queries_mfma<1>";
@@ -3480,12 +3493,10 @@ static int linear_ggsws_impl(fhe_ctx* ctx, const uint64_t* d_ggsw, int32_t L, co
   hipLaunchKernelGGL(k_ggsws_planes, dim3((unsigned)KB, (unsigned)rtp), dim3(64), 0, st, d_ggsw, p.N, p.k, (int)L,
                      (int)Q, P8);
   const dim3 grid((unsigned)cgrid, (unsigned)rgrid, (unsigned)Sk);
-  if (RT == 2)
-    hipLaunchKernelGGL(k_extprod_queries_mfma<2>, grid, dim3(256), 0, st, (const v4i*)P8, (const uint8_t*)d_docs, p.N,
-                       p.k, (int)L, (int)Q, (int)G, KB, kslice, M);
-  else
-    hipLaunchKernelGGL(k_extprod_queries_mfma<1>, grid, dim3(256), 0, st, (const v4i*)P8, (const uint8_t*)d_docs, p.N,
-                       p.k, (int)L, (int)Q, (int)G, KB, kslice, M);
+  xq_dispatch(RT, [&, kslice = kslice](auto rt) {
+    hipLaunchKernelGGL(k_extprod_queries_mfma<decltype(rt)::value>, grid, dim3(256), 0, st, (const v4i*)P8,
+                       (const uint8_t*)d_docs, p.N, p.k, (int)L, (int)Q, (int)G, KB, kslice, M);
+  });
   hipLaunchKernelGGL(k_extprod_extract_queries, dim3((unsigned)B, (unsigned)((p.k * p.N + 256) / 256), (unsigned)Q),
                      dim3(256), 0, st, M, S, (int)D, p.N, p.k, G, B, d_cst, d_out);
   prof_end(ctx, ctx->prof_xq, st, e1, Q * B);
@@ -5008,18 +5019,116 @@ int fhe_search_seeded_queries_group_gens_batch(fhe_group* g, const fhe_group_cor
   return FHE_OK;
 }
 
+// ---- the segmented transposed external product (k_extprod_grp.h) ----------
+// What one call's leveled step launches over its segments (the participating
+// tenants of a group, §8.14; the generations with documents of a context,
+// §8.19): the records, the launch's RT, tile and row-tile counts, the K split
+// and the layout of its workspace (tables | constants | planes | results, each
+// 16-aligned). RT and L are set before the first add().
+struct XqWs {
+  XqGrpTenant* ten;
+  XqGrpTile* tiles;
+  int32_t *rtt, *qdt;  // row tile -> segment, row quad -> segment
+  int64_t* ends;
+  u64* cst;
+  v4i* P8;
+  u64* M;
+};
+struct XqPlan {
+  int ns = 0, RT = 1, L = 0, KB = 0, Sk = 1, kslice = 0;
+  int64_t ntiles = 0, nrt = 0, mwords = 0, nquads = 0;
+  bool with_ends = false;
+  XqSegs<XQ_GRP_MAX> seg;
+  size_t off_tiles = 0, off_rt = 0, off_quad = 0, off_ends = 0, off_cst = 0, off_planes = 0, off_M = 0, bytes = 0;
+  // Q queries (GGSWs at d_ggsw, their constants from c0 on) against the B packed documents at
+  // d_docs, D features each; `start`: where the form's extraction puts the segment
+  void add(const fhe_params& p, const uint64_t* d_ggsw, const void* d_docs, int64_t start, int64_t Q, int64_t B,
+           int32_t D, int64_t c0) {
+    const int64_t G = ggsw_glwes(p, B, D), rtp = xq_grp_rtiles(p.k, (int)Q, RT);
+    seg.v[ns++] = {d_ggsw, (const uint8_t*)d_docs, start, mwords, (int32_t)Q, (int32_t)G, (int32_t)B, D, (int32_t)nrt,
+                   (int32_t)c0};
+    ntiles += xq_grp_cgrid(p.N, (int)G) * (rtp / RT);
+    nrt += rtp;
+    mwords += Q * G * (p.k + 1) * p.N;
+  }
+  // The split and the layout, for `quads` row quads of a padded output (0: none), an ends table
+  // or none, and ncst constants. False when the launch has 2^31 tiles or (row tile, k-block)
+  // pairs and more: the tiles are the GEMM's grid x, the pairs the planes'.
+  bool finish(const fhe_params& p, int64_t quads, bool ends, int64_t ncst) {
+    const int n1 = (p.k + 1) * p.N;
+    KB = n1 * L / 64;
+    if (ntiles > 0x7fffffffLL || nrt * KB > 0x7fffffffLL) return false;
+    const auto [S, ks] = xq_ksplit(KB, ntiles);
+    Sk = S, kslice = ks, nquads = quads, with_ends = ends;
+    off_tiles = up16(sizeof(XqGrpTenant) * (size_t)ns);
+    off_rt = off_tiles + sizeof(XqGrpTile) * (size_t)ntiles;
+    off_quad = off_rt + up16(4 * (size_t)nrt);
+    off_ends = off_quad + up16(4 * (size_t)nquads);
+    off_cst = off_ends + (ends ? up16(8 * (size_t)ns) : 0);
+    // the planes' 1 KB fragment runs and the results' 128-byte store runs on whole cache lines
+    off_planes = (off_cst + 8 * (size_t)ncst + 255) / 256 * 256;
+    off_M = off_planes + (size_t)nrt * 16 * n1 * L * 8;
+    bytes = off_M + 8 * (size_t)mwords;
+    return true;
+  }
+  XqWs at(void* ws) const {
+    char* w = (char*)ws;
+    return {(XqGrpTenant*)w,         (XqGrpTile*)(w + off_tiles),
+            (int32_t*)(w + off_rt),  nquads ? (int32_t*)(w + off_quad) : nullptr,
+            with_ends ? (int64_t*)(w + off_ends) : nullptr,
+            (u64*)(w + off_cst),     (v4i*)(w + off_planes),
+            (u64*)(w + off_M)};
+  }
+};
+// The leveled step of every segment in the pl.bytes at `ws` the caller
+// reserved, its constants already queued to at(ws).cst: in one bracket of
+// ctx's "linear_ggsws" bucket (items = the call's results) the tables, the
+// memset of a split K, the planes, the GEMM and the form's extraction,
+// extract(at(ws)). The launch count does not depend on the segments.
+extern "C++" {
+template <class Extract>
+static int xq_launch(fhe_ctx* ctx, const XqPlan& pl, void* ws, int64_t items, Extract&& extract, hipStream_t st) {
+  const fhe_params& p = ctx->p;
+  const XqWs w = pl.at(ws);
+  hipEvent_t e1;
+  prof_begin(ctx, ctx->prof_xq, st, &e1);
+  ctx->prof_xq.kernel = pl.RT == 2 ? "k_extprod_queries_mfma_grp<2>" : "k_extprod_queries_mfma_grp<1>";
+  const int64_t nth = std::max(std::max(pl.ntiles, pl.nrt), std::max<int64_t>(pl.nquads, pl.ns));
+  auto tables = [&](const auto& segs) {
+    hipLaunchKernelGGL(k_xq_tables, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, st, segs, pl.ns, p.N, p.k,
+                       pl.RT, pl.ntiles, pl.nrt, pl.nquads, w.ten, w.tiles, w.rtt, w.qdt, w.ends);
+  };
+  if (pl.ns <= XQ_GENS_MAX) {  // the short argument: every generations call, and a group call of few tenants
+    XqSegs<XQ_GENS_MAX> few;
+    std::copy(pl.seg.v, pl.seg.v + XQ_GENS_MAX, few.v);
+    tables(few);
+  } else {
+    tables(pl.seg);
+  }
+  if (pl.Sk > 1) HIPCHK(ctx, hipMemsetAsync(w.M, 0, 8 * (size_t)pl.mwords, st));
+  hipLaunchKernelGGL(k_ggsws_planes_grp, dim3((unsigned)(pl.nrt * pl.KB)), dim3(64), 0, st,
+                     (const XqGrpTenant*)w.ten, (const int32_t*)w.rtt, p.N, p.k, pl.L, pl.KB, w.P8);
+  xq_dispatch(pl.RT, [&](auto rt) {
+    hipLaunchKernelGGL(k_extprod_queries_mfma_grp<decltype(rt)::value>, dim3((unsigned)pl.ntiles, 1, (unsigned)pl.Sk),
+                       dim3(256), 0, st, (const XqGrpTile*)w.tiles, (const XqGrpTenant*)w.ten, (const v4i*)w.P8, p.N,
+                       p.k, pl.L, pl.KB, pl.kslice, w.M);
+  });
+  extract(w);
+  prof_end(ctx, ctx->prof_xq, st, e1, items);
+  HIPCHK(ctx, hipGetLastError());
+  return FHE_OK;
+}
+}  // extern "C++"
+
 // ---- both-private search for a group ---------------------
-// What one call's leveled step launches, from the participating tenants'
-// shapes: the records, the launch's RT, tile, row-tile and row counts, the K
-// split and the layout of its part of the group workspace (tables | constants
-// | planes | results, each 16-aligned).
+// The group's part of a call's plan: the segments are the participating
+// tenants (record -> tenant), with their result counts and their starts in
+// the padded layout of M rows.
 struct XqGrpPlan {
-  int nt = 0, RT = 1, L = 0, KB = 0, Sk = 1, kslice = 0;
-  int64_t ntiles = 0, nrt = 0, M = 0, nq = 0, mwords = 0, total = 0;
-  XqGrpTenants rec;
+  XqPlan x;
+  int64_t M = 0, total = 0;
   int32_t tenant[XQ_GRP_MAX];  // record -> tenant of the group
   std::vector<int64_t> counts, starts;
-  size_t off_tiles = 0, off_rt = 0, off_quad = 0, off_cst = 0, off_planes = 0, off_M = 0, bytes = 0;
 };
 // The argument checks of both entries (FHE_E_ARG, "tenant t: ...", host-only
 // contexts report them too) and the plan. `search`: the thresholds, levels_bit
@@ -5028,6 +5137,7 @@ static int xq_grp_plan(fhe_group* g, const fhe_group_ggsw* items, int32_t T, con
                        XqGrpPlan* pl) {
   pl->counts.assign((size_t)T, 0);
   pl->starts.assign((size_t)T, 0);
+  int nt = 0;
   for (int32_t t = 0; t < T; ++t) {
     const fhe_group_ggsw& it = items[t];
     fhe_ctx* ctx = g->ctxs[t];
@@ -5045,90 +5155,49 @@ static int xq_grp_plan(fhe_group* g, const fhe_group_ggsw* items, int32_t T, con
     } else if (!h_cst[t]) {
       return gfail(FHE_E_ARG, who + "null constants");
     }
-    if (pl->nt && it.level != pl->L)
+    if (nt && it.level != pl->x.L)
       return gfail(FHE_E_ARG, who + "gadget level " + std::to_string(it.level) + " differs from the first participating "
-                                  "tenant's " + std::to_string(pl->L) + ": one level per call");
-    pl->L = it.level;
+                                  "tenant's " + std::to_string(pl->x.L) + ": one level per call");
+    pl->x.L = it.level;
     pl->counts[t] = it.Q * it.B;
     pl->total += pl->counts[t];
     if (pl->total >= ((int64_t)1 << 31)) return gfail(FHE_E_ARG, "2^31 results and more: split the call");
-    pl->tenant[pl->nt++] = t;
+    pl->tenant[nt++] = t;
   }
   pl->M = fhe_group_rows(pl->counts.data(), T, pl->starts.data());
-  if (!pl->nt) return FHE_OK;
+  if (!nt) return FHE_OK;
   const fhe_params& p = g->ctxs[0]->p;  // the contexts' parameters are equal (grp_check_params, before any launch)
-  const int n1 = (p.k + 1) * p.N;
-  pl->KB = n1 * pl->L / 64;
-  for (int i = 0; i < pl->nt; ++i)
-    if (items[pl->tenant[i]].Q * (p.k + 1) > 16) pl->RT = 2;
-  for (int i = 0; i < pl->nt; ++i) {
+  for (int i = 0; i < nt; ++i)
+    if (items[pl->tenant[i]].Q * (p.k + 1) > 16) pl->x.RT = 2;
+  int64_t nq = 0;
+  for (int i = 0; i < nt; ++i) {
     const int32_t t = pl->tenant[i];
     const fhe_group_ggsw& it = items[t];
-    XqGrpTenant& r = pl->rec.v[i];
-    const int64_t G = ggsw_glwes(p, it.B, it.D), rtp = xq_grp_rtiles(p.k, (int)it.Q, pl->RT);
-    r = {it.d_ggsw, (const uint8_t*)it.d_docs, pl->starts[t], pl->mwords, (int32_t)it.Q, (int32_t)G, (int32_t)it.B,
-         it.D, (int32_t)pl->nrt, (int32_t)pl->nq};
-    pl->ntiles += xq_grp_cgrid(p.N, (int)G) * (rtp / pl->RT);
-    pl->nrt += rtp;
-    pl->nq += it.Q;
-    pl->mwords += it.Q * G * n1;
+    pl->x.add(p, it.d_ggsw, it.d_docs, pl->starts[t], it.Q, it.B, it.D, nq);
+    nq += it.Q;
   }
-  // the tiles are the GEMM's grid x, (row tile, k-block) the planes'
-  if (pl->ntiles > 0x7fffffffLL || pl->nrt * pl->KB > 0x7fffffffLL)
+  if (!pl->x.finish(p, pl->M / 4, false, nq))
     return gfail(FHE_E_ARG, "ggsw queries batch too large (2^31 tiles over all tenants): split the call");
-  // linear_ggsws_impl's K split on the launch's total of tiles
-  pl->Sk = (int)std::max<int64_t>(1, std::min<int64_t>(pl->KB / 4, FHEICP_XQ_WGS / std::max<int64_t>(1, pl->ntiles)));
-  pl->kslice = (pl->KB + pl->Sk - 1) / pl->Sk;
-  pl->Sk = (pl->KB + pl->kslice - 1) / pl->kslice;
-  pl->off_tiles = up16(sizeof(XqGrpTenant) * (size_t)pl->nt);
-  pl->off_rt = pl->off_tiles + sizeof(XqGrpTile) * (size_t)pl->ntiles;
-  pl->off_quad = pl->off_rt + up16(4 * (size_t)pl->nrt);
-  pl->off_cst = pl->off_quad + up16((size_t)pl->M);  // 4 bytes per row quad
-  pl->off_planes = pl->off_cst + up16(8 * (size_t)pl->nq);
-  pl->off_M = pl->off_planes + (size_t)pl->nrt * 16 * n1 * pl->L * 8;
-  pl->bytes = pl->off_M + 8 * (size_t)pl->mwords;
   return FHE_OK;
 }
-// The leveled step of every participating tenant at `ws` (pl->bytes of the
-// group workspace): the constants, then in one bracket the tables, the memset
-// of a split K, the planes, the GEMM and the extraction into the padded rows of
-// d_out (and d_cpy, when given). The launch count does not depend on T.
-// Timing goes to tenant 0's "linear_ggsws" bucket.
+// The leveled step of every participating tenant at `ws` (pl.x.bytes of the
+// group workspace): the constants cs, then xq_launch with the extraction into
+// the padded rows of d_out (and d_cpy, when given). Timing goes to tenant 0's
+// "linear_ggsws" bucket.
 static int xq_grp_launch(fhe_group* g, const XqGrpPlan& pl, const std::vector<u64>& cs, void* ws, u64* d_out,
                          u64* d_cpy, hipStream_t st) {
   fhe_ctx* c0 = g->ctxs[0];
   const fhe_params& p = c0->p;
-  XqGrpTenant* ten = (XqGrpTenant*)ws;
-  XqGrpTile* tiles = (XqGrpTile*)((char*)ws + pl.off_tiles);
-  int32_t* rtt = (int32_t*)((char*)ws + pl.off_rt);
-  int32_t* qdt = (int32_t*)((char*)ws + pl.off_quad);
-  u64* d_cst = (u64*)((char*)ws + pl.off_cst);
-  v4i* P8 = (v4i*)((char*)ws + pl.off_planes);
-  u64* Mall = (u64*)((char*)ws + pl.off_M);
-  int rc = store_words(c0, d_cst, cs.data(), pl.nq, st);
+  int rc = store_words(c0, pl.x.at(ws).cst, cs.data(), (int64_t)cs.size(), st);
   if (rc) return rc;
-  hipEvent_t e1;
-  prof_begin(c0, c0->prof_xq, st, &e1);
-  c0->prof_xq.kernel = pl.RT == 2 ? "k_extprod_queries_mfma_grp<2>" : "k_extprod_queries_mfma_grp<1>";
-  const int64_t nquads = pl.M / 4, nth = std::max(std::max(pl.ntiles, pl.nrt), std::max<int64_t>(nquads, pl.nt));
-  hipLaunchKernelGGL(k_xq_grp_tables, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, st, pl.rec, pl.nt, p.N, p.k,
-                     pl.RT, pl.ntiles, pl.nrt, nquads, ten, tiles, rtt, qdt);
-  if (pl.Sk > 1) HIPCHK(c0, hipMemsetAsync(Mall, 0, 8 * (size_t)pl.mwords, st));
-  hipLaunchKernelGGL(k_ggsws_planes_grp, dim3((unsigned)(pl.nrt * pl.KB)), dim3(64), 0, st,
-                     (const XqGrpTenant*)ten, (const int32_t*)rtt, p.N, p.k, pl.L, pl.KB, P8);
-  const dim3 grid((unsigned)pl.ntiles, 1, (unsigned)pl.Sk);
-  if (pl.RT == 2)
-    hipLaunchKernelGGL(k_extprod_queries_mfma_grp<2>, grid, dim3(256), 0, st, (const XqGrpTile*)tiles,
-                       (const XqGrpTenant*)ten, (const v4i*)P8, p.N, p.k, pl.L, pl.KB, pl.kslice, Mall);
-  else
-    hipLaunchKernelGGL(k_extprod_queries_mfma_grp<1>, grid, dim3(256), 0, st, (const XqGrpTile*)tiles,
-                       (const XqGrpTenant*)ten, (const v4i*)P8, p.N, p.k, pl.L, pl.KB, pl.kslice, Mall);
-  hipLaunchKernelGGL(k_extprod_extract_grp, dim3((unsigned)pl.M, (unsigned)((p.k * p.N + 256) / 256)), dim3(256), 0, st,
-                     (const u64*)Mall, (const XqGrpTenant*)ten, (const int32_t*)qdt, p.N, p.k, (const u64*)d_cst, d_out,
-                     d_cpy);
-  prof_end(c0, c0->prof_xq, st, e1, pl.total);
-  HIPCHK(c0, hipGetLastError());
-  return FHE_OK;
+  return xq_launch(
+      c0, pl.x, ws, pl.total,
+      [&](const XqWs& w) {
+        hipLaunchKernelGGL(k_extprod_extract_grp, dim3((unsigned)pl.M, (unsigned)((p.k * p.N + 256) / 256)), dim3(256),
+                           0, st, (const u64*)w.M, (const XqGrpTenant*)w.ten, (const int32_t*)w.qdt, p.N, p.k,
+                           (const u64*)w.cst, d_out, d_cpy);
+      },
+      st);
 }
 
 int fhe_linear_ggsws_group_batch(fhe_group* g, const fhe_group_ggsw* items, int32_t T, const int64_t* const* h_cst,
@@ -5142,12 +5211,12 @@ int fhe_linear_ggsws_group_batch(fhe_group* g, const fhe_group_ggsw* items, int3
   if ((rc = grp_check_params(g))) return rc;
   if (g->device < 0) return gfail(FHE_E_DEVICE, "host-only contexts");
   if (hipSetDevice(g->device) != hipSuccess) return gfail(FHE_E_DEVICE, "hipSetDevice failed");
-  if (!pl.nt) return FHE_OK;
+  if (!pl.x.ns) return FHE_OK;
   if (!d_out) return gfail(FHE_E_ARG, "null output rows");
-  if ((rc = grp_ensure_ws(g, pl.bytes))) return rc;
+  if ((rc = grp_ensure_ws(g, pl.x.bytes))) return rc;
   const int sh = 64 - g->ctxs[0]->p.msg_bits;
   std::vector<u64> cs;
-  for (int i = 0; i < pl.nt; ++i)
+  for (int i = 0; i < pl.x.ns; ++i)
     for (int64_t q = 0; q < items[pl.tenant[i]].Q; ++q) cs.push_back((u64)h_cst[pl.tenant[i]][q] << sh);
   return xq_grp_launch(g, pl, cs, g->ws.p, d_out, nullptr, (hipStream_t)stream);
 }
@@ -5159,28 +5228,28 @@ int fhe_search_ggsws_group_batch(fhe_group* g, const fhe_group_ggsw* items, int3
   int rc = xq_grp_plan(g, items, T, nullptr, true, &pl);  // argument errors first
   if (rc) return rc;
   if ((rc = grp_enter(g))) return rc;
-  for (int i = 0; i < pl.nt; ++i) {
+  for (int i = 0; i < pl.x.ns; ++i) {
     const int32_t t = pl.tenant[i];
     const std::string who = "tenant " + std::to_string(t) + ": ";
     if ((rc = need_pack_key(g->ctxs[t]))) return gfail(rc, who + fhe_last_error(g->ctxs[t]));
     if (items[t].levels_bit > g->ctxs[t]->pack_key.level)
       return gfail(FHE_E_ARG, who + "levels_bit exceeds the packing key's levels");
   }
-  if (!pl.nt) return FHE_OK;
+  if (!pl.x.ns) return FHE_OK;
   if ((rc = grp_ks_fits(g, pl.counts.data()))) return rc;
   hipStream_t st = (hipStream_t)stream;
   const fhe_params& p = g->ctxs[0]->p;
   const int64_t M = pl.M;
   const size_t Wb = fhe_big_lwe_words(&p), Ws = fhe_small_lwe_words(&p), tb = grp_table_bytes((size_t)T, M);
   const size_t rows = up16(8 * (size_t)M * (3 * Wb + Ws));
-  if ((rc = grp_ensure_ws(g, tb + rows + pl.bytes))) return rc;
+  if ((rc = grp_ensure_ws(g, tb + rows + pl.x.bytes))) return rc;
   u64* small = (u64*)((char*)g->ws.p + tb);
   u64* ctv = small + (size_t)M * Ws;
   u64* sgn = ctv + (size_t)M * Wb;
   u64* cpy = sgn + (size_t)M * Wb;
   const int sh = 64 - p.msg_bits;
   std::vector<u64> cs;
-  for (int i = 0; i < pl.nt; ++i) {
+  for (int i = 0; i < pl.x.ns; ++i) {
     const fhe_group_ggsw& it = items[pl.tenant[i]];
     for (int64_t q = 0; q < it.Q; ++q) cs.push_back((u64)(it.cst - it.h_T[q]) << sh);
   }
@@ -5189,7 +5258,7 @@ int fhe_search_ggsws_group_batch(fhe_group* g, const fhe_group_ggsw* items, int3
   if ((rc = xq_grp_launch(g, pl, cs, (char*)g->ws.p + tb + rows, ctv, cpy, st))) return rc;
   if ((rc = grp_sign(g, ctv, pl.counts.data(), pl.starts.data(), M, sgn, small, g->ws.p, st))) return rc;
   // tenant t's two packings with its own key, as fhe_search_ggsws_batch
-  for (int i = 0; i < pl.nt; ++i) {
+  for (int i = 0; i < pl.x.ns; ++i) {
     const int32_t t = pl.tenant[i];
     const fhe_group_ggsw& it = items[t];
     fhe_ctx* ctx = g->ctxs[t];
@@ -5205,21 +5274,19 @@ int fhe_search_ggsws_group_batch(fhe_group* g, const fhe_group_ggsw* items, int3
 }  // extern "C"
 
 // ---- both-private key rotation: per-generation GGSW queries
-// What one call's leveled step launches, from the generations' shapes: the
-// segments (generations with documents), the launch's RT, tile and row-tile
-// counts, the K split, and the layout of xp_ws:
-//   planes | results | constants   (fhe_ggsws_gens_ws_bytes)
-//   | the records | the tile table | the row-tile table | the ends table.
+// The generations' part of a call's plan: the segments are the generations
+// with documents (segment -> generation), each from its first document off_g
+// of the call's B; and the bridge's row map over the old ones. The workspace
+// is xp_ws: XqPlan's layout, whose planes, results and constants are what
+// fhe_ggsws_gens_ws_bytes counts.
 struct XqGensPlan {
-  int ns = 0, RT = 1, KB = 0, Sk = 1, kslice = 0;
-  int64_t B = 0, rtp = 0, ntiles = 0, nrt = 0, mwords = 0;
-  XqGensSegs seg;
+  XqPlan x;
+  int64_t B = 0;
   int32_t gen[XQ_GENS_MAX];  // segment -> generation of the call
   int64_t off[XQ_GENS_MAX];  // generation -> its first document of the call
   int32_t n_old = 0;         // the bridge's row map: the generations before a slot -1 entry
   int64_t ends[XQ_GENS_MAX];
   int32_t slots[XQ_GENS_MAX];
-  size_t off_M = 0, off_cst = 0, off_ten = 0, off_tiles = 0, off_rt = 0, off_ends = 0, bytes = 0;
 };
 // The argument checks of both entries (FHE_E_ARG, host-only contexts report
 // them too) and the plan.
@@ -5259,39 +5326,21 @@ static int xq_gens_plan(fhe_ctx* ctx, const fhe_ggsw_gen* gens, int32_t G, int32
   int rc = ggsws_args(ctx, Q, B, D, base_log, L);
   if (rc) return rc;
   const fhe_params& p = ctx->p;
-  const int n1 = (p.k + 1) * p.N;
   pl->B = B;
-  pl->KB = n1 * L / 64;
-  pl->rtp = ggsws_row_tiles(p, Q, &pl->RT);
+  pl->x.L = L;
+  const int64_t rtp = ggsws_row_tiles(p, Q, &pl->x.RT);
   for (int g = 0; g < G; ++g) {
     const fhe_ggsw_gen& it = gens[g];
     if (it.B == 0) continue;
-    const int64_t Gg = ggsw_glwes(p, it.B, D);
-    pl->seg.v[pl->ns] = {it.d_ggsw, (const uint8_t*)it.d_docs, pl->off[g], pl->mwords, (int32_t)Q, (int32_t)Gg,
-                         (int32_t)it.B, D, (int32_t)pl->nrt, 0};
-    pl->gen[pl->ns++] = g;
-    pl->ntiles += xq_grp_cgrid(p.N, (int)Gg) * (pl->rtp / pl->RT);
-    pl->nrt += pl->rtp;
-    pl->mwords += Q * Gg * n1;
+    pl->gen[pl->x.ns] = g;
+    pl->x.add(p, it.d_ggsw, it.d_docs, pl->off[g], Q, it.B, D, 0);  // one set of Q constants for all
   }
-  // the tiles are the GEMM's grid x, (row tile, k-block) the planes'
-  if (pl->ntiles > 0x7fffffffLL || pl->nrt * pl->KB > 0x7fffffffLL)
+  if (!pl->x.finish(p, 0, true, Q))
     return fail(ctx, FHE_E_ARG, "ggsw queries batch too large (2^31 tiles over all generations): split the call");
   if (!FHEICP_GRP_XGENS)
-    for (int i = 0; i < pl->ns; ++i)
-      if (pl->seg.v[i].G > 65535 || pl->rtp / pl->RT > 65535)
+    for (int i = 0; i < pl->x.ns; ++i)
+      if (pl->x.seg.v[i].G > 65535 || rtp / pl->x.RT > 65535)
         return fail(ctx, FHE_E_ARG, "ggsw queries batch too large: split the call");
-  // linear_ggsws_impl's K split on the launch's total of tiles
-  pl->Sk = (int)std::max<int64_t>(1, std::min<int64_t>(pl->KB / 4, FHEICP_XQ_WGS / std::max<int64_t>(1, pl->ntiles)));
-  pl->kslice = (pl->KB + pl->Sk - 1) / pl->Sk;
-  pl->Sk = (pl->KB + pl->kslice - 1) / pl->kslice;
-  pl->off_M = (size_t)pl->nrt * 16 * n1 * L * 8;
-  pl->off_cst = pl->off_M + 8 * (size_t)pl->mwords;
-  pl->off_ten = up16(pl->off_cst + 8 * (size_t)Q);
-  pl->off_tiles = pl->off_ten + up16(sizeof(XqGrpTenant) * (size_t)pl->ns);
-  pl->off_rt = pl->off_tiles + sizeof(XqGrpTile) * (size_t)pl->ntiles;
-  pl->off_ends = pl->off_rt + up16(4 * (size_t)pl->nrt);
-  pl->bytes = pl->off_ends + 8 * (size_t)pl->ns;
   return FHE_OK;
 }
 size_t fhe_ggsws_gens_ws_bytes(const fhe_params* p, int64_t Q, const int64_t* h_B, int32_t G, int32_t D,
@@ -5307,29 +5356,28 @@ size_t fhe_ggsws_gens_ws_bytes(const fhe_params* p, int64_t Q, const int64_t* h_
 }
 // The leveled step of every generation into d_out (Q B x (kN+1), query-major,
 // generation g's documents from off_g on), h_cst[q] (or cst - h_T[q]) on query
-// q's bodies: the constants, then in one bracket the tables, the memset of a
-// split K, the planes, the GEMM and the extraction. The launch count does not
-// depend on G.
+// q's bodies: the constants, then xq_launch with the extraction by the ends
+// table.
 static int linear_ggsws_gens_impl(fhe_ctx* ctx, const fhe_ggsw_gen* gens, const XqGensPlan& pl, int32_t L, int64_t Q,
                                   int32_t D, const int64_t* h_cst, int64_t cst, const int64_t* h_T, uint64_t* d_out,
                                   hipStream_t st) {
   const fhe_params& p = ctx->p;
-  const int n1 = p.k * p.N + 1;
   int rc;
 #if !FHEICP_GRP_XGENS
   {
     // the loop form: every generation through the single-key step into a compact buffer behind
     // the largest generation's own workspace, then scattered to its rows
+    const int n1 = p.k * p.N + 1;
     size_t need = 0, rows = 0;
-    for (int i = 0; i < pl.ns; ++i) {
-      need = std::max(need, up16(fhe_ggsws_ws_bytes(&p, Q, pl.seg.v[i].B, D, L)));
-      rows = std::max(rows, (size_t)Q * (size_t)pl.seg.v[i].B);
+    for (int i = 0; i < pl.x.ns; ++i) {
+      need = std::max(need, up16(fhe_ggsws_ws_bytes(&p, Q, pl.x.seg.v[i].B, D, L)));
+      rows = std::max(rows, (size_t)Q * (size_t)pl.x.seg.v[i].B);
     }
     rc = reserve(ctx, ctx->xp_ws, need + 8 * rows * n1, FHE_E_DEVICE, "hipMalloc of the ggsw product workspace failed");
     if (rc) return rc;
     u64* compact = (u64*)((char*)ctx->xp_ws.p + need);
-    for (int i = 0; i < pl.ns; ++i) {
-      const XqGrpTenant& e = pl.seg.v[i];
+    for (int i = 0; i < pl.x.ns; ++i) {
+      const XqGrpTenant& e = pl.x.seg.v[i];
       if ((rc = linear_ggsws_impl(ctx, e.ggsw, L, e.F, Q, e.B, D, h_cst, cst, h_T, compact, st))) return rc;
       hipLaunchKernelGGL(k_xq_gens_scatter, dim3((unsigned)(Q * e.B), (unsigned)((n1 + 255) / 256)), dim3(256), 0, st,
                          (const u64*)compact, (int64_t)e.B, e.start, pl.B, n1, d_out);
@@ -5338,39 +5386,18 @@ static int linear_ggsws_gens_impl(fhe_ctx* ctx, const fhe_ggsw_gen* gens, const 
     return FHE_OK;
   }
 #endif
-  rc = reserve(ctx, ctx->xp_ws, pl.bytes, FHE_E_DEVICE, "hipMalloc of the ggsw product workspace failed");
+  rc = reserve(ctx, ctx->xp_ws, pl.x.bytes, FHE_E_DEVICE, "hipMalloc of the ggsw product workspace failed");
   if (rc) return rc;
-  char* ws = (char*)ctx->xp_ws.p;
-  v4i* P8 = (v4i*)ws;
-  u64* Mall = (u64*)(ws + pl.off_M);
-  u64* d_cst = (u64*)(ws + pl.off_cst);
-  XqGrpTenant* ten = (XqGrpTenant*)(ws + pl.off_ten);
-  XqGrpTile* tiles = (XqGrpTile*)(ws + pl.off_tiles);
-  int32_t* rtt = (int32_t*)(ws + pl.off_rt);
-  int64_t* ends = (int64_t*)(ws + pl.off_ends);
-  if ((rc = store_scaled_csts(ctx, d_cst, Q, h_cst, cst, h_T, st))) return rc;
-  hipEvent_t e1;
-  prof_begin(ctx, ctx->prof_xq, st, &e1);
-  ctx->prof_xq.kernel = pl.RT == 2 ? "k_extprod_queries_mfma_grp<2>" : "k_extprod_queries_mfma_grp<1>";
-  const int64_t nth = std::max(std::max(pl.ntiles, pl.nrt), (int64_t)pl.ns);
-  hipLaunchKernelGGL(k_xq_gens_tables, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, st, pl.seg, pl.ns, p.N,
-                     pl.RT, pl.rtp, pl.ntiles, ten, tiles, rtt, ends);
-  if (pl.Sk > 1) HIPCHK(ctx, hipMemsetAsync(Mall, 0, 8 * (size_t)pl.mwords, st));
-  hipLaunchKernelGGL(k_ggsws_planes_grp, dim3((unsigned)(pl.nrt * pl.KB)), dim3(64), 0, st, (const XqGrpTenant*)ten,
-                     (const int32_t*)rtt, p.N, p.k, (int)L, pl.KB, P8);
-  const dim3 grid((unsigned)pl.ntiles, 1, (unsigned)pl.Sk);
-  if (pl.RT == 2)
-    hipLaunchKernelGGL(k_extprod_queries_mfma_grp<2>, grid, dim3(256), 0, st, (const XqGrpTile*)tiles,
-                       (const XqGrpTenant*)ten, (const v4i*)P8, p.N, p.k, (int)L, pl.KB, pl.kslice, Mall);
-  else
-    hipLaunchKernelGGL(k_extprod_queries_mfma_grp<1>, grid, dim3(256), 0, st, (const XqGrpTile*)tiles,
-                       (const XqGrpTenant*)ten, (const v4i*)P8, p.N, p.k, (int)L, pl.KB, pl.kslice, Mall);
-  hipLaunchKernelGGL(k_extprod_extract_gens, dim3((unsigned)(Q * pl.B), (unsigned)((p.k * p.N + 256) / 256)),
-                     dim3(256), 0, st, (const u64*)Mall, (const XqGrpTenant*)ten, (const int64_t*)ends, pl.ns, pl.B,
-                     p.N, p.k, (const u64*)d_cst, d_out);
-  prof_end(ctx, ctx->prof_xq, st, e1, Q * pl.B);
-  HIPCHK(ctx, hipGetLastError());
-  return FHE_OK;
+  void* ws = ctx->xp_ws.p;
+  if ((rc = store_scaled_csts(ctx, pl.x.at(ws).cst, Q, h_cst, cst, h_T, st))) return rc;
+  return xq_launch(
+      ctx, pl.x, ws, Q * pl.B,
+      [&](const XqWs& w) {
+        hipLaunchKernelGGL(k_extprod_extract_gens, dim3((unsigned)(Q * pl.B), (unsigned)((p.k * p.N + 256) / 256)),
+                           dim3(256), 0, st, (const u64*)w.M, (const XqGrpTenant*)w.ten, (const int64_t*)w.ends,
+                           pl.x.ns, pl.B, p.N, p.k, (const u64*)w.cst, d_out);
+      },
+      st);
 }
 
 int fhe_linear_ggsws_gens_batch(fhe_ctx* ctx, const fhe_ggsw_gen* gens, int32_t G, int32_t base_log, int32_t level,

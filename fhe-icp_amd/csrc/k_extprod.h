@@ -161,31 +161,24 @@ __global__ void __launch_bounds__(64) k_extprod_planes(const u64* __restrict__ g
     const int d = t - u0 - j;  // in (-N, N)
     xs[j] = d >= 0 ? (u64)0 - row[d] : row[d + N];  // -T: T is -row past the wrap
   }
-  uint32_t pk[8][4];
-#pragma unroll
-  for (int q = 0; q < 8; ++q)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) pk[q][e] = 0;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    u64 x = xs[j];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int8_t sq = (int8_t)(x & 0xff);
-      x = (x - (u64)(int64_t)sq) >> 8;
-      pk[q][j >> 2] |= (uint32_t)(uint8_t)sq << (8 * (j & 3));
-    }
-  }
-  v4i* o = out + (size_t)f * 8 * 64 + lane;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) o[q * 64] = (v4i){(int)pk[q][0], (int)pk[q][1], (int)pk[q][2], (int)pk[q][3]};
+  byte_planes16_store(true, [&](int j) { return xs[j]; }, out + (size_t)f * 8 * 64 + lane);
 }
 
-// Sample extraction of one slot per document: document b sits in GLWE
-// g = b / S at coefficient p = (b % S) D of M (the GEMM's G x (k+1)N result),
-//   a_{cN + u} = A_c[p - u] for u <= p, -A_c[p - u + N] otherwise; b = B[p] + cst_scaled,
-// the big LWE (kN + 1 words) fhe_sign_batch and fhe_pack_batch take.
-// Grid (B, ceil((kN + 1) / 256)).
+// Sample extraction of the slot at coefficient p of one GLWE src ((k+1) N
+// words, a row of a GEMM result): word col <= kN of the big LWE (kN + 1 words)
+// fhe_sign_batch and fhe_pack_batch take,
+//   a_{cN + u} = A_c[p - u] for u <= p, -A_c[p - u + N] otherwise; b = B[p] + cst,
+// cst already scaled to the encoding. The one extraction of the four extract
+// kernels (here, k_extprod_q.h, k_extprod_grp.h), which differ in how a row
+// finds its GLWE and its constant and in where it writes.
+__device__ __forceinline__ u64 xq_extract_word(const u64* __restrict__ src, int p, int col, int N, int k, u64 cst) {
+  if (col == k * N) return src[(size_t)k * N + p] + cst;
+  const int c = col / N, u = col - c * N;
+  return u <= p ? src[(size_t)c * N + p - u] : (u64)0 - src[(size_t)c * N + p - u + N];
+}
+
+// One slot per document: document b sits in GLWE g = b / S at coefficient
+// p = (b % S) D of M (the GEMM's G x (k+1)N result). Grid (B, ceil((kN + 1) / 256)).
 __global__ void __launch_bounds__(256) k_extprod_extract(const u64* __restrict__ M, int S, int D, int N, int k,
                                                          u64 cst_scaled, u64* __restrict__ out) {
   const int col = blockIdx.y * 256 + threadIdx.x;
@@ -194,13 +187,5 @@ __global__ void __launch_bounds__(256) k_extprod_extract(const u64* __restrict__
   if (col > big) return;
   const int64_t g = b / S;
   const int p = (int)(b - g * S) * D;
-  const u64* src = M + (size_t)g * (k + 1) * N;
-  u64 v;
-  if (col == big) {
-    v = src[(size_t)k * N + p] + cst_scaled;
-  } else {
-    const int c = col / N, u = col - c * N;
-    v = u <= p ? src[(size_t)c * N + p - u] : (u64)0 - src[(size_t)c * N + p - u + N];
-  }
-  out[(size_t)b * (big + 1) + col] = v;
+  out[(size_t)b * (big + 1) + col] = xq_extract_word(M + (size_t)g * (k + 1) * N, p, col, N, k, cst_scaled);
 }

@@ -1,47 +1,51 @@
-// Group form of the transposed external product (k_extprod_q.h): the leveled
-// step of several key holders in a fixed number of launches.
-// Included by fheicp.hip after k_extprod_q.h and k_blind_rotate.h.
+// Segmented form of the transposed external product (k_extprod_q.h): the
+// leveled step of several key holders, or of several key
+// generations of one holder (§8.19), in a fixed number of launches. Included
+// by fheicp.hip after k_extprod_q.h and k_blind_rotate.h.
 //
-// Tenant t brings its own Q_t GGSW queries and its own document operand F_t
-// (G_t GLWEs); all share (N, k) and the gadget level L, so the K extent
-// KB = (k+1) N L / 64 is one for the launch. The query planes of all tenants
-// lie in one buffer, tenant t's row tiles (16 rows each, padded to whole groups
-// of the launch's RT) from row tile rt0_t on; the results M_t[q][g][c'][t] lie
-// in one buffer from word m0_t on; the extracted rows go to the padded group
-// layout (fhe_group_rows: tenant t's Q_t B_t rows from start_t, query-major).
-// A workgroup finds its work in two tables read at a workgroup-uniform address
-// (scalar loads, as BrGrpTenant and KsGrpBlock are): its tile, and through it
-// the tenant's record.
+// Segment t (a tenant, or a generation with documents) brings its own Q_t GGSW
+// queries and its own document operand F_t (G_t GLWEs); all share (N, k) and
+// the gadget level L, so the K extent KB = (k+1) N L / 64 is one for the
+// launch. The query planes of all segments lie in one buffer, segment t's row
+// tiles (16 rows each, padded to whole groups of the launch's RT) from row
+// tile rt0_t on; the results M_t[q][g][c'][t] lie in one buffer from word m0_t
+// on. A workgroup finds its work in two tables read at a workgroup-uniform
+// address (scalar loads, as BrGrpTenant and KsGrpBlock are): its tile, and
+// through it the segment's record. The tables, the planes and the GEMM are one
+// for both forms; the extraction differs in where a row goes:
+//   tenants      the padded group layout (fhe_group_rows: tenant t's Q_t B_t
+//                rows from start_t, query-major), k_extprod_extract_grp;
+//   generations  ONE query-major Q x B matrix (row q B + off_g + b, off_g the
+//                documents before generation g), the layout the segmented
+//                bridge (k_bridge.h) takes its row map over,
+//                k_extprod_extract_gens. Every generation has the same Q and D.
 #pragma once
-
-// Operands whose pointers come out of a table, in global memory: without the
-// address space the compiler emits flat loads for them, which count against
-// the LDS counter too (k_ks_grp.h's ksm_gv4i).
-typedef __attribute__((address_space(1))) u64 xq_gu64;
-typedef __attribute__((address_space(1))) uint8_t xq_gu8;
-typedef __attribute__((address_space(1))) v4i_dw xq_gv4dw;
-typedef __attribute__((address_space(1))) int xq_gint;
 
 struct XqGrpTenant {
   const u64* ggsw;   // Q GGSWs [Q][c][l][c'][coef]
-  const uint8_t* F;  // fhe_glwe_docs_queries_pack of the tenant's B documents
-  int64_t start;     // first row of the tenant in the padded layout
+  const uint8_t* F;  // fhe_glwe_docs_queries_pack of the segment's B documents
+  int64_t start;     // first row of the tenant in the padded layout; off_g of a generation
   int64_t m0;        // first word of M_t in the result buffer
   int32_t Q, G;
   int32_t B, D;
-  int32_t rt0;       // first row tile of the tenant in the plane buffer
-  int32_t c0;        // first of the tenant's Q scaled constants
+  int32_t rt0;       // first row tile of the segment in the plane buffer
+  int32_t c0;        // first of the segment's Q scaled constants
 };
-// the participating tenants of one call, passed by value to k_xq_grp_tables
-// (64 records of 56 bytes: inside the 4 KB of kernel arguments)
+// The segments of one call, passed by value to k_xq_tables<CAP>: 64 records of
+// 56 bytes are inside the 4 KB of kernel arguments; a call of up to
+// XQ_GENS_MAX segments passes that many (0.5 KB: the 3.5 KB cost the
+// generations' leveled step 0.013 ms of 0.061, docs/AB_LOG_r24.md).
 constexpr int XQ_GRP_MAX = 64;
-struct XqGrpTenants {
-  XqGrpTenant v[XQ_GRP_MAX];
+constexpr int XQ_GENS_MAX = FHE_BRIDGE_SLOTS + 1;  // every bridge slot's generation and the current one
+static_assert(XQ_GENS_MAX <= XQ_GRP_MAX, "the generations of a call are segments of one table");
+template <int CAP>
+struct XqSegs {
+  XqGrpTenant v[CAP];
 };
 struct XqGrpTile {
   int32_t tenant;  // index into the records
-  int32_t cw;      // column workgroup within the tenant (k_extprod_queries_mfma's blockIdx.x)
-  int32_t rg;      // row-tile group within the tenant (its blockIdx.y)
+  int32_t cw;      // column workgroup within the segment (k_extprod_queries_mfma's blockIdx.x)
+  int32_t rg;      // row-tile group within the segment (its blockIdx.y)
   int32_t pad;
 };
 
@@ -52,15 +56,21 @@ __host__ __device__ inline int64_t xq_grp_rtiles(int k, int Q, int RT) {
 __host__ __device__ inline int64_t xq_grp_cgrid(int N, int G) { return (int64_t)G * (N / 16) / XQ_CG; }
 
 // The tables of a call, one thread per entry of the longest: the records
-// themselves, tile -> (tenant, column workgroup, row-tile group) with a
-// tenant's tiles row group after row group, row tile -> tenant for the planes,
-// and row quad -> tenant for the extraction (-1: tenants end before it).
-__global__ void __launch_bounds__(256) k_xq_grp_tables(XqGrpTenants h, int nt, int N, int k, int RT, int64_t ntiles,
-                                                       int64_t nrt, int64_t nquads, XqGrpTenant* __restrict__ ten,
-                                                       XqGrpTile* __restrict__ tiles, int32_t* __restrict__ rt_tenant,
-                                                       int32_t* __restrict__ quad_tenant) {
+// themselves, tile -> (segment, column workgroup, row-tile group) with a
+// segment's tiles row group after row group, row tile -> segment for the
+// planes, and what the form's extraction finds a row's segment by: row quad ->
+// tenant (-1: tenants end before it) when nquads > 0, the segments' document
+// ends when `ends` is given.
+template <int CAP>
+__global__ void __launch_bounds__(256) k_xq_tables(XqSegs<CAP> h, int nt, int N, int k, int RT, int64_t ntiles,
+                                                   int64_t nrt, int64_t nquads, XqGrpTenant* __restrict__ ten,
+                                                   XqGrpTile* __restrict__ tiles, int32_t* __restrict__ rt_tenant,
+                                                   int32_t* __restrict__ quad_tenant, int64_t* __restrict__ ends) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nt) ten[i] = h.v[i];
+  if (i < nt) {
+    ten[i] = h.v[i];
+    if (ends) ends[i] = h.v[i].start + h.v[i].B;
+  }
   if (i < ntiles) {
     int64_t t0 = 0;
     for (int u = 0; u < nt; ++u) {
@@ -87,71 +97,40 @@ __global__ void __launch_bounds__(256) k_xq_grp_tables(XqGrpTenants h, int nt, i
   }
 }
 
-// k_ggsws_planes over the row tiles of all tenants: block (kb, rt) flattened on
+// k_ggsws_planes over the row tiles of all segments: block (kb, rt) flattened on
 // x (rt KB + kb), so no 65,535 bound applies to the row tiles. The tile's
-// tenant gives the GGSWs, Q and its first tile; the fragment order within a
-// tenant is k_ggsws_planes's.
+// segment gives the GGSWs, Q and its first tile; the fragment within a segment
+// is k_ggsws_planes's (ggsws_fragment).
 __global__ void __launch_bounds__(64) k_ggsws_planes_grp(const XqGrpTenant* __restrict__ ten,
                                                          const int32_t* __restrict__ rt_tenant, int N, int k, int L,
                                                          int KB, v4i* __restrict__ out) {
-  const int lane = threadIdx.x;
   const int64_t rtg = blockIdx.x / (unsigned)KB;  // row tile of the launch
   const int kb = (int)(blockIdx.x - rtg * KB);
   const XqGrpTenant e = ten[rt_tenant[rtg]];
-  const xq_gu64* __restrict__ ggsw = (const xq_gu64*)e.ggsw;
-  const int rt = (int)(rtg - e.rt0), kpr = N >> 6;
-  const int cl = kb / kpr, s0 = (kb - cl * kpr) * 64 + 16 * (lane >> 4);
-  const int rho = rt * 16 + (lane & 15);
-  const int q = rho / (k + 1), cp = rho - q * (k + 1);
-  uint32_t pk[8][4];
-#pragma unroll
-  for (int p = 0; p < 8; ++p)
-#pragma unroll
-    for (int e4 = 0; e4 < 4; ++e4) pk[p][e4] = 0;
-  if (q < e.Q) {
-    const xq_gu64* row = ggsw + (((size_t)q * (k + 1) * L + cl) * (k + 1) + cp) * N + s0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      u64 x = row[j];
-#pragma unroll
-      for (int p = 0; p < 8; ++p) {
-        const int8_t sp = (int8_t)(x & 0xff);
-        x = (x - (u64)(int64_t)sp) >> 8;
-        pk[p][j >> 2] |= (uint32_t)(uint8_t)sp << (8 * (j & 3));
-      }
-    }
-  }
-  v4i* o = out + ((size_t)rtg * KB + kb) * 8 * 64 + lane;
-#pragma unroll
-  for (int p = 0; p < 8; ++p) o[p * 64] = (v4i){(int)pk[p][0], (int)pk[p][1], (int)pk[p][2], (int)pk[p][3]};
+  ggsws_fragment((const xq_gu64*)e.ggsw, e.Q, (int)(rtg - e.rt0), kb, N, k, L,
+                 out + ((size_t)rtg * KB + kb) * 8 * 64 + threadIdx.x);
 }
 
-// k_extprod_queries_mfma<RT> over the tiles of all tenants: grid (tiles, 1, S),
+// k_extprod_queries_mfma<RT> over the tiles of all segments: grid (tiles, 1, S),
 // tiles flattened on x, so no 65,535 bound applies to row groups or GLWEs. The
-// tile's record gives the planes, F, Q, G and M of its tenant; from there on
-// the body is k_extprod_queries_mfma's (fragment formation, LDS double buffer,
-// epilogue), copied rather than shared, as k_keyswitch_mfma_grp's is: moved
-// into a common __device__ function, the single-tenant kernels came out of the
-// compiler with other code (docs/AB_LOG_r17.md), and they are what this form
-// is tested against. A row rho >= (k+1) Q_t and a block with g >= G_t store
-// nothing. One S for the launch: atomics into the zeroed results when S > 1,
-// plain stores otherwise.
+// tile's record gives the planes, F, Q, G and M of its segment; from there on
+// the body is k_extprod_queries_mfma's (xq_gemm_tail). A row rho >= (k+1) Q_t
+// and a block with g >= G_t store nothing. One S for the launch: atomics into
+// the zeroed results when S > 1, plain stores otherwise.
 template <int RT>
 __global__ void __launch_bounds__(256, 2) k_extprod_queries_mfma_grp(const XqGrpTile* __restrict__ tiles,
                                                                      const XqGrpTenant* __restrict__ ten,
                                                                      const v4i* __restrict__ P8all, int N, int k,
                                                                      int L, int KB, int kslice,
                                                                      u64* __restrict__ Mall) {
-  constexpr int TV = RT * 8 * 64;   // v4i per query tile (one k-block)
-  constexpr int TL = TV / 256;      // per thread
-  __shared__ v4i at[2][TV];
+  __shared__ v4i at[2][RT * 8 * 64];  // two query tiles (one k-block each)
   const XqGrpTile tl = tiles[blockIdx.x];
   const XqGrpTenant te = ten[tl.tenant];
   const xq_gu8* __restrict__ F = (const xq_gu8*)te.F;
   const int Q = te.Q, G = te.G;
   u64* __restrict__ M = Mall + te.m0;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int kpr = N >> 6, nbg = N >> 4;  // k-blocks per (c, l) row; column blocks per GLWE
+  const int nbg = N >> 4;  // column blocks per GLWE
   const int rt0 = tl.rg * RT;
   const int kb_lo = blockIdx.z * kslice, kb_hi = min(KB, kb_lo + kslice);
   const size_t fs = xq_fstride(N);
@@ -171,95 +150,11 @@ __global__ void __launch_bounds__(256, 2) k_extprod_queries_mfma_grp(const XqGrp
 #endif
     const int o = N - 1 - t[c] + 16 * (lane >> 4);  // + s0 (a multiple of 64) per k-block
     sh[c] = o & 3;
-    // a block past the tenant's batch streams its GLWE 0's digits and stores nothing
+    // a block past the segment's batch streams its GLWE 0's digits and stores nothing
     Fw[c] = F + (size_t)(g[c] < G ? g[c] : 0) * rowsF * fs + (o & ~3);
   }
   const v4i* Pv = P8all + ((size_t)te.rt0 + rt0) * KB * 8 * 64 + tid;
-  v4i acc[RT][XQ_CW][8];
-#pragma unroll
-  for (int h = 0; h < RT; ++h)
-#pragma unroll
-    for (int c = 0; c < XQ_CW; ++c)
-#pragma unroll
-      for (int p = 0; p < 8; ++p) acc[h][c][p] = (v4i){0, 0, 0, 0};
-  v4i ra[TL];
-  v4i_dw fa[XQ_CW];
-  int fb[XQ_CW];
-  // row tile h's fragments of k-block kb are 512 consecutive v4i: two per thread
-  auto tile_load = [&](int kb) {
-#pragma unroll
-    for (int e = 0; e < TL; ++e) ra[e] = Pv[((size_t)(e >> 1) * KB + kb) * 8 * 64 + (e & 1) * 256];
-  };
-  auto tile_store = [&](v4i* dst) {
-#pragma unroll
-    for (int e = 0; e < TL; ++e) dst[(e >> 1) * 512 + (e & 1) * 256 + tid] = ra[e];
-  };
-  auto frag_load = [&](int kb) {
-    const int cl = kb / kpr, s0 = (kb - cl * kpr) * 64;
-#pragma unroll
-    for (int c = 0; c < XQ_CW; ++c) {
-      const xq_gu8* p = Fw[c] + (size_t)cl * fs + s0;
-      fa[c] = *(const xq_gv4dw*)p;
-      fb[c] = *(const xq_gint*)(p + 16);
-    }
-  };
-  tile_load(kb_lo);
-  frag_load(kb_lo);
-  tile_store(at[0]);
-  __syncthreads();
-  int cur = 0;
-  for (int kb = kb_lo; kb < kb_hi; ++kb) {
-    v4i b[XQ_CW];
-#pragma unroll
-    for (int c = 0; c < XQ_CW; ++c) {
-      b[c][0] = (int)__builtin_amdgcn_alignbyte((uint32_t)fa[c][1], (uint32_t)fa[c][0], (uint32_t)sh[c]);
-      b[c][1] = (int)__builtin_amdgcn_alignbyte((uint32_t)fa[c][2], (uint32_t)fa[c][1], (uint32_t)sh[c]);
-      b[c][2] = (int)__builtin_amdgcn_alignbyte((uint32_t)fa[c][3], (uint32_t)fa[c][2], (uint32_t)sh[c]);
-      b[c][3] = (int)__builtin_amdgcn_alignbyte((uint32_t)fb[c], (uint32_t)fa[c][3], (uint32_t)sh[c]);
-    }
-    const int kn = min(kb + 1, kb_hi - 1);  // clamped: the last step reloads its own
-    tile_load(kn);
-    frag_load(kn);
-#pragma unroll
-    for (int h = 0; h < RT; ++h)
-#pragma unroll
-      for (int p = 0; p < 8; ++p) {
-        const v4i a = at[cur][(h * 8 + p) * 64 + lane];
-#pragma unroll
-        for (int c = 0; c < XQ_CW; ++c)
-          acc[h][c][p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b[c], acc[h][c][p], 0, 0, 0);
-      }
-    tile_store(at[cur ^ 1]);
-    __syncthreads();
-    cur ^= 1;
-  }
-  const int rows = (k + 1) * Q;
-  const bool split = gridDim.z > 1;
-#pragma unroll
-  for (int c = 0; c < XQ_CW; ++c) {
-    if (g[c] >= G) continue;
-#pragma unroll
-    for (int h = 0; h < RT; ++h) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int rho = (rt0 + h) * 16 + 4 * (lane >> 4) + r;
-        if (rho >= rows) continue;
-        const int q = rho / (k + 1), cp = rho - q * (k + 1);
-        u64 lo = 0;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) lo += (u64)((int64_t)acc[h][c][p][r] * (int64_t)(1 << (8 * p)));
-        uint32_t hi = 0;
-#pragma unroll
-        for (int p = 4; p < 8; ++p) hi += (uint32_t)acc[h][c][p][r] << (8 * (p - 4));
-        const u64 v = lo + ((u64)hi << 32);
-        u64* dst = M + (((size_t)q * G + g[c]) * (k + 1) + cp) * N + t[c];
-        if (split)
-          atomicAdd((unsigned long long*)dst, (unsigned long long)v);
-        else
-          *dst = v;
-      }
-    }
-  }
+  xq_gemm_tail<RT>(at, Pv, Fw, sh, g, t, rt0, kb_lo, kb_hi, N, k, Q, G, KB, M);
 }
 
 // k_extprod_extract_queries over the padded group rows: row r belongs to the
@@ -287,14 +182,50 @@ __global__ void __launch_bounds__(256) k_extprod_extract_grp(const u64* __restri
   const int64_t g = b / S;
   const int p = (int)(b - g * S) * e.D;
   const u64* src = Mall + e.m0 + ((size_t)q * (size_t)e.G + (size_t)g) * (k + 1) * N;
-  u64 v;
-  if (col == big) {
-    v = src[(size_t)k * N + p] + cst[e.c0 + q];
-  } else {
-    const int c = col / N, u = col - c * N;
-    v = u <= p ? src[(size_t)c * N + p - u] : (u64)0 - src[(size_t)c * N + p - u + N];
-  }
+  const u64 v = xq_extract_word(src, p, col, N, k, cst[e.c0 + q]);
   const size_t at = (size_t)r * (big + 1) + col;
   out[at] = v;
   if (cpy) cpy[at] = v;
 }
+
+// k_extprod_extract_queries over the Q x B rows of all generations: row
+// r = q B + x is document x of the call under query q. Its segment is the
+// first whose end lies beyond x (the ends table, read at a workgroup-uniform
+// address: a workgroup is one row); within the segment it is document
+// b = x - off_g, read from M_g with k_extprod_extract_grp's index arithmetic,
+// cst[q] (pre-scaled) on the body. Grid (Q B, ceil((kN + 1) / 256)): no row
+// beyond Q B exists, a thread per word of the row, consecutive threads
+// consecutive words.
+__global__ void __launch_bounds__(256) k_extprod_extract_gens(const u64* __restrict__ Mall,
+                                                              const XqGrpTenant* __restrict__ ten,
+                                                              const int64_t* __restrict__ ends, int ns, int64_t B,
+                                                              int N, int k, const u64* __restrict__ cst,
+                                                              u64* __restrict__ out) {
+  const int col = blockIdx.y * 256 + threadIdx.x;
+  const int64_t r = blockIdx.x;
+  const int big = k * N;
+  if (col > big) return;
+  const int64_t q = r / B, x = r - q * B;
+  int s = 0;
+  while (s + 1 < ns && ends[s] <= x) ++s;
+  const XqGrpTenant e = ten[s];
+  const int64_t b = x - e.start;
+  const int S = N / e.D;
+  const int64_t g = b / S;
+  const int p = (int)(b - g * S) * e.D;
+  const u64* src = Mall + e.m0 + ((size_t)q * (size_t)e.G + (size_t)g) * (k + 1) * N;
+  out[(size_t)r * (big + 1) + col] = xq_extract_word(src, p, col, N, k, cst[q]);
+}
+
+#if !FHEICP_GRP_XGENS
+// -DFHEICP_GRP_XGENS=0 builds: a generation's compact Q x B_g rows (what
+// fhe_linear_ggsws_batch writes) into rows q B + off + b of the call's matrix.
+// Grid (Q B_g, ceil((kN + 1) / 256)).
+__global__ void __launch_bounds__(256) k_xq_gens_scatter(const u64* __restrict__ src, int64_t Bg, int64_t off,
+                                                         int64_t B, int n1, u64* __restrict__ out) {
+  const int col = blockIdx.y * 256 + threadIdx.x;
+  if (col >= n1) return;
+  const int64_t r = blockIdx.x, q = r / Bg, b = r - q * Bg;
+  out[(size_t)(q * B + off + b) * n1 + col] = src[(size_t)r * n1 + col];
+}
+#endif

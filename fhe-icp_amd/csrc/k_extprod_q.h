@@ -57,35 +57,23 @@ __global__ void __launch_bounds__(256) k_glwe_digits_rev(const u64* __restrict__
 // rho = 16 rt + (lane & 15) = q (k+1) + c', k-block kb = (c L + l) N / 64 + s / 64,
 // and lane holds s = 64 (kb % (N / 64)) + 16 (lane >> 4) + j in byte j. Rows
 // from (k+1) Q up to the padded tile are written as zeros. One thread per
-// fragment lane; grid (KB, RT), 64 threads.
-__global__ void __launch_bounds__(64) k_ggsws_planes(const u64* __restrict__ ggsw, int N, int k, int L, int Q,
-                                                     v4i* __restrict__ out) {
-  const int lane = threadIdx.x, kb = blockIdx.x, rt = blockIdx.y;
-  const int KB = gridDim.x, kpr = N >> 6;
+// fragment lane: ggsws_fragment is this lane's part of fragment (rt, kb), o
+// the fragment's first plane at this lane. GP: const u64*, or const xq_gu64*
+// for GGSWs whose pointer came out of a table (k_extprod_grp.h).
+template <typename GP>
+__device__ __forceinline__ void ggsws_fragment(GP ggsw, int Q, int rt, int kb, int N, int k, int L, v4i* o) {
+  const int lane = threadIdx.x, kpr = N >> 6;
   const int cl = kb / kpr, s0 = (kb - cl * kpr) * 64 + 16 * (lane >> 4);
   const int rho = rt * 16 + (lane & 15);
   const int q = rho / (k + 1), cp = rho - q * (k + 1);
-  uint32_t pk[8][4];
-#pragma unroll
-  for (int p = 0; p < 8; ++p)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) pk[p][e] = 0;
-  if (q < Q) {
-    const u64* row = ggsw + (((size_t)q * (k + 1) * L + cl) * (k + 1) + cp) * N + s0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      u64 x = row[j];
-#pragma unroll
-      for (int p = 0; p < 8; ++p) {
-        const int8_t sp = (int8_t)(x & 0xff);
-        x = (x - (u64)(int64_t)sp) >> 8;
-        pk[p][j >> 2] |= (uint32_t)(uint8_t)sp << (8 * (j & 3));
-      }
-    }
-  }
-  v4i* o = out + ((size_t)rt * KB + kb) * 8 * 64 + lane;
-#pragma unroll
-  for (int p = 0; p < 8; ++p) o[p * 64] = (v4i){(int)pk[p][0], (int)pk[p][1], (int)pk[p][2], (int)pk[p][3]};
+  const GP row = ggsw + (((size_t)q * (k + 1) * L + cl) * (k + 1) + cp) * N + s0;
+  byte_planes16_store(q < Q, [&](int j) { return row[j]; }, o);
+}
+// Grid (KB, RT), 64 threads.
+__global__ void __launch_bounds__(64) k_ggsws_planes(const u64* __restrict__ ggsw, int N, int k, int L, int Q,
+                                                     v4i* __restrict__ out) {
+  const int kb = blockIdx.x, rt = blockIdx.y, KB = gridDim.x;
+  ggsws_fragment(ggsw, Q, rt, kb, N, k, L, out + ((size_t)rt * KB + kb) * 8 * 64 + threadIdx.x);
 }
 
 // The GEMM. Workgroup = 4 waves = RT row tiles (16 RT rows (q, c')) x 8 column
@@ -116,39 +104,34 @@ __global__ void __launch_bounds__(64) k_ggsws_planes(const u64* __restrict__ ggs
 #endif
 constexpr int XQ_CW = FHEICP_XQ_CW, XQ_WAVES = 4, XQ_CG = XQ_CW * XQ_WAVES;  // column blocks per wave / workgroup
 typedef int v4i_dw __attribute__((ext_vector_type(4), aligned(4)));
-template <int RT>
-__global__ void __launch_bounds__(256, 2) k_extprod_queries_mfma(const v4i* __restrict__ P8,
-                                                                 const uint8_t* __restrict__ F, int N, int k, int L,
-                                                                 int Q, int G, int KB, int kslice,
-                                                                 u64* __restrict__ M) {
-  constexpr int TV = RT * 8 * 64;   // v4i per query tile (one k-block)
-  constexpr int TL = TV / 256;      // per thread
-  __shared__ v4i at[2][TV];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int kpr = N >> 6, nbg = N >> 4;  // k-blocks per (c, l) row; column blocks per GLWE
-  const int rt0 = blockIdx.y * RT;
-  const int kb_lo = blockIdx.z * kslice, kb_hi = min(KB, kb_lo + kslice);
+// Operands whose pointers come out of a table (k_extprod_grp.h), in global
+// memory: without the address space the compiler emits flat loads for them,
+// which count against the LDS counter too (k_ks_grp.h's ksm_gv4i).
+typedef __attribute__((address_space(1))) u64 xq_gu64;
+typedef __attribute__((address_space(1))) uint8_t xq_gu8;
+typedef __attribute__((address_space(1))) v4i_dw xq_gv4dw;
+typedef __attribute__((address_space(1))) int xq_gint;
+// a lane's five dwords of F, for either kind of pointer
+__device__ __forceinline__ v4i_dw xq_ld16(const uint8_t* p) { return *(const v4i_dw*)p; }
+__device__ __forceinline__ int xq_ld4(const uint8_t* p) { return *(const int*)p; }
+__device__ __forceinline__ v4i_dw xq_ld16(const xq_gu8* p) { return *(const xq_gv4dw*)p; }
+__device__ __forceinline__ int xq_ld4(const xq_gu8* p) { return *(const xq_gint*)p; }
+
+// The body of both GEMM kernels, after the prologue in which a kernel finds
+// its work (from the grid here, from the tile table in k_extprod_grp.h): the
+// LDS double buffer, the fragment formation, the main loop over the k-blocks
+// kb_lo .. kb_hi - 1 and the epilogue. Pv: the planes of row tile rt0 at this
+// thread; Fw[c] (FP: const uint8_t* or const xq_gu8*), sh[c], g[c], t[c]: the
+// window start, byte shift, GLWE and coefficient of this wave's column block c.
+template <int RT, typename FP>
+__device__ __forceinline__ void xq_gemm_tail(v4i (&at)[2][RT * 8 * 64], const v4i* Pv, const FP (&Fw)[XQ_CW],
+                                             const int (&sh)[XQ_CW], const int (&g)[XQ_CW], const int (&t)[XQ_CW],
+                                             int rt0, int kb_lo, int kb_hi, int N, int k, int Q, int G, int KB,
+                                             u64* __restrict__ M) {
+  constexpr int TL = RT * 8 * 64 / 256;  // v4i of a query tile per thread
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int kpr = N >> 6;  // k-blocks per (c, l) row
   const size_t fs = xq_fstride(N);
-  const int rowsF = (k + 1) * L;
-  // this wave's column blocks
-  int g[XQ_CW], t[XQ_CW], sh[XQ_CW];
-  const uint8_t* Fw[XQ_CW];
-#pragma unroll
-  for (int c = 0; c < XQ_CW; ++c) {
-    const int nb = (blockIdx.x * XQ_WAVES + w) * XQ_CW + c;
-    g[c] = nb / nbg;
-    const int rem = nb - g[c] * nbg;
-#ifdef FHEICP_XQ_STRIDE16
-    t[c] = 256 * (rem >> 4) + (rem & 15) + 16 * (lane & 15);
-#else
-    t[c] = 16 * rem + (lane & 15);
-#endif
-    const int o = N - 1 - t[c] + 16 * (lane >> 4);  // + s0 (a multiple of 64) per k-block
-    sh[c] = o & 3;
-    // a block past the batch streams GLWE 0's digits and stores nothing
-    Fw[c] = F + (size_t)(g[c] < G ? g[c] : 0) * rowsF * fs + (o & ~3);
-  }
-  const v4i* Pv = P8 + (size_t)rt0 * KB * 8 * 64 + tid;
   v4i acc[RT][XQ_CW][8];
 #pragma unroll
   for (int h = 0; h < RT; ++h)
@@ -172,9 +155,9 @@ __global__ void __launch_bounds__(256, 2) k_extprod_queries_mfma(const v4i* __re
     const int cl = kb / kpr, s0 = (kb - cl * kpr) * 64;
 #pragma unroll
     for (int c = 0; c < XQ_CW; ++c) {
-      const uint8_t* p = Fw[c] + (size_t)cl * fs + s0;
-      fa[c] = *(const v4i_dw*)p;
-      fb[c] = *(const int*)(p + 16);
+      const FP p = Fw[c] + (size_t)cl * fs + s0;
+      fa[c] = xq_ld16(p);
+      fb[c] = xq_ld4(p + 16);
     }
   };
   tile_load(kb_lo);
@@ -236,6 +219,40 @@ __global__ void __launch_bounds__(256, 2) k_extprod_queries_mfma(const v4i* __re
   }
 }
 
+template <int RT>
+__global__ void __launch_bounds__(256, 2) k_extprod_queries_mfma(const v4i* __restrict__ P8,
+                                                                 const uint8_t* __restrict__ F, int N, int k, int L,
+                                                                 int Q, int G, int KB, int kslice,
+                                                                 u64* __restrict__ M) {
+  __shared__ v4i at[2][RT * 8 * 64];  // two query tiles (one k-block each)
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nbg = N >> 4;  // column blocks per GLWE
+  const int rt0 = blockIdx.y * RT;
+  const int kb_lo = blockIdx.z * kslice, kb_hi = min(KB, kb_lo + kslice);
+  const size_t fs = xq_fstride(N);
+  const int rowsF = (k + 1) * L;
+  // this wave's column blocks
+  int g[XQ_CW], t[XQ_CW], sh[XQ_CW];
+  const uint8_t* Fw[XQ_CW];
+#pragma unroll
+  for (int c = 0; c < XQ_CW; ++c) {
+    const int nb = (blockIdx.x * XQ_WAVES + w) * XQ_CW + c;
+    g[c] = nb / nbg;
+    const int rem = nb - g[c] * nbg;
+#ifdef FHEICP_XQ_STRIDE16
+    t[c] = 256 * (rem >> 4) + (rem & 15) + 16 * (lane & 15);
+#else
+    t[c] = 16 * rem + (lane & 15);
+#endif
+    const int o = N - 1 - t[c] + 16 * (lane >> 4);  // + s0 (a multiple of 64) per k-block
+    sh[c] = o & 3;
+    // a block past the batch streams GLWE 0's digits and stores nothing
+    Fw[c] = F + (size_t)(g[c] < G ? g[c] : 0) * rowsF * fs + (o & ~3);
+  }
+  const v4i* Pv = P8 + (size_t)rt0 * KB * 8 * 64 + tid;
+  xq_gemm_tail<RT>(at, Pv, Fw, sh, g, t, rt0, kb_lo, kb_hi, N, k, Q, G, KB, M);
+}
+
 // k_extprod_extract with the query on the grid: row q B + b of out is document
 // b under query q (M + q G (k+1) N), with cst[q] (device, pre-scaled) on the
 // body. Grid (B, ceil((kN + 1) / 256), Q).
@@ -250,12 +267,5 @@ __global__ void __launch_bounds__(256) k_extprod_extract_queries(const u64* __re
   const int64_t g = b / S;
   const int p = (int)(b - g * S) * D;
   const u64* src = M + (q * (size_t)G + (size_t)g) * (k + 1) * N;
-  u64 v;
-  if (col == big) {
-    v = src[(size_t)k * N + p] + cst[q];
-  } else {
-    const int c = col / N, u = col - c * N;
-    v = u <= p ? src[(size_t)c * N + p - u] : (u64)0 - src[(size_t)c * N + p - u + N];
-  }
-  out[(q * (size_t)B + (size_t)b) * (big + 1) + col] = v;
+  out[(q * (size_t)B + (size_t)b) * (big + 1) + col] = xq_extract_word(src, p, col, N, k, cst[q]);
 }

@@ -60,32 +60,16 @@ __global__ void __launch_bounds__(64) k_query_planes(const u64* __restrict__ ct,
   const int kb = f / NB, nb = f - kb * NB;
   const int col = nb * 16 + (lane & 15);
   const int r0 = kb * 64 + 16 * (lane >> 4);
-  uint32_t pk[8][4];
-#pragma unroll
-  for (int q = 0; q < 8; ++q)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) pk[q][i] = 0;
-  if (col < W && r0 < D) {
-    u64 xs[16];
+  const bool live = col < W && r0 < D;
+  u64 xs[16];
+  if (live) {
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       const int r = min(r0 + j, D - 1);
       xs[j] = ct[(size_t)r * W + col] * (r0 + j < D ? (u64)w[r] : (u64)0);
     }
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      u64 x = xs[j];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int8_t sq = (int8_t)(x & 0xff);
-        x = (x - (u64)(int64_t)sq) >> 8;
-        pk[q][j >> 2] |= (uint32_t)(uint8_t)sq << (8 * (j & 3));
-      }
-    }
   }
-  v4i* o = out + ((size_t)kb * NB + nb) * 8 * 64 + lane;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) o[q * 64] = (v4i){(int)pk[q][0], (int)pk[q][1], (int)pk[q][2], (int)pk[q][3]};
+  byte_planes16_store(live, [&](int j) { return xs[j]; }, out + ((size_t)kb * NB + nb) * 8 * 64 + lane);
 }
 
 // The GEMM. A wave owns LQ_RB 16-document groups x LQ_CB 16-column blocks x

@@ -138,6 +138,34 @@ __global__ void k_ksk_colsum(const u64* __restrict__ ksk, int rows, int n, int R
 typedef int v4i __attribute__((ext_vector_type(4)));
 constexpr int KSM_NB_COLS = 16;  // columns per block
 
+// A fragment lane's 16 words word(0..15) as their 8 balanced byte planes,
+// x = sum_p s_p 2^(8p) with s_p in [-128, 127] (the last carry dropped: it is
+// a multiple of 2^64), word j in byte j of plane p's fragment o[64 p]; zeros
+// when the lane is not live (word is then not called). The one split of the
+// plane kernels of k_query.h, k_extprod.h, k_extprod_q.h and k_extprod_grp.h.
+template <typename Word>
+__device__ __forceinline__ void byte_planes16_store(bool live, Word&& word, v4i* o) {
+  uint32_t pk[8][4];
+#pragma unroll
+  for (int p = 0; p < 8; ++p)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) pk[p][e] = 0;
+  if (live) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      u64 x = word(j);
+#pragma unroll
+      for (int p = 0; p < 8; ++p) {
+        const int8_t sp = (int8_t)(x & 0xff);
+        x = (x - (u64)(int64_t)sp) >> 8;
+        pk[p][j >> 2] |= (uint32_t)(uint8_t)sp << (8 * (j & 3));
+      }
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < 8; ++p) o[p * 64] = (v4i){(int)pk[p][0], (int)pk[p][1], (int)pk[p][2], (int)pk[p][3]};
+}
+
 // key planes: [kb][nb][q][lane][16 B], q < QP. The GEMM's K runs level-major,
 // k = l * big + i (a k-block of 64 is 64 consecutive input coefficients of
 // one level, for any ks_level); the KSK itself is stored [i][l][n+1].

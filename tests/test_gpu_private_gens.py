@@ -130,6 +130,44 @@ def test_linear_gens_old_generations_only(toy):
     np.testing.assert_array_equal(got, PG.scatter_gens(per, Qn, Bs, eng.W))
 
 
+@pytest.mark.parametrize("Qn,D,B,rt", [
+    (6, 5, 55, 2),      # 18 product rows: RT = 2 with padded rows; S = 51, a partial second GLWE; K split, atomics
+    (1, 256, 140, 1),   # RT = 1; 140 GLWEs, 280 tiles: the K split is off, plain stores
+], ids=["q6d5b55", "q1d256b140"])
+def test_context_entry_is_the_group_entry_of_one_tenant(toy, Qn, D, B, rt):
+    """The two callers of the segmented launcher agree: one generation under
+    slot -1 through fhe_linear_ggsws_gens_batch, and a group of this one
+    context through fhe_linear_ggsws_group_batch, on the same GGSWs, documents
+    and constants. The first Q B rows are equal words; the context entry's row
+    Q B keeps its canary, the group's rows from Q B on (its padding up to M and
+    four more) their sentinel."""
+    from fheicp.engine import EngineGroup, group_rows
+    eng, _ = toy
+    (ggsws, _, docs, _), = random_operands(eng, np.random.default_rng(24 * Qn + D), Qn, D, [B])
+    gg = dev_u64(eng, ggsws)
+    csts = CSTS[:Qn]
+    n = Qn * B
+    M, starts = group_rows([n])
+    assert starts == [0] and M >= n
+    a = torch.full((n + 1, eng.W), CANARY, dtype=torch.int64, device=eng.device)
+    b = torch.full((M + 4, eng.W), CANARY + 1, dtype=torch.int64, device=eng.device)
+    eng.linear_ggsws_gens([(-1, gg, docs, B)], BETA, LV, D, csts, out=a)
+    if GROUPED:
+        assert eng.kernel_name("linear_ggsws") == f"k_extprod_queries_mfma_grp<{rt}>"
+    grp = EngineGroup([eng])
+    try:
+        grp.linear_ggsws([(gg.reshape(-1), BETA, LV, docs, B, D)], [csts], out=b)
+        assert eng.kernel_name("linear_ggsws") == f"k_extprod_queries_mfma_grp<{rt}>"
+        torch.cuda.synchronize()
+    finally:
+        grp.close()
+    ga, gb = u64(a), u64(b)
+    assert np.array_equal(ga[:n], gb[:n])
+    assert (ga[:n, -1] != U(CANARY)).any()                             # the rows were written
+    assert (ga[n] == U(CANARY)).all()
+    assert (gb[n:] == U(CANARY + 1)).all()
+
+
 # ----------------------------------------------------------- search entry --
 def encrypted_operands(eng, rng, Qn, D, Bs):
     """Valid encryptions under the context's own key: the search entry's sign
